@@ -1,6 +1,16 @@
 """Headline benchmark: vectorised racing-env steps on MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu E] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu E] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up, runs the
+untimed steps, times the --steps production steps, writes the last timed step's
+outputs where --dump-outputs DIR is given (DIR/obs.npy, reward.npy, done.npy,
+float32; the seeds are fixed, so the same arguments give the same inputs in
+every run and two builds can be compared output for output) and prints the
+result line.  Everything else described below -- the CPU baseline, the
+instrumented and counter steps with the rooflines, the stress / async / GAE /
+PPO / self-play / time-to-90 legs -- runs only with --full, after the timed
+region (the CPU baseline before it), and adds its entries to the same line.
 
 Workload = BASELINE.json configs[2] ("65536 parallel single-agent envs,
 1xMI355X"): the reference's seed-1 track pool (train.py:67-80:
@@ -21,7 +31,7 @@ policy kernels, BASELINE configs[1] as named, at N = 1).  With N GPUs
 (torch.distributed.run, one rank per GPU) every rank owns 65,536 envs of a
 N*65,536-env pool (weak scaling, configs[4]); the env step has no collective.
 
-Order of a run: CPU baseline (host only, before the GPU is touched), at
+Order of a --full run: CPU baseline (host only, before the GPU is touched), at
 least --burn-in untimed steps (the steady state: cars spread over their tracks,
 episodes ending and resetting), the timed region of --steps production steps
 (one rx_step each, nothing instrumented), then --profile-steps instrumented
@@ -767,11 +777,42 @@ def launch_selftest(args, world, rank, local):
     return 0
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, envs, rank):
+    """--dump-outputs: what the timed path returned for its last step -- obs
+    [N, obs_dim], reward [N], done [N] (float32, env order; stream groups
+    concatenated) -- as path/<name>.npy (rank r > 0: <name>_rank<r>.npy).  Above
+    64 MB in all, the same seeded sample of env rows is kept of every array."""
+    arrs = {k: torch.cat([e.buf[b].reshape(e.num_envs, -1) for e in envs]).cpu().numpy().astype(np.float32)
+            for k, b in (("obs", "obs"), ("reward", "reward"), ("done", "done_f32"))}
+    n = arrs["obs"].shape[0]
+    row_bytes = sum(a.nbytes for a in arrs.values()) // n
+    rows = None
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    for k, a in arrs.items():
+        a = a if rows is None else a[rows]
+        np.save(os.path.join(path, k + sfx + ".npy"), a[:, 0] if k != "obs" else a)
+    return {"files": [k + sfx + ".npy" for k in arrs], "envs": n if rows is None else len(rows),
+            "sampled": rows is not None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baseline, the instrumented and "
+                         "counter steps (per-kernel durations, rooflines, executed work) and the stress, async, GAE, "
+                         "PPO, RCCL world-1, self-play and time-to-90 legs (each still has its own switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (obs, reward, done) as "
+                         "DIR/<name>.npy (float32)")
     ap.add_argument("--burn-in", type=int, default=100,
                     help="untimed steps before the timed region counted together with --warmup: at least this many "
                          "(a run that starts with every car on its start line is not the steady state)")
@@ -859,7 +900,8 @@ def main():
     n_total = E * world
     pool, widths = seed1_pool(n_total)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:  # host-only work first: no process here has touched the GPU yet
+    # host-only work first: no process here has touched the GPU yet
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(pool, widths, budget_s=args.cpu_budget)
 
     ndev = torch.cuda.device_count()
@@ -1061,12 +1103,14 @@ def main():
     else:
         elapsed = timed(one_step, args.steps, collect=refill == 0)
     ep = [sum(x) for x in zip(*(e.episode_stats() for e in envs))]
+    dumped = dump_outputs(args.dump_outputs, envs, rank) if args.dump_outputs else None
+    full = args.full
     # ---- instrumented region (after, same state distribution): per-kernel durations of the
     # production launches (k_kin1, k_step2) on every other step; on the others the dynamics
     # phase and the raycast run as separate launches so the raycast has a duration of its own
     prof = {}
     waves = None
-    if args.profile_steps > 0:
+    if full and args.profile_steps > 0:
         events = {k: ("step" if k % 2 == 0 else "split") for k in range(args.profile_steps)}
         mark("instrumented_begin")
         env0.profile(1)
@@ -1078,7 +1122,7 @@ def main():
     # ---- executed-work counters (after timing): per ray wave its box tests and leaf scans,
     # per REWARD wave its waypoint-box tests and leaf scans (rx_io.counters, one atomic per wave)
     work = None
-    if args.counter_steps > 0 and G == 1:
+    if full and args.counter_steps > 0 and G == 1:
         mark("counters_begin")
         env0.enable_counters(True)
         for _ in range(args.counter_steps):
@@ -1101,11 +1145,11 @@ def main():
     for e in envs:
         e.close()
     stress = None
-    if args.stress == "on" and rank == 0:
+    if full and args.stress == "on" and rank == 0:
         stress = stress_leg(dev, args.stress_envs or E, args.steps, untimed, sched)
     async_probe = None
     Ga = args.async_probe_groups
-    if Ga > 1 and E % Ga == 0 and Ga != G:
+    if full and Ga > 1 and E % Ga == 0 and Ga != G:
         a_envs, a_step, _ = make_groups(Ga)
         for _ in range(untimed):
             a_step()
@@ -1116,44 +1160,31 @@ def main():
                                "timed after the main region, not the headline value"}
         for e in a_envs:
             e.close()
-    gae = gae_roofline(E, dev) if rank == 0 else None
+    gae = gae_roofline(E, dev) if full and rank == 0 else None
     if gae is not None:
         gae["cache_resident_T128"] = gae_roofline(E, dev, T=128)
     ppo = ppo_leg(world, rank, dev, dist, args.dist_backend, args.ppo_envs_per_gpu, args.ppo_steps,
-                  args.ppo_updates) if args.ppo_updates > 0 else None
+                  args.ppo_updates) if full and args.ppo_updates > 0 else None
     # BASELINE configs[1] is named "PPO bf16": the same leg with the bf16 policy kernels
     # (bf16 MFMA operands, f32 accumulation, f32 master weights / Adam), at N = 1 only
     ppo_bf16 = ppo_leg(world, rank, dev, dist, args.dist_backend, args.ppo_envs_per_gpu, args.ppo_steps,
-                       args.ppo_updates, "bf16") if args.ppo_updates > 0 and world == 1 else None
+                       args.ppo_updates, "bf16") if full and args.ppo_updates > 0 and world == 1 else None
     rccl1 = None
-    if args.ppo_updates > 0 and world == 1 and args.rccl_world1 == "on":
+    if full and args.ppo_updates > 0 and world == 1 and args.rccl_world1 == "on":
         try:
             rccl1 = rccl_world1_leg(dev, args.ppo_envs_per_gpu, args.ppo_steps, args.ppo_updates)
         except Exception as e:  # noqa: BLE001 -- reported in the line, the headline is unaffected
             rccl1 = {"error": f"{type(e).__name__}: {e}"[:400]}
     sp = None
-    if args.selfplay_updates > 0 and world == 1:
+    if full and args.selfplay_updates > 0 and world == 1:
         sp = selfplay_leg(dev, args.selfplay_envs, args.ppo_steps, args.selfplay_updates)
     tt90 = None
-    if world == 1 and not args.no_time_to_90:
+    if full and world == 1 and not args.no_time_to_90:
         # configs[1] is named "PPO bf16": its 4,096-env entry runs in both precisions
         tt90 = time_to_90([(16, 2048, "numpy"), (4096, 128, "device"), (4096, 128, "device", "bf16")])
 
     if rank == 0:
         value = n_total * args.steps / elapsed
-        ms = lambda k: prof[k][0] if k in prof else float("nan")  # noqa: E731
-        step2_ms, kin_ms, ray_ms = ms("k_step2"), ms("k_kin1"), ms("k_rays")
-        pmc = load_pmc(n)
-        step2_gbs = STEP2_BYTES_PER_ENV * n / (step2_ms * 1e-3) / 1e9
-        ray_gbs = RAYS_BYTES_PER_ENV * n / (ray_ms * 1e-3) / 1e9
-        roof = {"bound": "hbm", "kernel": "k_step2", "achieved": round(step2_gbs, 3),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": step2_gbs / HBM_PEAK_GBS,
-                "traffic": pmc.get("k_step2", {}).get("hbm_bytes_per_launch"),
-                "traffic_source": pmc.get("source"),
-                "bytes_per_env": STEP2_BYTES_PER_ENV, "envs_per_launch": n,
-                "avg_launch_ms": round(step2_ms, 5),
-                "note": "the step is VALU-bound (branchy f64 ray/segment math): the HBM fraction is "
-                        "expected to be tiny; see compute_roofline"}
         out = {
             "metric": "env-steps/sec (whole node) @65536 envs",
             "value": round(value, 1),
@@ -1192,33 +1223,53 @@ def main():
                                          "once untimed)")
                                         if step_graph is not None else
                                         ("one rx_steps call" if multi else "one rx_step call per step from Python"))},
-            # dominant kernel of the production step: k_step2 (REWARD half beside the raycast)
-            "roofline": roof,
-            "compute_roofline": compute_roofline(pmc, {"k_step2": step2_ms, "k_kin1": kin_ms, "k_rays": ray_ms}, n,
-                                                 waves),
-            "executed_work": work,
-            "kernels_ms": {k: round(v[0], 5) for k, v in prof.items()},
-            "kernel_launches": {k: v[1] for k, v in prof.items()},
-            "kernel_timing": f"{args.profile_steps} instrumented steps after the timed region (per-wave device "
-                             "wall-clock stamps, rx_profile: first wave start .. last wave end); even steps record "
-                             "the production launches, odd steps run k_kin1 + k_step2_reward + k_rays so the "
-                             "raycast has its own duration",
-            "k_rays_alone": {"avg_launch_ms": round(ray_ms, 5), "bytes_per_env": RAYS_BYTES_PER_ENV,
-                             "achieved_GBs": round(ray_gbs, 3),
-                             "traffic": pmc.get("k_rays", {}).get("hbm_bytes_per_launch")},
-            "step_roofline": {"kernels": "k_kin1 + k_step2", "avg_step_kernels_ms": round(kin_ms + step2_ms, 5),
-                              "bytes_per_env_step": STEP_BYTES_PER_ENV,
-                              "achieved_GBs": round(STEP_BYTES_PER_ENV * n / ((kin_ms + step2_ms) * 1e-3) / 1e9, 3)},
             "dist": dist_info,
-            "gae": gae,
-            "stress": stress,
-            "async_stream_groups": async_probe,
-            "ppo_train": ppo,
-            "ppo_train_bf16": ppo_bf16,
-            "ppo_train_rccl_world1": rccl1,
-            "selfplay_train": sp,
-            "time_to_90": tt90,
+            "full": full,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if full:
+            ms = lambda k: prof[k][0] if k in prof else float("nan")  # noqa: E731
+            step2_ms, kin_ms, ray_ms = ms("k_step2"), ms("k_kin1"), ms("k_rays")
+            pmc = load_pmc(n)
+            step2_gbs = STEP2_BYTES_PER_ENV * n / (step2_ms * 1e-3) / 1e9
+            ray_gbs = RAYS_BYTES_PER_ENV * n / (ray_ms * 1e-3) / 1e9
+            roof = {"bound": "hbm", "kernel": "k_step2", "achieved": round(step2_gbs, 3),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": step2_gbs / HBM_PEAK_GBS,
+                    "traffic": pmc.get("k_step2", {}).get("hbm_bytes_per_launch"),
+                    "traffic_source": pmc.get("source"),
+                    "bytes_per_env": STEP2_BYTES_PER_ENV, "envs_per_launch": n,
+                    "avg_launch_ms": round(step2_ms, 5),
+                    "note": "the step is VALU-bound (branchy f64 ray/segment math): the HBM fraction is "
+                            "expected to be tiny; see compute_roofline"}
+            out.update({
+                # dominant kernel of the production step: k_step2 (REWARD half beside the raycast)
+                "roofline": roof,
+                "compute_roofline": compute_roofline(pmc, {"k_step2": step2_ms, "k_kin1": kin_ms, "k_rays": ray_ms}, n,
+                                                     waves),
+                "executed_work": work,
+                "kernels_ms": {k: round(v[0], 5) for k, v in prof.items()},
+                "kernel_launches": {k: v[1] for k, v in prof.items()},
+                "kernel_timing": f"{args.profile_steps} instrumented steps after the timed region (per-wave device "
+                                 "wall-clock stamps, rx_profile: first wave start .. last wave end); even steps record "
+                                 "the production launches, odd steps run k_kin1 + k_step2_reward + k_rays so the "
+                                 "raycast has its own duration",
+                "k_rays_alone": {"avg_launch_ms": round(ray_ms, 5), "bytes_per_env": RAYS_BYTES_PER_ENV,
+                                 "achieved_GBs": round(ray_gbs, 3),
+                                 "traffic": pmc.get("k_rays", {}).get("hbm_bytes_per_launch")},
+                "step_roofline": {"kernels": "k_kin1 + k_step2", "avg_step_kernels_ms": round(kin_ms + step2_ms, 5),
+                                  "bytes_per_env_step": STEP_BYTES_PER_ENV,
+                                  "achieved_GBs": round(STEP_BYTES_PER_ENV * n / ((kin_ms + step2_ms) * 1e-3) / 1e9,
+                                                        3)},
+                "gae": gae,
+                "stress": stress,
+                "async_stream_groups": async_probe,
+                "ppo_train": ppo,
+                "ppo_train_bf16": ppo_bf16,
+                "ppo_train_rccl_world1": rccl1,
+                "selfplay_train": sp,
+                "time_to_90": tt90,
+            })
         if cpu is not None:
             out["cpu_baseline"] = cpu
         print(json.dumps(out), flush=True)

@@ -29,6 +29,8 @@ Sets:
                       evaluate.py pool (seed 42, widths by run), driven by a
                       scripted agent; the actions it issued are recorded so
                       the device evaluator can replay them open loop.
+  reference_line_counts.json (set ``line_counts``) lines per .py file of the
+                      reference, for tests/test_citations_cpu.py.
 
 Metadata (numpy/scipy/torch versions, libm behaviour notes, CPU model) is stored
 in every file under ``meta_*`` keys.
@@ -817,9 +819,37 @@ def gen_eval_metrics(track, racing_env):
     _save("eval_metrics.npz", **res)
 
 
+def gen_line_counts():
+    """reference_line_counts.json: the number of lines of every .py file of the
+    reference, by path relative to its root (tests/test_citations_cpu.py checks the
+    documents' `file.py:line` citations against it)."""
+    import json
+    if not os.path.isdir(REF):
+        raise SystemExit(f"reference not found at {REF}")
+    out = {}
+    for d, _, fs in os.walk(REF):
+        if "/." in d:
+            continue
+        for f in fs:
+            if f.endswith(".py"):
+                p = os.path.join(d, f)
+                with open(p, errors="replace") as fh:
+                    out[os.path.relpath(p, REF)] = sum(1 for _ in fh)
+    path = os.path.join(HERE, "reference_line_counts.json")
+    with open(path, "w") as fh:
+        json.dump(dict(sorted(out.items())), fh, indent=1)
+        fh.write("\n")
+    print(f"wrote {path} ({len(out)} files)")
+
+
 def main(argv):
     want = set(argv[1:]) or {"geometry", "raycast", "step_single", "traj_single", "step_multi", "gae", "agent",
-                             "ppo_update", "ppo_update_mb32k", "schedules", "eval_metrics"}
+                             "ppo_update", "ppo_update_mb32k", "schedules", "eval_metrics", "line_counts"}
+    if "line_counts" in want:
+        gen_line_counts()
+        want.discard("line_counts")
+        if not want:
+            return
     if want <= {"ppo_update", "ppo_update_mb32k", "schedules"}:
         sys.path.insert(0, os.path.join(HERE, "_gym_stub"))
         if "ppo_update" in want:

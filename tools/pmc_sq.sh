@@ -1,11 +1,11 @@
 #!/bin/bash
 # SQ counters (issue/wait breakdown) for chosen kernels; counters only, one pass per counter set.
-#   CMD="python bench.py --steps 10 --warmup 20 --no-cpu-baseline" KERNELS="k_rays k_dyn1" bash tools/pmc_sq.sh
+#   CMD="python bench.py --full --steps 10 --warmup 20 --no-cpu-baseline" KERNELS="k_rays k_dyn1" bash tools/pmc_sq.sh
 set -u
 OUT=${GRAFT_REPO_ROOT:-$(pwd)}/gpurun_out/${PMC_NAME:-pmc_sq}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD=${CMD:-python bench.py --steps 10 --warmup 20 --no-cpu-baseline}
+CMD=${CMD:-python bench.py --full --steps 10 --warmup 20 --no-cpu-baseline}
 KERNELS=${KERNELS:-k_rays k_dyn1}
 SETS=${SETS:-"SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM"}
 i=0

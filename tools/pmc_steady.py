@@ -100,7 +100,7 @@ def main():
     ap.add_argument("--timeout", type=int, default=240)
     ap.add_argument("--cmd", default=None, help="profile this command instead of bench.py (e.g. tools/bench_ppo.py ...)")
     ap.add_argument("--passes", default=None, help="counter passes 'C1,C2;C3,...' instead of the default four")
-    ap.add_argument("--bench-args", default="--steps 24 --burn-in 100 --warmup 0 --profile-steps 128 "
+    ap.add_argument("--bench-args", default="--full --steps 24 --burn-in 100 --warmup 0 --profile-steps 128 "
                                             "--no-cpu-baseline --async-probe-groups 0 --ppo-updates 0 "
                                             "--no-time-to-90 --selfplay-updates 0 --counter-steps 0 --stress off "
                                             "--rccl-world1 off")
