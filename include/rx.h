@@ -39,7 +39,7 @@ extern "C" {
 #define RX_ENOMEM (-3)   /* device allocation failed */
 #define RX_ESTATE (-4)   /* call order: tracks/assignment/state not set */
 
-#define RX_ABI_VERSION 23
+#define RX_ABI_VERSION 24
 #define RX_EP_SHARDS 64  /* episode-statistics accumulator rows (rx_io.ep_stats) */
 
 /* state flag bits (rx_state.flags, per agent) */
@@ -350,6 +350,54 @@ int rx_gae(int32_t T, int32_t N, const float* rewards, const float* values, cons
 int rx_gae_scan(int32_t T, int32_t N, const float* rewards, const float* values, const float* dones,
                 const float* next_value, const float* next_done, double gamma, double gae_lambda, float* advantages,
                 float* returns, void* stream);
+
+/* Track table builders (ABI v24), handle-free like rx_gae.  They replace the
+ * per-track Track.__init__ geometry (environment/track.py:61-148: two scipy
+ * CubicSpline solves and a chain of numpy calls per track) with one call for
+ * n_tracks tracks and write the rx_upload_tracks layout above.
+ *   inputs : factor (waypoints per control point; the reference uses 30);
+ *            cp_off HOST int32 [n+1], cp_off[0] = 0: track k owns control points
+ *            cp[cp_off[k] .. cp_off[k+1]) -- P_k of them, 3 <= P_k <= 64;
+ *            cp f64 [cp_off[n]][2]; width f64 [n].
+ *   outputs: wp_off HOST int32 [n+1] (filled by the call: wp_off[k] =
+ *            cp_off[k] * factor, W_k = P_k * factor); wp, nrm f64 [Wtot][2];
+ *            seg f64 [2*Wtot][4]; meta f64 [n][8].
+ * Geometry (csrc/rx_spline.h): the chord-length periodic cubic spline of
+ * track.py:100-115 -- the knot derivatives from the cyclic tridiagonal system
+ * by Sherman-Morrison over two Thomas sweeps, scipy's power-basis coefficients
+ * and evaluation order -- sampled at np.linspace(0, t[-1], W, endpoint=False),
+ * then track.py:82-96,117-148 operation for operation.  scipy solves the system
+ * through LAPACK, so the waypoints agree with the reference's to rounding
+ * (a few ulp of the coordinates), not bit for bit; nrm, seg and
+ * meta are exact functions of the waypoints.  Two columns of meta differ from
+ * the reference's numpy expressions in the last bit at most: meta[2] uses the
+ * platform's atan2 (ocml on the device, libm on the host), and meta[4] squares
+ * with x * x where numpy's scalar ** 2 calls pow.  rx.track overwrites both
+ * with the numpy expressions.
+ *
+ * rx_build_tracks: cp, width and the four outputs are DEVICE pointers.  Checks
+ * everything the host can see before any launch (RX_EINVAL, the message names
+ * the track and the field): P < 3 or P > 64, factor < 1, W above the limit of
+ * rx_upload_tracks, a table above int32 rows.  The launch is enqueued on
+ * `stream` and the call does not wait for it; the (n+1) offsets travel through
+ * a stream-ordered allocation (hipMallocAsync / hipMemcpyAsync from the
+ * caller's pageable array / hipFreeAsync), so the call is not capturable into
+ * a hipGraph.  What lives in device memory cannot be checked without a wait: a
+ * track with a non-finite coordinate, a zero-length chord or a negative width
+ * gets meta[k][4] = NaN, which rx_upload_tracks refuses.
+ *
+ * rx_build_tracks_host: the same arguments with HOST pointers (`stream` is
+ * ignored), the same rx_spline.h code in a plain loop.  It makes no HIP call,
+ * so it works on a machine with no GPU, and it checks the data too: RX_EINVAL
+ * for a non-finite coordinate, a zero-length chord (two consecutive control
+ * points coincide; scipy raises there too) and a negative width, before
+ * anything is written.  Its output equals the device's bit for bit except
+ * meta[2] (atan2 above). */
+int rx_build_tracks(int32_t n_tracks, int32_t factor, const int32_t* cp_off, const double* cp, const double* width,
+                    int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta, void* stream);
+int rx_build_tracks_host(int32_t n_tracks, int32_t factor, const int32_t* cp_off, const double* cp,
+                         const double* width, int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta,
+                         void* stream);
 
 /* Fused optimizer step of PPO.ppo_update (agent/ppo.py:204-207):
  * nn.utils.clip_grad_norm_(params, max_grad_norm) then torch.optim.Adam.step()

@@ -19,6 +19,7 @@
 
 #include "rx.h"
 #include "rx_internal.h"
+#include "rx_spline.h"
 
 namespace {
 
@@ -1318,6 +1319,92 @@ int rx_gae(int32_t T, int32_t N, const float* r, const float* v, const float* d,
 int rx_gae_scan(int32_t T, int32_t N, const float* r, const float* v, const float* d, const float* nv,
                 const float* nd, double gamma, double lam, float* adv, float* ret, void* stream) {
   return gae(T, N, r, v, d, nv, nd, gamma, lam, adv, ret, 1, stream);
+}
+
+// ---- track table builders (ABI v24) ------------------------------------------
+// What the host can check from the offsets alone; fills wp_off.
+static int tracks_shape(const char* fn, int32_t n, int32_t factor, const int32_t* cp_off, const void* cp,
+                        const void* width, int32_t* wp_off, const void* wp, const void* nrm, const void* seg,
+                        const void* meta) {
+  if (n <= 0) return fail(RX_EINVAL, "%s: n_tracks must be > 0 (got %d)", fn, n);
+  if (!cp_off || !cp || !width || !wp_off || !wp || !nrm || !seg || !meta) return fail(RX_EINVAL, "%s: null buffer", fn);
+  if (factor < 1) return fail(RX_EINVAL, "%s: factor must be >= 1 (got %d)", fn, factor);
+  if (cp_off[0] != 0) return fail(RX_EINVAL, "%s: cp_off[0] must be 0", fn);
+  const int max_w = 64 * RX_WP_CHUNK * RX_WP_SUPER;  // rx_upload_tracks' limit
+  for (int32_t k = 0; k < n; ++k) {
+    const int64_t P = (int64_t)cp_off[k + 1] - cp_off[k];
+    if (P < 3 || P > RX_TRACK_MAX_P)
+      return fail(RX_EINVAL, "%s: track %d has P = %lld control points (3 .. %d)", fn, k, (long long)P, RX_TRACK_MAX_P);
+    if (P * factor > max_w)
+      return fail(RX_EINVAL, "%s: track %d has W = P * factor = %lld waypoints (at most %d)", fn, k,
+                  (long long)(P * factor), max_w);
+  }
+  if ((int64_t)cp_off[n] * factor > INT32_MAX)
+    return fail(RX_EINVAL, "%s: W summed over the tracks = %lld overflows wp_off (int32)", fn,
+                (long long)cp_off[n] * factor);
+  for (int32_t k = 0; k <= n; ++k) wp_off[k] = cp_off[k] * factor;
+  return RX_OK;
+}
+
+int rx_build_tracks(int32_t n, int32_t factor, const int32_t* cp_off, const double* cp, const double* width,
+                    int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta, void* stream) {
+  const int rc = tracks_shape("rx_build_tracks", n, factor, cp_off, cp, width, wp_off, wp, nrm, seg, meta);
+  if (rc != RX_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* off_dev = nullptr;
+  const size_t bytes = ((size_t)n + 1) * sizeof(int32_t);
+  if (hipMallocAsync((void**)&off_dev, bytes, s) != hipSuccess || !off_dev)
+    return fail(RX_ENOMEM, "rx_build_tracks: hipMallocAsync(%zu bytes) failed", bytes);
+  hipError_t e = hipMemcpyAsync(off_dev, cp_off, bytes, hipMemcpyHostToDevice, s);
+  int lrc = 0;
+  if (e == hipSuccess) lrc = rx_launch_build_tracks(n, factor, off_dev, cp, width, wp, nrm, seg, meta, s);
+  const hipError_t ef = hipFreeAsync(off_dev, s);
+  if (e != hipSuccess) return fail(RX_EHIP, "rx_build_tracks: offset copy failed: %s", hipGetErrorString(e));
+  if (lrc != 0) return fail(RX_EHIP, "rx_build_tracks: launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  if (ef != hipSuccess) return fail(RX_EHIP, "rx_build_tracks: hipFreeAsync failed: %s", hipGetErrorString(ef));
+  return RX_OK;
+}
+
+int rx_build_tracks_host(int32_t n, int32_t factor, const int32_t* cp_off, const double* cp, const double* width,
+                         int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta, void* /*stream*/) {
+  const int rc = tracks_shape("rx_build_tracks_host", n, factor, cp_off, cp, width, wp_off, wp, nrm, seg, meta);
+  if (rc != RX_OK) return rc;
+  for (int32_t k = 0; k < n; ++k) {  // the data, before anything is written
+    const int P = cp_off[k + 1] - cp_off[k];
+    int at = 0;
+    switch (rx_track_check(P, cp + 2 * (size_t)cp_off[k], width[k], &at)) {
+      case RX_TRACK_BAD_COORD:
+        return fail(RX_EINVAL, "rx_build_tracks_host: track %d: cp[%d] has a non-finite coordinate", k, at);
+      case RX_TRACK_BAD_CHORD:
+        return fail(RX_EINVAL, "rx_build_tracks_host: track %d: chord %d (cp[%d] to cp[%d]) has zero or non-finite "
+                               "length", k, at, at, (at + 1) % P);
+      case RX_TRACK_BAD_WIDTH:
+        return fail(RX_EINVAL, "rx_build_tracks_host: track %d: width %g is negative or NaN", k, width[k]);
+      default:
+        break;
+    }
+  }
+  rx_spline_ws ws;
+  for (int32_t k = 0; k < n; ++k) {  // the kernel's steps (rx_track.hip), one lane at a time
+    const int P = cp_off[k + 1] - cp_off[k], W = P * factor;
+    const double* c = cp + 2 * (size_t)cp_off[k];
+    const size_t base = (size_t)wp_off[k];
+    for (int i = 0; i < P; ++i) rx_spline_load(i, c, &ws);
+    rx_spline_knots(P, W, &ws);
+    rx_spline_solve(P, 0, &ws);
+    rx_spline_solve(P, 1, &ws);
+    for (int i = 0; i < P; ++i) rx_spline_coef(P, i, &ws);
+    double b[4] = {HUGE_VAL, -HUGE_VAL, HUGE_VAL, -HUGE_VAL};
+    for (int j = 0; j < W; ++j) {
+      double x, y;
+      rx_track_point(P, W, &ws, width[k], j, wp + 2 * base, nrm + 2 * base, seg + 8 * base, &x, &y);
+      rx_track_bounds(x, y, b);
+    }
+    double dy, dx;
+    rx_track_meta(P, W, &ws, width[k], b, meta + 8 * (size_t)k, &dy, &dx);
+    meta[8 * (size_t)k + 2] = atan2(dy, dx);
+  }
+  return RX_OK;
 }
 
 static int adam_cfg_error(const rx_adam_config* cfg) {

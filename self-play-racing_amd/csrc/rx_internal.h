@@ -213,6 +213,10 @@ extern "C" int rx_launch_agent_rows(int N, int D, int q, const float* obs, const
                                     float* rew_out, hipStream_t s);
 extern "C" int rx_launch_gae(int T, int N, const float* r, const float* v, const float* d, const float* nv,
                              const float* nd, float g, float gl, float* adv, float* ret, int scan, hipStream_t s);
+// rx_track.hip: the track table of n_tracks tracks, a wavefront per track (cp_off on the device)
+extern "C" int rx_launch_build_tracks(int n_tracks, int factor, const int32_t* cp_off, const double* cp,
+                                      const double* width, double* wp, double* nrm, double* seg, double* meta,
+                                      hipStream_t s);
 // Adam's per-step scalars for step count s (torch.optim.Adam, non-capturable):
 // out[0] = step_size = -lr / (1 - beta1^s), out[1] = sqrt(1 - beta2^s).  Written
 // once per optimizer step next to the clip-norm partials (rx_adam_workspace_floats

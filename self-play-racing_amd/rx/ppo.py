@@ -116,7 +116,8 @@ class PPO:
         c = self.config
         lo, n = rdist.shard(c["num_envs"])
         fn = env_fn if lo == 0 else (lambda i: env_fn(lo + i))
-        return build_vector_env(fn, n, c["seed"] + rdist.rank(), self.device)
+        return build_vector_env(fn, n, c["seed"] + rdist.rank(), self.device,
+                                track_backend=c.get("track_backend", "scipy"))
 
     @property
     def num_local_envs(self):

@@ -114,7 +114,8 @@ class SelfPlayPPO(PPO):
         c = self.config
         lo, n = rdist.shard(c["num_envs"])
         fn = env_fn if lo == 0 else (lambda i: env_fn(lo + i))
-        venv = build_vector_env(fn, n, c["seed"] + rdist.rank(), self.device)
+        venv = build_vector_env(fn, n, c["seed"] + rdist.rank(), self.device,
+                                track_backend=c.get("track_backend", "scipy"))
         if c.get("start_draws", "hash") == "numpy":  # the reference's np.random start-slot stream
             if rdist.world() > 1:
                 # every rank would replay the SAME np.random stream for its own env shard, not

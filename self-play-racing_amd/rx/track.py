@@ -17,6 +17,11 @@ new is what happens around them:
   points and, optionally, the env -> slot assignment) in one ``.npz`` file, so
   a 65,536-env pool is rebuilt without regenerating or re-splining anything
   (format in DESIGN.md).
+* ``backend="native"`` / ``"device"`` (``TrackSet``, ``TrackSet.build``) hand
+  the geometry of all distinct slots to librx in one call (``build_table``:
+  csrc/rx_spline.h on the host or as a gfx950 kernel) instead of one scipy
+  spline pair per slot; waypoints then agree with scipy's to rounding, the
+  rest is an exact function of them.  "scipy" is the default.
 """
 import numpy as np
 from scipy.interpolate import CubicSpline
@@ -120,7 +125,21 @@ class TrackGeometry:
         sx = CubicSpline(t, closed[:, 0], bc_type="periodic")
         sy = CubicSpline(t, closed[:, 1], bc_type="periodic")
         tw = np.linspace(0, t[-1], len(cp) * factor, endpoint=False)
-        self.waypoints = np.column_stack((sx(tw), sy(tw)))
+        self._derive(np.column_stack((sx(tw), sy(tw))))
+
+    @classmethod
+    def from_waypoints(cls, control_points, track_width, waypoints):
+        """Everything Track.__init__ derives from the waypoints (track.py:82-96,
+        117-148), for waypoints produced elsewhere (rx_build_tracks): what
+        ``__init__`` itself runs after its spline."""
+        self = cls.__new__(cls)
+        self.control_points = control_points
+        self.track_width = track_width
+        self._derive(waypoints)
+        return self
+
+    def _derive(self, waypoints):
+        self.waypoints = waypoints
         wp = self.waypoints
         # track_bounds / max_track_distance, track.py:82-91 (np.float64 ** 2 is pow())
         lo_x, hi_x = wp[:, 0].min(), wp[:, 0].max()
@@ -165,6 +184,62 @@ class TrackGeometry:
         return (wp[0, 0], wp[0, 1], np.arctan2(wp[1, 1] - wp[0, 1], wp[1, 0] - wp[0, 0]))
 
 
+BACKENDS = ("scipy", "native", "device")
+
+
+def build_table(control_points, widths, factor=30, backend="native", device=None):
+    """The packed table (``TrackSet.arrays`` layout) of the given tracks from
+    librx's builders (include/rx.h, ABI v24), as the C level leaves it:
+
+    * ``"native"``: rx_build_tracks_host -- a serial in-process loop over
+      csrc/rx_spline.h, no HIP call, no torch call, no worker pool;
+    * ``"device"``: rx_build_tracks -- the same code as a gfx950 kernel, a
+      wavefront per track, enqueued on torch's current stream of ``device``;
+      control points and widths go up as two tensors and the table comes back
+      in one download.
+
+    Both give the same bytes except meta[:, 2] (atan2: libm / ocml);
+    ``TrackSet`` replaces that column and meta[:, 4] with the reference's numpy
+    expressions.  Invalid input raises ``RxError`` naming the track and field."""
+    from . import _lib
+    L = _lib.load()
+    n = len(control_points)
+    cps = [np.asarray(c, dtype=np.float64) for c in control_points]
+    for k, c in enumerate(cps):
+        if c.ndim != 2 or c.shape[1] != 2:
+            raise ValueError(f"track {k}: control points must be [P, 2], got {c.shape}")
+    cp_off = np.concatenate([[0], np.cumsum([len(c) for c in cps])]).astype(np.int32)
+    cp = np.ascontiguousarray(np.concatenate(cps)) if n else np.zeros((0, 2))
+    w = np.ascontiguousarray(widths, dtype=np.float64)
+    wt = max(int(cp_off[-1]) * max(int(factor), 0), 0)
+    sizes = (2 * wt, 2 * wt, 8 * wt, 8 * n)  # wp, nrm, seg, meta in doubles
+    cuts = np.concatenate([[0], np.cumsum(sizes)])
+    wp_off = np.zeros(n + 1, dtype=np.int32)
+    if backend == "native":
+        flat = np.empty(cuts[-1], dtype=np.float64)
+        parts = [flat[cuts[i]:cuts[i + 1]] for i in range(4)]
+        _lib.check(L.rx_build_tracks_host(n, factor, _lib.ptr(cp_off), _lib.ptr(cp), _lib.ptr(w), _lib.ptr(wp_off),
+                                          *[_lib.ptr(x) for x in parts], None), "rx_build_tracks_host")
+    elif backend == "device":
+        import torch
+        dev = torch.device("cuda" if device is None else device)
+        with torch.cuda.device(dev):
+            cp_d, w_d = torch.from_numpy(cp).to(dev), torch.from_numpy(w).to(dev)
+            flat_d = torch.empty(int(cuts[-1]), dtype=torch.float64, device=dev)
+            parts = [flat_d[cuts[i]:cuts[i + 1]] for i in range(4)]
+            _lib.check(L.rx_build_tracks(n, factor, _lib.ptr(cp_off), _lib.ptr(cp_d), _lib.ptr(w_d), _lib.ptr(wp_off),
+                                         *[_lib.ptr(x) for x in parts], _lib.stream_ptr()), "rx_build_tracks")
+            flat = flat_d.cpu().numpy()
+        bad = np.flatnonzero(~np.isfinite(flat[cuts[3]:].reshape(n, 8)[:, 4]))
+        if len(bad):  # the kernel marks what only device memory shows; the host twin's checks word the error
+            build_table(control_points, w, factor, "native")
+            raise _lib.RxError(f"rx_build_tracks: track {int(bad[0])} has a non-finite max_track_distance")
+    else:
+        raise ValueError(f"backend must be 'native' or 'device' here, got {backend!r}")
+    return dict(wp_off=wp_off, wp=flat[cuts[0]:cuts[1]].reshape(wt, 2), nrm=flat[cuts[1]:cuts[2]].reshape(wt, 2),
+                seg=flat[cuts[2]:cuts[3]].reshape(2 * wt, 4), meta=flat[cuts[3]:cuts[4]].reshape(n, 8))
+
+
 def _geoms_worker(args):
     """Worker of TrackSet.build (a spawned process: numpy / scipy only): the
     packed table rows of its tracks (TrackSet.arrays layout), not the objects --
@@ -180,21 +255,32 @@ class TrackSet:
     ``slot(cp, width)`` returns the slot index of a pair, adding it on first
     sight; ``arrays()`` gives the rx_upload_tracks layout (include/rx.h)."""
 
-    def __init__(self, factor=30):
+    def __init__(self, factor=30, backend="scipy"):
+        if backend not in BACKENDS:
+            raise ValueError(f"backend must be one of {BACKENDS}, got {backend!r}")
         self.factor = factor
+        self.backend = backend
+        self.device = None  # backend "device": the torch device that builds (None = the current one)
         self.geoms = []
         self._index = {}
         self._packed = None
 
     @classmethod
-    def build(cls, control_points, widths, workers=None, factor=30):
+    def build(cls, control_points, widths, workers=None, factor=30, backend="scipy", device=None):
         """The slots of (control_points[i], widths[i]) for every i, in first-sight
         order (as ``slot`` adds them), with the splines of many distinct slots
         computed in ``workers`` spawned processes (each runs TrackGeometry, so the
         geometry is bit-identical to the serial build).  For pools of thousands of
         distinct tracks -- ``gen_tracks(n, seed=None)``, SURVEY.md §8(d)'s stress
-        variant -- where the serial spline (~1 ms per track) dominates."""
-        ts = cls(factor)
+        variant -- where the serial spline (~1 ms per track) dominates.
+
+        ``backend="native"`` / ``"device"`` build all distinct slots in one
+        librx call instead (``build_table``; ``workers`` is unused, ``device``
+        picks the GPU): same slot order and dedup, waypoints equal to the scipy
+        ones to rounding, everything else an exact function of
+        them; the two give byte-identical tables."""
+        ts = cls(factor, backend)
+        ts.device = device
         todo = []
         for cp, w in zip(control_points, widths):
             cp = DEFAULT_CONTROL_POINTS if cp is None else cp
@@ -203,6 +289,9 @@ class TrackSet:
             if key not in ts._index:
                 ts._index[key] = len(todo)
                 todo.append((cp, w))
+        if backend != "scipy":
+            ts._adopt(todo, build_table([cp for cp, _ in todo], [w for _, w in todo], factor, backend, device))
+            return ts
         if workers is None:
             import os
             workers = min(16, len(os.sched_getaffinity(0)))
@@ -226,6 +315,22 @@ class TrackSet:
         ts._packed = a
         return ts
 
+    def _adopt(self, todo, a):
+        """Append the slots of a librx-built table (``build_table``): views into
+        it (TrackGeometry.from_arrays), with the start angle and
+        max_track_distance -- meta[:, 2] and meta[:, 4] -- recomputed by the
+        reference's own numpy expressions (libm / ocml atan2, pow against x * x:
+        include/rx.h), so the slot equals ``from_waypoints`` of its waypoints."""
+        off, meta = a["wp_off"], a["meta"]
+        for k, (cp, w) in enumerate(todo):
+            s, e = off[k], off[k + 1]
+            g = TrackGeometry.from_arrays(cp, w, a["wp"][s:e], a["nrm"][s:e], a["seg"][2 * s:2 * e], meta[k, 4])
+            b = g.track_bounds
+            g.max_track_distance = np.sqrt((b["max_x"] - b["min_x"]) ** 2 + (b["max_y"] - b["min_y"]) ** 2)
+            meta[k, 2], meta[k, 4] = g.get_start_pos()[2], g.max_track_distance
+            self.geoms.append(g)
+        self._packed = a if len(self.geoms) == len(todo) else None
+
     @staticmethod
     def _key(cp, width):
         a = np.asarray(cp)
@@ -238,7 +343,10 @@ class TrackSet:
         k = self._index.get(key)
         if k is None:
             k = len(self.geoms)
-            self.geoms.append(TrackGeometry(cp, w, self.factor))
+            if self.backend == "scipy":
+                self.geoms.append(TrackGeometry(cp, w, self.factor))
+            else:  # one new track: the host twin (byte-identical to the device's)
+                self._adopt([(cp, w)], build_table([cp], [w], self.factor, "native"))
             self._index[key] = k
             self._packed = None
         return k
@@ -276,7 +384,8 @@ class TrackSet:
         Keys: version, factor, n_slots; per slot: widths [n], cp_off [n+1] int64,
         cp_is_int [n] bool, control_points [sum P, 2] f64; the device table
         wp_off / wp / nrm / seg / meta exactly as rx_upload_tracks takes it;
-        optional track_of_env [N] int32 (the env -> slot assignment)."""
+        optional track_of_env [N] int32 (the env -> slot assignment); backend
+        (the builder of the geometry; files without it are "scipy")."""
         a = self.arrays()
         cps = [np.asarray(g.control_points) for g in self.geoms]
         cp_off = np.concatenate([[0], np.cumsum([len(c) for c in cps])]).astype(np.int64)
@@ -290,21 +399,29 @@ class TrackSet:
                  n_slots=np.int64(len(self)), widths=np.array([float(g.track_width) for g in self.geoms]),
                  cp_off=cp_off, cp_is_int=np.array([np.issubdtype(c.dtype, np.integer) for c in cps]),
                  control_points=np.concatenate(cps).astype(np.float64) if cps else np.zeros((0, 2)),
-                 **a, **extra)
+                 backend=np.array(self.backend), **a, **extra)
 
     @classmethod
     def load(cls, path, verify=False):
         """-> (TrackSet, track_of_env or None).  ``verify`` re-splines every slot
-        from its control points and requires the stored geometry bit for bit."""
+        from its control points with the stored backend ("device" through its
+        byte-identical host twin, so no GPU is needed) and requires the stored
+        geometry bit for bit."""
         with np.load(path, allow_pickle=False) as z:
             if int(z["version"]) != cls.TABLE_VERSION:
                 raise ValueError(f"track table version {int(z['version'])} != {cls.TABLE_VERSION}")
             d = {k: z[k] for k in z.files}
-        ts = cls(factor=int(d["factor"]))
+        ts = cls(factor=int(d["factor"]), backend=str(d["backend"]) if "backend" in d else "scipy")
         n = int(d["n_slots"])
         wp_off, cp_off = d["wp_off"], d["cp_off"]
         if wp_off.shape != (n + 1,) or cp_off.shape != (n + 1,) or d["meta"].shape != (n, 8):
             raise ValueError("inconsistent track table")
+        twin = None
+        if verify and ts.backend != "scipy" and n:
+            twin = build_table([d["control_points"][cp_off[k]:cp_off[k + 1]] for k in range(n)], d["widths"],
+                               ts.factor, "native")
+            if not np.array_equal(twin["wp_off"], wp_off):
+                raise ValueError("track table offsets do not match its control points")
         for k in range(n):
             cp = d["control_points"][cp_off[k]:cp_off[k + 1]]
             if d["cp_is_int"][k]:
@@ -313,7 +430,11 @@ class TrackSet:
             a, b = wp_off[k], wp_off[k + 1]
             g = TrackGeometry.from_arrays(cp, w, d["wp"][a:b], d["nrm"][a:b], d["seg"][2 * a:2 * b],
                                           d["meta"][k, 4])
-            if verify:
+            if twin is not None:
+                for key, lo, hi in (("wp", a, b), ("nrm", a, b), ("seg", 2 * a, 2 * b)):
+                    if d[key].shape != twin[key].shape or d[key][lo:hi].tobytes() != twin[key][lo:hi].tobytes():
+                        raise ValueError(f"track table slot {k} does not match its control points")
+            elif verify:
                 ref = TrackGeometry(cp, w, ts.factor)
                 for x, y in ((ref.waypoints, g.waypoints), (ref.normals, g.normals),
                              (ref.segment_cache["starts"], g.segment_cache["starts"]),

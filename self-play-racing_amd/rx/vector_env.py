@@ -120,11 +120,15 @@ class RacingVectorEnv:
     train.py); sensor cone pi/3 for A=1 (racing_env.py:45) and pi/2 for A=2
     (multi_racing_env.py:50).  ``sched``: launch-schedule overrides, a dict
     over ``_lib.SCHED_FIELDS`` (rx_config ABI v17: 0 = auto, -1 = off;
-    scheduling only, results are identical -- the tests force each path)."""
+    scheduling only, results are identical -- the tests force each path).
+    ``track_backend``: who builds the track table when no ``track_set`` is
+    passed -- "scipy" (the reference's splines, one slot at a time), "native"
+    or "device" (rx.track.TrackSet.build: every distinct slot in one librx call,
+    on the host or on this env's device)."""
 
     def __init__(self, control_points, widths, n_agents=1, n_sensors=11, device=None, autoreset="next_step",
                  seed=0, speed_weight=8.0, max_steps=3000, half_cone=None, track_set=None, cull_chunk=8,
-                 sort_interval=None, ray_order=None, cull_super=8, sched=None):
+                 sort_interval=None, ray_order=None, cull_super=8, sched=None, track_backend="scipy"):
         self.L = _lib.load()
         self.device = torch.device(device) if device is not None else _default_device()
         if self.device.type != "cuda":
@@ -145,7 +149,12 @@ class RacingVectorEnv:
         self.speed_weight = float(speed_weight)
         if half_cone is None:
             half_cone = np.pi / 3 if A == 1 else np.pi / 2
-        self.tracks = track_set if track_set is not None else TrackSet()
+        if track_set is not None:
+            self.tracks = track_set
+        elif track_backend == "scipy":
+            self.tracks = TrackSet()
+        else:  # all distinct slots at once; the loop below then only looks them up
+            self.tracks = TrackSet.build(control_points, widths, backend=track_backend, device=self.device)
         slots = np.empty(N, dtype=np.int32)
         cache = {}
         for i, (cp, w) in enumerate(zip(control_points, widths)):
@@ -616,10 +625,15 @@ class RacingVectorEnv:
 
     # ------------------------------------------------------------ construction helpers
     @classmethod
-    def from_table(cls, path, track_of_env=None, **kw):
+    def from_table(cls, path, track_of_env=None, track_backend=None, **kw):
         """Build from an on-disk track table (rx.track.TrackSet.save): env i
-        runs slot track_of_env[i] (default: the assignment stored in the file)."""
+        runs slot track_of_env[i] (default: the assignment stored in the file).
+        ``track_backend``: the builder the table must come from ("native" and
+        "device" tables are the same bytes and count as one); None takes the
+        file's."""
         ts, stored = TrackSet.load(path)
+        if track_backend is not None and (track_backend == "scipy") != (ts.backend == "scipy"):
+            raise ValueError(f"{path} was built by backend {ts.backend!r}, not {track_backend!r}")
         toe = stored if track_of_env is None else np.asarray(track_of_env, dtype=np.int32)
         if toe is None:
             raise ValueError(f"{path} holds no env assignment: pass track_of_env")
