@@ -39,7 +39,7 @@ extern "C" {
 #define RX_ENOMEM (-3)   /* device allocation failed */
 #define RX_ESTATE (-4)   /* call order: tracks/assignment/state not set */
 
-#define RX_ABI_VERSION 24
+#define RX_ABI_VERSION 25
 #define RX_EP_SHARDS 64  /* episode-statistics accumulator rows (rx_io.ep_stats) */
 
 /* state flag bits (rx_state.flags, per agent) */
@@ -626,6 +626,57 @@ typedef struct rx_selfplay_io {
 } rx_selfplay_io;
 int rx_selfplay_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
                               int32_t precision, void* stream);
+
+/* ABI v25: an evaluation's step loop from one call.  Replaces the per-episode
+ * loops of utils/metrics.py:39-78 (eval_single_agent) and utils/metrics.py:80-150
+ * (eval_multi_agent) that evaluate.py:12-122 runs once per (track, run), for every
+ * episode of the protocol at once: per step t, with no host wait in between,
+ *   policy mode (params != NULL): one rx_policy_act over the N*A rows of io->obs
+ *     (contiguous [N][A][D]; two cars: both driven by the same policy, as
+ *     utils/metrics.py:94-101 does) with eps[t], actions into actions[t] (bf16: the
+ *     operand fragments are built once per call, as rx_rollout_steps does);
+ *   open loop (params == NULL): actions[t] are the caller's;
+ *   rx_step of actions[t], writing io->obs in place;
+ *   k_eval_acc (csrc/rx_eval.hip): for every env e with active[e], per car q,
+ *     acc[e][q]: total_reward += reward64; total_distance += sqrt(dx*dx + dy*dy)
+ *     against the stored previous post-step position (not on the episode's first
+ *     step, utils/metrics.py:59-64); prev_x, prev_y = the position; steps += 1;
+ *     progress, speed, placement = this step's info columns; flags = the car's
+ *     RX_F_* byte; then active[e] = 0 if done_f32[e] != 0, and *n_active -= the
+ *     envs that ended.  An env whose episode has ended is never touched again (its
+ *     record keeps the terminal step's values); with *n_active == 0 the kernel
+ *     returns at once.
+ * The kernel reads the post-step positions and flags from the engine's working
+ * state, so no rx_state_export is needed.  The record is bit-equal to the one
+ * rx.evaluate's eager loop accumulates with torch from the same actions (the same
+ * float64 operations in the same order: separate multiply and add, IEEE sqrt);
+ * policy-mode actions are rx_policy_act's, equal to the torch forward within
+ * float rounding.
+ *   acc      f64 [N][A][RX_EVAL_W], env order: 0 total_reward, 1 total_distance,
+ *            2 steps (per env, written to every car's record), 3 progress, 4 speed,
+ *            5 placement, 6 flags, 7 prev_x, 8 prev_y, 9 zero; integers as exact
+ *            doubles, so a result is one device-to-host copy;
+ *   active   uint8 [N];  n_active  int32 [1].
+ * Before the first call of an evaluation the caller resets the envs (rx_reset
+ * into io->obs) and sets acc = 0, active = 1, *n_active = N; later calls continue
+ * the same episodes.  io supplies obs, reward64, info and done_f32 (all required;
+ * its actions pointer is ignored).  Any autoreset mode is accepted; an evaluation
+ * uses RX_AUTORESET_DISABLED.  Same stream semantics as rx_step. */
+#define RX_EVAL_W 10
+typedef struct rx_eval_io {
+  int32_t obs_dim;       /* the handle's D */
+  int32_t precision;     /* RX_PREC_*; policy mode only */
+  const float* params;   /* flat policy parameters, or NULL = open loop (actions are inputs) */
+  const float* log_std;  /* [2] (policy mode) */
+  const float* eps;      /* [n_steps][N*A][2] N(0,1) noise (policy mode); all zeros = deterministic mu */
+  float* actions;        /* [n_steps][N][A][2]: read in open-loop mode, WRITTEN in policy mode */
+  float* logp_sink;      /* [N*A] scratch (policy mode) */
+  float* value_sink;     /* [N*A] scratch (policy mode) */
+  double* acc;           /* [N][A][RX_EVAL_W] */
+  uint8_t* active;       /* [N] */
+  int32_t* n_active;     /* [1] */
+} rx_eval_io;
+int rx_eval_steps(rx_env* h, const rx_io* io, const rx_eval_io* ev, int32_t n_steps, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1297,6 +1297,62 @@ int rx_selfplay_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r
   return RX_OK;
 }
 
+// ABI v25: an evaluation's step loop (policy or open-loop actions, rx_step, k_eval_acc
+// per step) enqueued by one call; every argument is checked before the first HIP call.
+int rx_eval_steps(rx_env* h, const rx_io* io, const rx_eval_io* ev, int32_t n_steps, void* stream) {
+  if (!h) return fail(RX_EINVAL, "rx_eval_steps: null handle");
+  if (!io) return fail(RX_EINVAL, "rx_eval_steps: null io");
+  if (!ev) return fail(RX_EINVAL, "rx_eval_steps: null ev");
+  if (n_steps <= 0) return fail(RX_EINVAL, "rx_eval_steps: n_steps=%d must be > 0", n_steps);
+  if (!ev->actions) return fail(RX_EINVAL, "rx_eval_steps: null actions");
+  if (!ev->acc || !ev->active || !ev->n_active)
+    return fail(RX_EINVAL, "rx_eval_steps: null %s", !ev->acc ? "acc" : !ev->active ? "active" : "n_active");
+  if (!io->obs || !io->reward64 || !io->info || !io->done_f32)
+    return fail(RX_EINVAL, "rx_eval_steps: null io->%s",
+                !io->obs ? "obs" : !io->reward64 ? "reward64" : !io->info ? "info" : "done_f32");
+  const bool policy = ev->params != nullptr;
+  if (policy) {
+    if (ev->obs_dim != 15 && ev->obs_dim != 19)
+      return fail(RX_EINVAL, "rx_eval_steps: obs_dim=%d has no policy kernel (15 or 19)", ev->obs_dim);
+    if (ev->precision != RX_PREC_FP32 && ev->precision != RX_PREC_BF16)
+      return fail(RX_EINVAL, "rx_eval_steps: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", ev->precision);
+    if (!ev->log_std || !ev->eps || !ev->logp_sink || !ev->value_sink)
+      return fail(RX_EINVAL, "rx_eval_steps: null %s (policy mode)",
+                  !ev->log_std ? "log_std" : !ev->eps ? "eps" : !ev->logp_sink ? "logp_sink" : "value_sink");
+  }
+  // from here on the handle is read
+  if (ev->obs_dim != h->D) return fail(RX_EINVAL, "rx_eval_steps: obs_dim %d != the handle's %d", ev->obs_dim, h->D);
+  if (h->n_tracks <= 0 || !h->assigned || !h->bound)
+    return fail(RX_ESTATE, "rx_eval_steps: needs an assigned, bound handle");
+  const int64_t N = h->cfg.n_envs, A = h->cfg.n_agents, NA = N * A;
+  hipStream_t hs = (hipStream_t)stream;
+  const void* frag = nullptr;
+  if (policy && ev->precision == RX_PREC_BF16) {  // fixed parameters: bf16 operand fragments once per call
+    if (rx_launch_policy_frag(ev->obs_dim, ev->params, h->policy_frag.p, hs))
+      return fail(RX_EHIP, "rx_eval_steps: fragment launch failed");
+    frag = h->policy_frag.p;
+  }
+  int rc;
+  for (int32_t t = 0; t < n_steps; ++t) {
+    float* act = ev->actions + (int64_t)t * NA * 2;
+    if (policy) {
+      // both cars of a two-car env are rows of the same launch: one policy drives them (utils/metrics.py:94-101)
+      const rx_policy_io pio{ev->obs_dim, NA, io->obs, ev->eps + (int64_t)t * NA * 2, ev->params, ev->log_std, act,
+                             ev->logp_sink, ev->value_sink, 0, 0, ev->precision, nullptr, 0};
+      if ((rc = rx_launch_policy_act(&pio, hs, frag)) != 0)
+        return fail(RX_EHIP, "rx_eval_steps: policy launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    rx_io s = *io;
+    s.actions = act;
+    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
+    // after launch(): its re-sort (if any) has been enqueued, so perm and the working rows agree
+    if ((rc = rx_launch_eval_acc((int)N, (int)A, h->perm[0].p, &h->work, io, ev->acc, ev->active, ev->n_active,
+                                 hs)) != 0)
+      return fail(RX_EHIP, "k_eval_acc launch failed: %s", hipGetErrorString((hipError_t)rc));
+  }
+  return RX_OK;
+}
+
 static int gae(int32_t T, int32_t N, const float* r, const float* v, const float* d, const float* nv, const float* nd,
                double gamma, double lam, float* adv, float* ret, int scan, void* stream) {
   if (T <= 0 || N <= 0) return fail(RX_EINVAL, "rx_gae: T=%d N=%d must be > 0", T, N);

@@ -301,3 +301,7 @@ extern "C" int rx_sort_envs(const uint32_t* keys, uint32_t* off, int n, int A, u
 extern "C" int rx_launch_permutation(int64_t n, uint64_t seed, int64_t* out, hipStream_t s);
 extern "C" int rx_state_sync(const rx_state* work, const rx_state* user, const int32_t* perm, int n, int A,
                              int to_user, hipStream_t s);
+// rx_eval_steps' per-step metric accumulation (rx_eval.hip): one lane per env position,
+// x / y / flags from the working state (position order), the rest in env order
+extern "C" int rx_launch_eval_acc(int n, int A, const int32_t* perm, const rx_state* work, const rx_io* io,
+                                  double* acc, uint8_t* active, int32_t* n_active, hipStream_t s);

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede librx: shared HIP runtime, see above)
 
 from . import _build
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 RX_EP_SHARDS = 64  # rx_io.ep_stats rows (include/rx.h)
 RX_OK, RX_EINVAL, RX_EHIP, RX_ENOMEM, RX_ESTATE = 0, -1, -2, -3, -4
 RX_F_CRASHED, RX_F_FINISHED, RX_F_CP25, RX_F_CP50, RX_F_CP75, RX_F_HAS_CRASHED = 1, 2, 4, 8, 16, 32
@@ -32,7 +32,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_profile", "rx_profile_read", "rx_ppo_update_workspace_floats", "rx_ppo_minibatch_update", "rx_env_order",
            "rx_state_import", "rx_state_export", "rx_schedule",
            "rx_ppo_adv_workspace_doubles", "rx_ppo_adv_stats_ws", "rx_profile_waves", "rx_ray_waves", "rx_ray_tasks", "rx_set_start_draws",
-           "rx_rollout_steps", "rx_selfplay_rollout_steps", "rx_steps", "rx_build_tracks", "rx_build_tracks_host")
+           "rx_rollout_steps", "rx_selfplay_rollout_steps", "rx_steps", "rx_build_tracks", "rx_build_tracks_host",
+           "rx_eval_steps")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -116,6 +117,15 @@ class RxSelfplayIO(ctypes.Structure):
                                   "sink")] + [("agent", ctypes.c_int32), ("opp_precision", ctypes.c_int32)]
 
 
+RX_EVAL_W = 10  # doubles per (env, car) of rx_eval_io.acc (include/rx.h)
+
+
+class RxEvalIO(ctypes.Structure):
+    _fields_ = [("obs_dim", ctypes.c_int32), ("precision", ctypes.c_int32)] + \
+               [(k, _P) for k in ("params", "log_std", "eps", "actions", "logp_sink", "value_sink", "acc", "active",
+                                  "n_active")]
+
+
 class RxError(RuntimeError):
     pass
 
@@ -195,6 +205,7 @@ def load(build_if_missing=True):
     L.rx_set_start_draws.argtypes = [_P, _P, ctypes.c_int64, _P]
     L.rx_build_tracks.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_P] * 9
     L.rx_build_tracks_host.argtypes = L.rx_build_tracks.argtypes
+    L.rx_eval_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxEvalIO), ctypes.c_int32, _P]
     for name in EXPORTS:
         if name not in ("rx_last_error", "rx_abi_version", "rx_ppo_workspace_floats", "rx_ppo_workspace_doubles",
                         "rx_ppo_update_workspace_floats", "rx_adam_workspace_floats",

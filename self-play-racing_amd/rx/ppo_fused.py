@@ -106,7 +106,8 @@ class FusedMinibatchGrad:
             n = self.L.rx_ppo_update_workspace_floats(self.batch.obs_dim, f.cfg)
             if n == 0:
                 raise RuntimeError(self.L.rx_last_error().decode())
-            # zero-filled: its last word is the fused launch's arrival counter (rx.h, ABI v22)
+            # the per-tensor norm partials and Adam's two step scalars (rx.h, ABI v23: no control block);
+            # every word is written before it is read, the zero fill is only a defined start
             ws = self.adam_ws = torch.zeros(n, dtype=torch.float32, device=self.stats.device)
         _lib.check(self.L.rx_ppo_minibatch_update(
             self.batch if batch is None else batch, int(m), f.cfg, _lib.ptr(f.flat_param), _lib.ptr(self.ws_f), _lib.ptr(self.ws_d),

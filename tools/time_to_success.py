@@ -27,9 +27,12 @@ sys.path.insert(0, os.path.join(ROOT, "self-play-racing_amd"))
 
 
 def run(num_envs=16, num_steps=2048, total_timesteps=5_000_000, eval_every=5, target=0.9, max_minutes=15.0, seed=1,
-        device_shuffle=False, quiet=False, policy_dtype="fp32"):
+        device_shuffle=False, quiet=False, policy_dtype="fp32", eval_backend="eager"):
     """Train (train.py train_single through rx) and evaluate every ``eval_every``
-    updates; returns the result dict (value_s = training seconds to target)."""
+    updates; returns the result dict (value_s = training seconds to target).
+    ``eval_backend``: rx.evaluate.Evaluator's backend -- "fused" samples another
+    evaluation noise stream than "eager", so the update at which the target is
+    first seen (and with it value_s) is not comparable sample for sample."""
     from rx.configs import base_config
     from rx.envs import RacingEnv
     from rx.evaluate import Evaluator
@@ -49,7 +52,7 @@ def run(num_envs=16, num_steps=2048, total_timesteps=5_000_000, eval_every=5, ta
 
     t_build = time.perf_counter()
     trainer = PPO(env_fn, config, device="cuda")
-    evaluator = Evaluator(device=trainer.device)
+    evaluator = Evaluator(device=trainer.device, backend=eval_backend)
     build_s = time.perf_counter() - t_build
     train_s = 0.0
     curve = []
@@ -86,7 +89,7 @@ def run(num_envs=16, num_steps=2048, total_timesteps=5_000_000, eval_every=5, ta
             "config": {"num_envs": num_envs, "num_steps": num_steps, "total_timesteps": total_timesteps,
                        "shuffle": config.get("shuffle", "numpy"), "policy_dtype": policy_dtype,
                        "eval": "evaluate.py protocol: 40 tracks (seed 42) x 5 runs, widths by run, max 2000 steps, "
-                               "stochastic policy", "eval_every_updates": eval_every},
+                               "stochastic policy", "eval_every_updates": eval_every, "eval_backend": eval_backend},
             "build_s": round(build_s, 3), "curve": curve}
 
 
@@ -103,9 +106,11 @@ def main():
     ap.add_argument("--device-shuffle", action="store_true", help="config shuffle='device' (rx_random_permutation)")
     ap.add_argument("--policy-dtype", choices=("fp32", "bf16"), default="fp32",
                     help="config policy_dtype: bf16 runs the policy / PPO kernels on bf16 MFMA operands")
+    ap.add_argument("--eval-backend", choices=("eager", "fused"), default="eager",
+                    help="rx.evaluate backend: fused = rx_eval_steps (another evaluation noise stream than eager)")
     args = ap.parse_args()
     out = run(args.num_envs, args.num_steps, args.total_timesteps, args.eval_every, args.target, args.max_minutes,
-              args.seed, args.device_shuffle, policy_dtype=args.policy_dtype)
+              args.seed, args.device_shuffle, policy_dtype=args.policy_dtype, eval_backend=args.eval_backend)
     print(json.dumps(out), flush=True)
     if args.out:
         with open(args.out, "w") as f:
