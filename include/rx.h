@@ -277,7 +277,10 @@ int rx_step(rx_env* h, const rx_io* io, void* stream);
  * rows).  Step s reads actions + s * strides->actions and writes obs + s *
  * strides->obs, reward + s * strides->reward, ... (element strides; a stride of 0
  * writes every step into the same rows, which then hold the last step's outputs;
- * strides = NULL: all 0).  ep_stats and counters accumulate.  The actions of all
+ * strides = NULL: all 0; with stride-0 rows a step's kernels may write next-step
+ * columns while an earlier step's are still being written, so such rows are
+ * defined once the call's work has completed on the stream, not between its
+ * launches).  ep_stats and counters accumulate.  The actions of all
  * n_steps steps must be in device memory when the call is made: open-loop
  * action sequences (the env-throughput benchmark: a bank of random actions) --
  * a policy-in-the-loop rollout is rx_rollout_steps.  Replaces n_steps iterations

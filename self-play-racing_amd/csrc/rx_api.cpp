@@ -134,6 +134,10 @@ struct rx_env {
   // split step (k_kin1 + k_step2): cos / sin of the stepped angles; RX_SPLIT=0 disables
   DevBuf<double> cs_scratch;
   bool split = true;
+  // rx_steps' carried schedule: two snapshots of what the ray waves read -- the stepped
+  // pose ([3][N] x, y, angle) and the sorted task ids -- written by a step's KIN part
+  DevBuf<double> snap_pose[2];
+  DevBuf<int32_t> snap_tasks[2];
   // rx_profile: per recorded launch, [RX_PROF_SLOTS] wave start + [RX_PROF_SLOTS] wave end stamps
   bool prof = false;
   DevBuf<unsigned long long> prof_buf;
@@ -446,6 +450,10 @@ int rx_destroy(rx_env* h) {
                   &h->slot_n, &h->tasks})
     b->release();
   h->cs_scratch.release();
+  for (int b = 0; b < 2; ++b) {
+    h->snap_pose[b].release();
+    h->snap_tasks[b].release();
+  }
   h->policy_frag.release();
   h->pos_slot.release();
   h->prof_buf.release();
@@ -738,6 +746,15 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
     std::vector<double> z(2 * (size_t)N * A, 0.0);
     if ((rc = upload(h->cs_scratch, z.data(), z.size()))) return rc;
   }
+  // the carried schedule's snapshots (single-agent; here, not in rx_steps: it may run under capture)
+  for (int b = 0; b < 2 && RX_STEPS_CARRY && A == 1; ++b) {
+    std::vector<double> z(3 * (size_t)N, 0.0);
+    if ((rc = upload(h->snap_pose[b], z.data(), z.size()))) return rc;
+    if (h->cfg.ray_order == 2) {
+      std::vector<int32_t> t0((size_t)N * R, 0);
+      if ((rc = upload(h->snap_tasks[b], t0.data(), t0.size()))) return rc;
+    }
+  }
   if ((rc = upload(h->dyn_waves, dyn.data(), dyn.size()))) return rc;
   if ((rc = upload(h->ray_waves, ray.data(), ray.size()))) return rc;
   h->ray_waves_h = ray;
@@ -880,6 +897,9 @@ static void make_kargs(rx_env* h, const rx_io* io, int mode, const uint8_t* mask
   a.lane_tracks = h->lane_tracks;
   a.pos_slot = h->lane_tracks ? h->pos_slot.p : nullptr;
   a.cs_scratch = h->cs_scratch.p;
+  a.ray_x = a.st.x;  // the ray inputs: the working state (rx_steps' carried schedule: a snapshot)
+  a.ray_y = a.st.y;
+  a.ray_angle = a.st.angle;
   a.sort_base = h->sort_base.p;
   a.sort_shift = h->sort_shift;
   a.box_quadrants = h->cfg.box_quadrants >= 0;
@@ -1157,6 +1177,112 @@ static rx_io io_at(const rx_io* io, const rx_io_strides& st, int64_t s) {
   return o;
 }
 
+// rx_steps' carried schedule (DESIGN.md §3 "The carried step") applies to the split step of
+// single-agent envs at one lane per env while nothing records (rx_profile, the counters)
+static bool steps_carried(const rx_env* h, const rx_io* io) {
+  return RX_STEPS_CARRY && split_step(h, RX_MODE_STEP) && h->cfg.n_agents == 1 && h->reward_lpe == 1 && !h->prof &&
+         !io->counters && !h->sort_pending && h->snap_pose[0].p && h->snap_pose[1].p &&
+         (h->cfg.ray_order != 2 || h->lane_tracks || (h->snap_tasks[0].p && h->snap_tasks[1].p));
+}
+
+// K steps with the actions of all of them in device memory: block b's KIN part of step
+// k + 1 needs only block b's REWARD results of step k, so REWARD wave b of step k's
+// k_step2 runs it (k_step2_carry) and k_kin1 leaves the step:
+//   k_kin1(0); per step k: k_step2_carry(REWARD k | rays k | KIN k + 1); plain k_step2(K - 1)
+// A step whose re-sort is due runs the plain k_step2, the sort, then a k_kin1 for the next
+// step (the sort moves rows, and the tasks name positions).  KIN k + 1 overwrites what the
+// ray waves of step k read, so every KIN part also stores its pose and its task row to a
+// snapshot and the ray waves read that: poses alternate by the step's parity within the call
+// (the launch boundary frees the other one), task rows by the sorts of the call (task_sort
+// > 1: the rays read the row last written, which the next sort must not overwrite under
+// them) -- a captured call replays with the same buffers.  Until the call's first sort the
+// rays read the handle's task buffer, which every sort otherwise also writes (it stays the
+// current order for the launches after the call): a CARRIED sort while the rays still read
+// it writes the snapshot alone, and if no later sort of the call brings the handle's buffer
+// up to date the call leaves it marked stale (it is a valid, older order; the next dynamics
+// launch sorts).  No carrying launch reads the buffer it sorts into (rx_launch_step2_carry
+// refuses one).  The working state stays single-buffered and is current after every launch;
+// the bookkeeping (dyn_calls, task_calls, the re-sort) advances as K x rx_step.
+static int steps_carry(rx_env* h, const rx_io* io, const rx_io_strides& st, int32_t K, hipStream_t s) {
+  const size_t N = (size_t)h->cfg.n_envs;
+  rx_kargs a{};
+  make_kargs(h, io, RX_MODE_STEP, nullptr, a);
+  int32_t* const tasks_main = a.tasks_out;  // nullptr: this schedule sorts no ray tasks
+  const int32_t* ray_tasks = h->tasks.p;    // the row the last sort wrote: the handle's before the call's first
+  int tb = 0, rc;
+  bool main_behind = false;  // the last sort left the handle's task buffer out
+  // the KIN part of step k (the ray-task sort's turn as in launch()); carried: in the launch
+  // whose ray waves read ray_tasks
+  auto kin_args = [&](int32_t k, bool carried) {
+    a.snap_x = h->snap_pose[k & 1].p;
+    a.snap_y = a.snap_x + N;
+    a.snap_angle = a.snap_x + 2 * N;
+    a.tasks_out = tasks_main;
+    a.tasks_snap = nullptr;
+    if (tasks_main) {
+      if (h->tasks_stale || (h->task_calls % (uint64_t)h->task_sort) == 0) {
+        h->tasks_stale = false;
+        main_behind = carried && ray_tasks == tasks_main;  // this launch's ray waves read the handle's buffer
+        if (main_behind)
+          a.tasks_out = h->snap_tasks[tb].p;
+        else
+          a.tasks_snap = h->snap_tasks[tb].p;
+        ray_tasks = h->snap_tasks[tb].p;
+        tb ^= 1;
+      } else {
+        a.tasks_out = nullptr;
+      }
+      ++h->task_calls;
+    }
+  };
+  a.io = io_at(io, st, 0);
+  kin_args(0, false);
+  if ((rc = rx_launch_split(&a, 1, RX_SPLIT_KIN, s)) != 0)
+    return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
+  for (int32_t k = 0; k < K; ++k) {
+    a.io = io_at(io, st, k);
+    a.ray_x = h->snap_pose[k & 1].p;  // what KIN k stored
+    a.ray_y = a.ray_x + N;
+    a.ray_angle = a.ray_x + 2 * N;
+    a.tasks = ray_tasks;
+    const bool resort = h->cfg.sort_interval > 0 && h->sort_on && (h->dyn_calls++ % h->cfg.sort_interval) == 0;
+    a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
+    if (!resort && k + 1 < K) {
+      a.io_next = io_at(io, st, k + 1);
+      kin_args(k + 1, true);
+      if ((rc = rx_launch_step2_carry(&a, s)) != 0)
+        return fail(RX_EHIP, "k_step2_carry launch failed: %s", hipGetErrorString((hipError_t)rc));
+      continue;
+    }
+    if (resort) {  // as launch(): the REWARD half writes the keys and counts the bins
+      if (h->sort_hist_done) RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sort_bins * sizeof(uint32_t), s));
+      a.sort_keys = h->keys_in.p;
+      a.sort_hist = h->sort_hist.p;
+      a.sort_off = h->keys_off.p;
+    }
+    a.tasks_out = nullptr;
+    if ((rc = rx_launch_split(&a, 1, RX_SPLIT_REWARD_RAYS, s)) != 0)
+      return fail(RX_EHIP, "k_step2 launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (resort) {
+      h->sort_hist_done = false;
+      h->tasks_stale = true;  // the re-sort moves envs between blocks
+      rx_state work = h->work, tmp = h->work_tmp;
+      if ((rc = rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, 1, h->sort_hist.p, h->sort_cursor.p,
+                             h->sort_bins, h->perm[0].p, h->perm[1].p, &work, &tmp, s, 1)) != 0)
+        return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    if (k + 1 < K) {
+      a.io = io_at(io, st, k + 1);
+      a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
+      kin_args(k + 1, false);
+      if ((rc = rx_launch_split(&a, 1, RX_SPLIT_KIN, s)) != 0)
+        return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+  }
+  if (main_behind) h->tasks_stale = true;
+  return RX_OK;
+}
+
 int rx_steps(rx_env* h, const rx_io* io, int32_t n_steps, const rx_io_strides* strides, void* stream) {
   if (!h) return fail(RX_EINVAL, "null handle");
   if (!io) return fail(RX_EINVAL, "io is null");
@@ -1166,6 +1292,7 @@ int rx_steps(rx_env* h, const rx_io* io, int32_t n_steps, const rx_io_strides* s
     return fail(RX_ESTATE, "rx_steps needs rx_upload_tracks, rx_assign and rx_bind_state");
   const rx_io_strides st = strides ? *strides : rx_io_strides{};
   int rc;
+  if (steps_carried(h, io) && n_steps > 0) return steps_carry(h, io, st, n_steps, (hipStream_t)stream);
   for (int32_t k = 0; k < n_steps; ++k) {
     const rx_io o = io_at(io, st, k);
     if ((rc = launch(h, &o, RX_MODE_STEP, nullptr, stream)) != 0) return rc;

@@ -190,7 +190,29 @@ struct rx_kargs {
   int64_t n_draws;
   const int64_t* draw_base;
   const int32_t* reset_rank;
+  // Ray inputs: what a ray wave reads of the stepped state (position order) -- st.x, st.y,
+  // st.angle (and `tasks` above) in every launch but rx_steps' carried ones, where they are
+  // the step's pose snapshot: the REWARD waves of a carrying k_step2 run the next step's KIN
+  // part, which overwrites the working state under this step's ray waves.
+  const double* ray_x;
+  const double* ray_y;
+  const double* ray_angle;
+  // rx_steps' carried schedule: KIN also stores its stepped pose here (the snapshot its
+  // step's ray waves read), and its sorted task row to tasks_snap; nullptr = no snapshot
+  double* snap_x;
+  double* snap_y;
+  double* snap_angle;
+  int32_t* tasks_snap;
+  // carrying k_step2: the io rows of the NEXT step (its KIN part writes them; by env id)
+  rx_io io_next;
 };
+
+// rx_steps' carried schedule (DESIGN.md §3 "The carried step"): the REWARD waves of step
+// t's k_step2 also run step t + 1's KIN part, so k_kin1 leaves the step.  0 = a k_kin1 and a
+// k_step2 launch per step.
+#ifndef RX_STEPS_CARRY
+#define RX_STEPS_CARRY 1
+#endif
 
 extern "C" int rx_launch_step(const rx_kargs* a, int n_agents, int phases, hipStream_t s);
 // split step (STEP mode, next-step / no autoreset): k_kin1 / k_kin2, then k_step2<A>
@@ -198,6 +220,10 @@ extern "C" int rx_launch_step(const rx_kargs* a, int n_agents, int phases, hipSt
 #define RX_SPLIT_REWARD 1
 #define RX_SPLIT_REWARD_RAYS 2
 extern "C" int rx_launch_split(const rx_kargs* a, int n_agents, int part, hipStream_t s);
+// the carrying k_step2 (single-agent, one lane per env): REWARD of a->io's step beside its
+// raycast, then KIN (and the ray-task sort, with a->tasks_out) of a->io_next's step in the
+// REWARD waves
+extern "C" int rx_launch_step2_carry(const rx_kargs* a, hipStream_t s);
 // persistent small-N rollout (k_rollout): a->n_dyn_waves workgroups, one env
 // each, its slot staged in max_w * 96 bytes of dynamic LDS
 #define RX_ROLLOUT_MAX_W 1024

@@ -526,6 +526,10 @@ __device__ __forceinline__ void sort_block_tasks(const rx_kargs& a, int perm_sta
   const int lane = threadIdx.x & 63;
   int32_t* out = a.tasks_out + (size_t)perm_start * (A * a.n_sensors);
   for (int i = lane; i < total; i += 64) stc(out + i, stage[i]);
+  if (a.tasks_snap) {  // rx_steps' carried schedule: the row this step's ray waves read
+    int32_t* snap = a.tasks_snap + (size_t)perm_start * (A * a.n_sensors);
+    for (int i = lane; i < total; i += 64) stc(snap + i, stage[i]);
+  }
 }
 
 __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
@@ -820,6 +824,11 @@ __device__ __forceinline__ void dyn1_env(const rx_kargs& a, int wave, double* an
     stc(S.vy + p, c.vy);
     stc(S.last_steering + p, last_steering);
     stc(S.steps + p, steps);
+    if (a.snap_x) {  // rx_steps' carried schedule: the pose this step's ray waves read
+      stc(a.snap_x + p, c.x);
+      stc(a.snap_y + p, c.y);
+      stc(a.snap_angle + p, c.angle);
+    }
     if (moving) {
       reinterpret_cast<double2*>(a.cs_scratch)[p] = make_double2(cs[0], cs[1]);
     }
@@ -1946,8 +1955,9 @@ __device__ __forceinline__ void rays_wave(const rx_kargs& a, const rx_wave we, c
   const int S_ = 2 * W;
   const double4* __restrict__ seg = reinterpret_cast<const double4*>(a.tr.seg) + 2 * wp0;
   const int i = A * pos + q;  // working state (position order); the obs row is A * perm[pos] + q
-  const double ox = ldc(a.st.x + i), oy = ldc(a.st.y + i);
-  const double theta = ldc(a.st.angle + i) + a.rel_angles[ray];  // racing_env.py:50
+  // the ray inputs: the working state, or the step's pose snapshot (rx_steps' carried schedule)
+  const double ox = ldc(a.ray_x + i), oy = ldc(a.ray_y + i);
+  const double theta = ldc(a.ray_angle + i) + a.rel_angles[ray];  // racing_env.py:50
   RAY_STAMP(1);
   double sn, cs;
   rx_sincos(theta, &sn, &cs);
@@ -2210,9 +2220,17 @@ __global__ __launch_bounds__(256) void k_rays_wide(rx_kargs a) {
 // the raycast's 64-VGPR cap (k_step2<1>: 36 B/lane of scratch) whichever
 // schedule ran.  For A = 2, RLPE 2 gives each car of an env its own lane in the
 // REWARD half (dyn2_env<REWARD, 2>).
-template <int A, int RLPE, int LPR, bool LV = false>
-__global__ __launch_bounds__(64, A == 1 ? (LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW) : RX_STEP2_MINW_2) void k_step2(
-    rx_kargs a, int n_rw) {
+//
+// CARRY (k_step2_carry, rx_steps' carried schedule; DESIGN.md §3 "The carried step"):
+// REWARD workgroup b goes on, in the same 64 lanes over the same 64 envs, with the KIN
+// part of the NEXT step and the block's ray-task sort -- k_kin1's work, by k_kin1's
+// functions -- under this step's raycast.  KIN reads what REWARD has just stored for its
+// own lane (flags, progress, episode counters: plain per-lane loads after per-lane
+// stores) and writes the next step's rows (a.io_next); it overwrites the working pose
+// and the task buffer, so the launch's ray waves read a snapshot (a.ray_x / ray_y /
+// ray_angle, a.tasks) that the KIN part of THEIR step stored.
+template <int A, int RLPE, int LPR, bool LV, bool CARRY>
+__device__ __forceinline__ void step2_body(const rx_kargs& a, int n_rw) {
   const int b = uniform((int)blockIdx.x);
   const unsigned long long prof_t0 = prof_start(a);
   if (b < n_rw) {
@@ -2236,10 +2254,38 @@ __global__ __launch_bounds__(64, A == 1 ? (LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW
       dyn2_env<RX_PART_REWARD>(a, b, ang, e, ep);
     }
     add_episode_stats(a, ep);
+    if constexpr (CARRY) {
+      static_assert(A == 1 && RLPE == 1, "the carried step: single-agent envs, one lane per env");
+      if (b < a.n_dyn_waves) {  // (n_rw pads the REWARD workgroups to a multiple of 8)
+        // as k_kin1: 64 sector counters and the staging row (dynamic LDS, only when sorting)
+        extern __shared__ int32_t task_lds[];
+        int32_t* cnt = task_lds;
+        int32_t* stage = cnt + kTaskSectors;
+        const bool sorting = a.tasks_out != nullptr;
+        if (sorting) cnt[threadIdx.x & 63] = 0;
+        rx_kargs an = a;
+        an.io = a.io_next;
+        double ang1[1], ep1[3];
+        int p1 = -1;
+        dyn1_env<1, RX_PART_KIN, LV>(an, b, ang1, p1, ep1);
+        if (sorting) sort_block_tasks<1>(an, uniform(a.dyn_waves[b].perm_start), p1, ang1, cnt, stage);
+      }
+    }
   } else {
     rays_dispatch<A, LPR, LV, LPR == 4>(a, b - n_rw);  // PF: prefetched leaf scans at 4 lanes per ray
   }
   prof_end(a, b, prof_t0);
+}
+
+template <int A, int RLPE, int LPR, bool LV = false>
+__global__ __launch_bounds__(64, A == 1 ? (LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW) : RX_STEP2_MINW_2) void k_step2(
+    rx_kargs a, int n_rw) {
+  step2_body<A, RLPE, LPR, LV, false>(a, n_rw);
+}
+
+template <int LPR, bool LV = false>
+__global__ __launch_bounds__(64, LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW) void k_step2_carry(rx_kargs a, int n_rw) {
+  step2_body<1, 1, LPR, LV, true>(a, n_rw);
 }
 
 // ============================================================ k_rollout
@@ -2652,6 +2698,27 @@ extern "C" int rx_launch_split(const rx_kargs* a, int n_agents, int part, hipStr
     launch_step2_lpr<1, 2>(a, grid, n_rw, s);
   else
     launch_step2_lpr<1, 1>(a, grid, n_rw, s);
+  return (int)hipGetLastError();
+}
+
+// The carrying k_step2: every workgroup of the launch gets the KIN part's sort LDS (the
+// ray workgroups leave it unused), so the staging row is sized for the handle's sensors,
+// not for the 16 the sort allows: 64 + 64 R words (3 KiB at 11 sensors; 32 workgroups a
+// CU keep k_step2's 8 waves per SIMD within the CU's LDS up to 16 sensors, 4.25 KiB).
+// The launch's ray waves read a->tasks while its KIN part sorts: never into the same buffer.
+extern "C" int rx_launch_step2_carry(const rx_kargs* a, hipStream_t s) {
+  if (a->tasks_out && (a->tasks_out == a->tasks || a->tasks_snap == a->tasks)) return (int)hipErrorInvalidValue;
+  const int n_rw = (a->n_dyn_waves + 7) / 8 * 8;
+  const dim3 grid(n_rw + a->n_ray_waves);
+  const size_t lds = a->tasks_out ? (size_t)(kTaskSectors + 64 * a->n_sensors) * sizeof(int32_t) : 0;
+  if (a->lane_tracks)
+    hipLaunchKernelGGL((k_step2_carry<1, true>), grid, dim3(64), lds, s, *a, n_rw);
+  else if (a->ray_lpr == 4)
+    hipLaunchKernelGGL((k_step2_carry<4>), grid, dim3(64), lds, s, *a, n_rw);
+  else if (a->ray_lpr == 2)
+    hipLaunchKernelGGL((k_step2_carry<2>), grid, dim3(64), lds, s, *a, n_rw);
+  else
+    hipLaunchKernelGGL((k_step2_carry<1>), grid, dim3(64), lds, s, *a, n_rw);
   return (int)hipGetLastError();
 }
 

@@ -482,7 +482,7 @@ class RacingVectorEnv:
         every step given up front: ``actions`` [K, N, (A,) 2] float32 on the device.
         Equal to K step_device calls on actions[0], ..., actions[K-1] bit for bit.
         ``obs_out`` / ``reward_out`` / ``done_out``: None = the env's own rows (each
-        step overwrites them: they end with the last step's outputs), or [K, ...]
+        step overwrites them: once the call's work has completed they hold the last step's), or [K, ...]
         buffers whose row k receives step k.  Returns the last step's (obs, reward,
         done_f32)."""
         dev_idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
