@@ -681,6 +681,93 @@ typedef struct rx_eval_io {
 } rx_eval_io;
 int rx_eval_steps(rx_env* h, const rx_io* io, const rx_eval_io* ev, int32_t n_steps, void* stream);
 
+/* ABI v25, additive: rgb_array rendering on the device.  Replaces the drawing of
+ * utils/visualization.py:103-120, :218-250 (pygame) by three handle-free kernels
+ * (csrc/rx_render.hip) with bit-identical host twins; the rules live in
+ * csrc/rx_raster.h and DESIGN.md §4 -- this project's own exact rules, not
+ * pygame's pixels, and no HUD text.
+ *
+ * Pixel classes of the static layer (one byte per pixel, later overwrites
+ * earlier) and the bits of the trail layer: */
+#define RX_PX_BACKGROUND 0  /* (50,50,50) */
+#define RX_PX_TRACK 1       /* (180,180,180): even-odd fill of track_polygon */
+#define RX_PX_BORDER 2      /* (0,0,0): both boundary loops, closed, width 4 */
+#define RX_PX_START 3       /* (0,255,0): the start line, width 5 */
+#define RX_PX_TRAIL0 0x10   /* (255,100,100): car 0's path, width 3 */
+#define RX_PX_TRAIL1 0x20   /* (100,100,255): car 1's path, drawn over car 0's */
+#define RX_RASTER_SIZE_MIN 16
+#define RX_RASTER_SIZE_MAX 2048
+#define RX_RASTER_MAX_IMAGES 65535 /* K and n_layers: one grid dimension */
+/* rx_raster_static: the static layers of n tracks, once per track.
+ *   edge_off int32 [n+1]: layer k owns edges [edge_off[k], edge_off[k+1]);
+ *   edges    int32 [n_edges][6]: ax, ay, bx, by in integer screen coordinates
+ *            (rx.render.track_view), class 1..7, width.  width 0: an edge of the
+ *            polygon filled with `class` by the even-odd rule; width > 0: a thick
+ *            line of `class`.  A pixel gets the highest class that covers it;
+ *   layer    uint8 [n][size][size], written in full.
+ * k_raster_static: a 16x16 pixel tile per block, the edges staged through LDS
+ * 256 at a time, each tested against the tile first (a conservative test: the
+ * layer is the same with and without it).
+ *
+ * rx_raster_io: K images of `size` x `size` pixels.  Image k shows env
+ * env_ids[k]; the poses are the env-order state arrays rx_state_export fills
+ * (element e*A+q of x, y, angle), so no handle is needed.
+ *   view     f64 [K][3]: scale, offset_x, offset_y of setup_track_visualization;
+ *   layer_of int32 [K]: the static layer of image k;
+ *   trail    uint8 [K][size][size]; last int32 [K][A][3] = (x, y, valid), the
+ *            last path point of each car.  Zero both to begin an episode;
+ *   out      image k's pixel (row j, column i) is the 3 bytes R, G, B at
+ *            out + out_off[k] + j*out_pitch + 3*i, so K images compose straight
+ *            into one mosaic; out_size is the byte size of the buffer behind
+ *            `out`, and an image that would not fit in it is not written.
+ * An env id outside [0, n_envs) or a layer outside [0, n_layers) leaves the
+ * image's cars / the image alone.  A car with a non-finite pose is not drawn and
+ * adds no path point for that call.
+ *
+ * rx_raster_trail (after each step; reads env_ids, x, y, view, trail, last): per
+ * car, convert_coords of (x, y); if the car has a last point, the capsule of
+ * width 3 from it to the new point is OR-ed into trail with the car's bit; the
+ * point becomes the last one.  One block per image, car 0 then car 1.
+ * rx_raster_frame (reads everything but last): the colour of every pixel from
+ * the static class, the trail bits and the up-to-two car quads (fill, then
+ * outline of width 2; car 1 over car 0).  Each lane owns 4 consecutive pixels of
+ * a row and stores 12 bytes, as three dwords when the image's rows start on
+ * 4-byte boundaries (out + out_off[k] and out_pitch both multiples of 4) and
+ * by bytes otherwise: a [K][size][size][3] stack with size % 4 == 0 takes the
+ * fast path, a mosaic only when its padding keeps the rows aligned.
+ *
+ * All pointers are DEVICE pointers; the *_host twins take the same arguments as
+ * HOST pointers, ignore `stream`, make no HIP call and give the same bytes.
+ * Checked before any launch (RX_EINVAL, the message names the field): null
+ * pointers, size outside 16..2048, A not 1 or 2, K <= 0 or above 65535, n_envs
+ * or n_layers <= 0, out_pitch negative or below 3*size, out_size < 0; for
+ * rx_raster_static n outside 1..65535 and n_edges < 0.  The launches are
+ * enqueued on `stream` and no call waits. */
+typedef struct rx_raster_io {
+  int32_t K, A, size, n_envs, n_layers, reserved0;
+  const int32_t* env_ids;  /* [K] */
+  const double* x;         /* [n_envs*A] */
+  const double* y;
+  const double* angle;
+  const double* view;      /* [K][3] */
+  const int32_t* layer_of; /* [K] */
+  const uint8_t* layer;    /* [n_layers][size][size] */
+  uint8_t* trail;          /* [K][size][size] */
+  int32_t* last;           /* [K][A][3] */
+  uint8_t* out;
+  const int64_t* out_off;  /* [K] */
+  int64_t out_pitch;
+  int64_t out_size;
+} rx_raster_io;
+int rx_raster_static(int32_t n, int32_t size, int32_t n_edges, const int32_t* edge_off, const int32_t* edges,
+                     uint8_t* layer, void* stream);
+int rx_raster_static_host(int32_t n, int32_t size, int32_t n_edges, const int32_t* edge_off, const int32_t* edges,
+                          uint8_t* layer, void* stream);
+int rx_raster_trail(const rx_raster_io* r, void* stream);
+int rx_raster_trail_host(const rx_raster_io* r, void* stream);
+int rx_raster_frame(const rx_raster_io* r, void* stream);
+int rx_raster_frame_host(const rx_raster_io* r, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

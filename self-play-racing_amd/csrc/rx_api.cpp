@@ -1590,6 +1590,101 @@ int rx_build_tracks_host(int32_t n, int32_t factor, const int32_t* cp_off, const
   return RX_OK;
 }
 
+// ---- rendering (ABI v25, additive) ---------------------------------------------
+static int raster_static_args(const char* fn, int32_t n, int32_t size, int32_t n_edges, const void* edge_off,
+                              const void* edges, const void* layer) {
+  if (n <= 0 || n > RX_RASTER_MAX_IMAGES) return fail(RX_EINVAL, "%s: n=%d outside 1..%d", fn, n, RX_RASTER_MAX_IMAGES);
+  if (size < RX_RASTER_SIZE_MIN || size > RX_RASTER_SIZE_MAX)
+    return fail(RX_EINVAL, "%s: size=%d outside %d..%d", fn, size, RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX);
+  if (n_edges < 0) return fail(RX_EINVAL, "%s: n_edges=%d is negative", fn, n_edges);
+  if (!edge_off) return fail(RX_EINVAL, "%s: null pointer: edge_off", fn);
+  if (!edges) return fail(RX_EINVAL, "%s: null pointer: edges", fn);
+  if (!layer) return fail(RX_EINVAL, "%s: null pointer: layer", fn);
+  return RX_OK;
+}
+
+// frame = 0: what rx_raster_trail reads; 1: what rx_raster_frame reads.
+static int raster_io_args(const char* fn, const rx_raster_io* r, int frame) {
+  if (!r) return fail(RX_EINVAL, "%s: null pointer: r", fn);
+  if (r->size < RX_RASTER_SIZE_MIN || r->size > RX_RASTER_SIZE_MAX)
+    return fail(RX_EINVAL, "%s: size=%d outside %d..%d", fn, r->size, RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX);
+  if (r->A != 1 && r->A != 2) return fail(RX_EINVAL, "%s: A=%d must be 1 or 2", fn, r->A);
+  if (r->K <= 0 || r->K > RX_RASTER_MAX_IMAGES)
+    return fail(RX_EINVAL, "%s: K=%d outside 1..%d", fn, r->K, RX_RASTER_MAX_IMAGES);
+  if (r->n_envs <= 0) return fail(RX_EINVAL, "%s: n_envs=%d must be > 0", fn, r->n_envs);
+#define RX_RASTER_PTR(f) \
+  if (!r->f) return fail(RX_EINVAL, "%s: null pointer: " #f, fn)
+  RX_RASTER_PTR(env_ids);
+  RX_RASTER_PTR(x);
+  RX_RASTER_PTR(y);
+  RX_RASTER_PTR(view);
+  RX_RASTER_PTR(trail);
+  if (!frame) {
+    RX_RASTER_PTR(last);
+    return RX_OK;
+  }
+  RX_RASTER_PTR(angle);
+  RX_RASTER_PTR(layer_of);
+  RX_RASTER_PTR(layer);
+  RX_RASTER_PTR(out);
+  RX_RASTER_PTR(out_off);
+#undef RX_RASTER_PTR
+  if (r->n_layers <= 0) return fail(RX_EINVAL, "%s: n_layers=%d must be > 0", fn, r->n_layers);
+  if (r->out_pitch < 0) return fail(RX_EINVAL, "%s: out_pitch=%lld is negative", fn, (long long)r->out_pitch);
+  if (r->out_pitch < 3 * (int64_t)r->size)
+    return fail(RX_EINVAL, "%s: out_pitch=%lld below 3*size=%d", fn, (long long)r->out_pitch, 3 * r->size);
+  if (r->out_size < 0) return fail(RX_EINVAL, "%s: out_size=%lld is negative", fn, (long long)r->out_size);
+  return RX_OK;
+}
+
+int rx_raster_static(int32_t n, int32_t size, int32_t n_edges, const int32_t* edge_off, const int32_t* edges,
+                     uint8_t* layer, void* stream) {
+  int rc = raster_static_args("rx_raster_static", n, size, n_edges, edge_off, edges, layer);
+  if (rc != RX_OK) return rc;
+  if ((rc = rx_launch_raster_static(n, size, n_edges, edge_off, edges, layer, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_raster_static: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_raster_trail(const rx_raster_io* r, void* stream) {
+  int rc = raster_io_args("rx_raster_trail", r, 0);
+  if (rc != RX_OK) return rc;
+  if ((rc = rx_launch_raster_trail(r, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_raster_trail: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_raster_frame(const rx_raster_io* r, void* stream) {
+  int rc = raster_io_args("rx_raster_frame", r, 1);
+  if (rc != RX_OK) return rc;
+  if ((rc = rx_launch_raster_frame(r, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_raster_frame: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+// The host twins: argument checks here, the loops in rx_raster_host.cpp.
+int rx_raster_static_host(int32_t n, int32_t size, int32_t n_edges, const int32_t* edge_off, const int32_t* edges,
+                          uint8_t* layer, void* /*stream*/) {
+  const int rc = raster_static_args("rx_raster_static_host", n, size, n_edges, edge_off, edges, layer);
+  if (rc != RX_OK) return rc;
+  rx_host_raster_static(n, size, n_edges, edge_off, edges, layer);
+  return RX_OK;
+}
+
+int rx_raster_trail_host(const rx_raster_io* r, void* /*stream*/) {
+  const int rc = raster_io_args("rx_raster_trail_host", r, 0);
+  if (rc != RX_OK) return rc;
+  rx_host_raster_trail(r);
+  return RX_OK;
+}
+
+int rx_raster_frame_host(const rx_raster_io* r, void* /*stream*/) {
+  const int rc = raster_io_args("rx_raster_frame_host", r, 1);
+  if (rc != RX_OK) return rc;
+  rx_host_raster_frame(r);
+  return RX_OK;
+}
+
 static int adam_cfg_error(const rx_adam_config* cfg) {
   if (!cfg) return fail(RX_EINVAL, "rx_adam: cfg is null");
   if (cfg->n_tensors <= 0 || cfg->n_tensors > RX_ADAM_MAX_TENSORS)

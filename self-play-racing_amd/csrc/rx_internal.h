@@ -243,6 +243,16 @@ extern "C" int rx_launch_gae(int T, int N, const float* r, const float* v, const
 extern "C" int rx_launch_build_tracks(int n_tracks, int factor, const int32_t* cp_off, const double* cp,
                                       const double* width, double* wp, double* nrm, double* seg, double* meta,
                                       hipStream_t s);
+// rx_render.hip: the renderer's three kernels (arguments checked by rx_api.cpp)
+extern "C" int rx_launch_raster_static(int n, int size, int n_edges, const int32_t* edge_off, const int32_t* edges,
+                                       uint8_t* layer, hipStream_t s);
+extern "C" int rx_launch_raster_trail(const rx_raster_io* r, hipStream_t s);
+extern "C" int rx_launch_raster_frame(const rx_raster_io* r, hipStream_t s);
+// rx_raster_host.cpp: the same three as host loops (plain C++, no HIP call)
+extern "C" void rx_host_raster_static(int32_t n, int32_t size, int32_t n_edges, const int32_t* edge_off,
+                                      const int32_t* edges, uint8_t* layer);
+extern "C" void rx_host_raster_trail(const rx_raster_io* r);
+extern "C" void rx_host_raster_frame(const rx_raster_io* r);
 // Adam's per-step scalars for step count s (torch.optim.Adam, non-capturable):
 // out[0] = step_size = -lr / (1 - beta1^s), out[1] = sqrt(1 - beta2^s).  Written
 // once per optimizer step next to the clip-norm partials (rx_adam_workspace_floats

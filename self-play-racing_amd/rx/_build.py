@@ -17,8 +17,12 @@ CSRC = os.path.join(ROOT, "csrc")
 INCLUDE = os.path.join(REPO, "include")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "librx.so")
-SOURCES = ["rx_kernels.hip", "rx_sort.hip", "rx_optim.hip", "rx_ppo.hip", "rx_track.hip", "rx_eval.hip", "rx_api.cpp"]
-HEADERS = ["rx_internal.h", "rx_math.h", "rx_sincos_table.h", "rx_policy.h", "rx_policy_mfma.h", "rx_spline.h"]
+SOURCES = ["rx_kernels.hip", "rx_sort.hip", "rx_optim.hip", "rx_ppo.hip", "rx_track.hip", "rx_eval.hip", "rx_render.hip",
+           "rx_api.cpp", "rx_raster_host.cpp"]
+# compiled as plain C++, not as HIP: shared headers take their host form (rx_math.h's rx_sincos on the host)
+HOST_ONLY = {"rx_raster_host.cpp"}
+HEADERS = ["rx_internal.h", "rx_math.h", "rx_sincos_table.h", "rx_policy.h", "rx_policy_mfma.h", "rx_spline.h",
+           "rx_raster.h"]
 
 ARCH = os.environ.get("RX_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=off: no implicit FMA anywhere (bit-exact with the reference's
@@ -54,7 +58,8 @@ def build(force=False, verbose=True, out=None, defines=()):
         obj = os.path.join(LIBDIR, os.path.splitext(src)[0] + ".o")
         if out is not None:
             obj = os.path.splitext(out)[0] + "_" + os.path.splitext(src)[0] + ".o"
-        cmd = [cc] + FLAGS + [f"-D{d}" for d in defines] + ["-c", os.path.join(CSRC, src), "-o", obj]
+        flags = [f for f in FLAGS if not f.startswith("--offload-arch")] + ["-x", "c++"] if src in HOST_ONLY else FLAGS
+        cmd = [cc] + flags + [f"-D{d}" for d in defines] + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

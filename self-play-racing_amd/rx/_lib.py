@@ -33,7 +33,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_state_import", "rx_state_export", "rx_schedule",
            "rx_ppo_adv_workspace_doubles", "rx_ppo_adv_stats_ws", "rx_profile_waves", "rx_ray_waves", "rx_ray_tasks", "rx_set_start_draws",
            "rx_rollout_steps", "rx_selfplay_rollout_steps", "rx_steps", "rx_build_tracks", "rx_build_tracks_host",
-           "rx_eval_steps")
+           "rx_eval_steps", "rx_raster_static", "rx_raster_static_host", "rx_raster_trail", "rx_raster_trail_host",
+           "rx_raster_frame", "rx_raster_frame_host")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -126,6 +127,17 @@ class RxEvalIO(ctypes.Structure):
                                   "n_active")]
 
 
+# rendering (ABI v25, additive): pixel classes / trail bits, size limits, edge record width (include/rx.h)
+RX_PX_BACKGROUND, RX_PX_TRACK, RX_PX_BORDER, RX_PX_START, RX_PX_TRAIL0, RX_PX_TRAIL1 = 0, 1, 2, 3, 0x10, 0x20
+RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX, RX_RASTER_EDGE_W = 16, 2048, 6
+RASTER_PTR_FIELDS = ("env_ids", "x", "y", "angle", "view", "layer_of", "layer", "trail", "last", "out", "out_off")
+
+
+class RxRasterIO(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("K", "A", "size", "n_envs", "n_layers", "reserved0")] + \
+               [(k, _P) for k in RASTER_PTR_FIELDS] + [("out_pitch", ctypes.c_int64), ("out_size", ctypes.c_int64)]
+
+
 class RxError(RuntimeError):
     pass
 
@@ -206,6 +218,10 @@ def load(build_if_missing=True):
     L.rx_build_tracks.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_P] * 9
     L.rx_build_tracks_host.argtypes = L.rx_build_tracks.argtypes
     L.rx_eval_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxEvalIO), ctypes.c_int32, _P]
+    for sfx in ("", "_host"):
+        getattr(L, "rx_raster_static" + sfx).argtypes = [ctypes.c_int32] * 3 + [_P] * 4
+        getattr(L, "rx_raster_trail" + sfx).argtypes = [ctypes.POINTER(RxRasterIO), _P]
+        getattr(L, "rx_raster_frame" + sfx).argtypes = [ctypes.POINTER(RxRasterIO), _P]
     for name in EXPORTS:
         if name not in ("rx_last_error", "rx_abi_version", "rx_ppo_workspace_floats", "rx_ppo_workspace_doubles",
                         "rx_ppo_update_workspace_floats", "rx_adam_workspace_floats",

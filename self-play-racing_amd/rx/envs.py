@@ -27,14 +27,45 @@ def _resolve_track(track_pool, track_id, track_width):
     return cp, (DEFAULT_WIDTH if track_width is None else track_width)
 
 
+RENDER_SIZE = 800  # visualization.py:68, :170
+
+
 class _SpecEnv:
     num_agents = 1
     half_cone = np.pi / 3
+    metadata = {"render_modes": ["rgb_array"]}
+    render_mode = None
 
-    def _init_track(self, track_pool, track_id, track_width):
+    def _init_track(self, track_pool, track_id, track_width, render_mode=None):
         self.control_points, self.track_width = _resolve_track(track_pool, track_id, track_width)
         self._track = None
         self._venv = None
+        if render_mode is not None and render_mode not in self.metadata["render_modes"]:
+            raise ValueError(f"render_mode must be None or one of {self.metadata['render_modes']}, got {render_mode!r}")
+        self.render_mode = render_mode
+        self._renderer = None
+
+    def _render_begin(self):
+        """reset(): a new, empty path."""
+        if self.render_mode is None:
+            return
+        if self._renderer is None:
+            from .render import Renderer
+            self._renderer = Renderer(self._vec(), size=RENDER_SIZE)
+        self._renderer.begin()
+
+    def _render_step(self):
+        if self._renderer is not None:
+            self._renderer.step()
+
+    def render(self):
+        """The current frame, uint8 (800, 800, 3) (rx.render: track, paths and cars,
+        no HUD text), or None when ``render_mode`` is None."""
+        if self.render_mode is None:
+            return None
+        if self._renderer is None:
+            self._render_begin()
+        return self._renderer.frame()[0].cpu().numpy()
 
     @property
     def track(self):
@@ -51,6 +82,7 @@ class _SpecEnv:
         return self._venv
 
     def close(self):
+        self._renderer = None
         if self._venv is not None:
             self._venv.close()
             self._venv = None
@@ -59,10 +91,9 @@ class _SpecEnv:
 class RacingEnv(_SpecEnv):
     """environment/racing_env.py:8-167 (Gymnasium surface), device-backed."""
 
-    metadata = {"render_modes": []}
-
-    def __init__(self, num_sensors=7, track_pool=None, track_id=None, track_width=None, speed_weight=8.0):
-        self._init_track(track_pool, track_id, track_width)
+    def __init__(self, num_sensors=7, track_pool=None, track_id=None, track_width=None, speed_weight=8.0,
+                 render_mode=None):
+        self._init_track(track_pool, track_id, track_width, render_mode)
         self.num_sensors = num_sensors
         self.max_sensor_range = 50.0
         self._speed_weight = speed_weight
@@ -94,11 +125,13 @@ class RacingEnv(_SpecEnv):
     def reset(self, seed=None, options=None):
         v = self._vec()
         v.reset_device()
+        self._render_begin()
         return v.buf["obs"][0].cpu().numpy().copy(), self._info(False)
 
     def step(self, action):
         v = self._vec()
         v.step_device(np.asarray(action, dtype=np.float32).reshape(1, 2), full_info=True)
+        self._render_step()
         obs = v.buf["obs"][0].cpu().numpy().copy()
         info = self._info(True)
         return (obs, info["reward"], bool(v.buf["terminated"][0].item()), bool(v.buf["truncated"][0].item()), info)
@@ -109,10 +142,11 @@ class MultiRacingEnv(_SpecEnv):
 
     half_cone = np.pi / 2
 
-    def __init__(self, num_agents=2, num_sensors=11, track_pool=None, track_id=None, track_width=None):
+    def __init__(self, num_agents=2, num_sensors=11, track_pool=None, track_id=None, track_width=None,
+                 render_mode=None):
         if num_agents != 2:
             raise NotImplementedError("the device kernel implements the 2-car race (num_agents=2) used by train.py")
-        self._init_track(track_pool, track_id, track_width)
+        self._init_track(track_pool, track_id, track_width, render_mode)
         self.num_agents = num_agents
         self.num_sensors = num_sensors
         self.max_sensor_range = 50.0
@@ -140,6 +174,7 @@ class MultiRacingEnv(_SpecEnv):
     def reset(self, seed=None, options=None):
         v = self._vec()
         v.reset_device()
+        self._render_begin()
         obs = v.buf["obs"][0].cpu().numpy()
         return {f"{i}": obs[i].copy() for i in range(2)}, self._infos(False)
 
@@ -147,6 +182,7 @@ class MultiRacingEnv(_SpecEnv):
         v = self._vec()
         a = np.stack([np.asarray(actions[f"{i}"], dtype=np.float32) for i in range(2)])[None]
         v.step_device(a, full_info=True)
+        self._render_step()
         obs = v.buf["obs"][0].cpu().numpy()
         rew = v.buf["reward64"][0].cpu().numpy()
         term = bool(v.buf["terminated"][0].item())
@@ -194,6 +230,9 @@ class SelfPlayWrapper:
         self.last_obs_dict = obs
         return (obs[f"{self.agent_idx}"], rew[f"{self.agent_idx}"], dones["__all__"], trunc,
                 infos[f"{self.agent_idx}"])
+
+    def render(self):
+        return self.env.render()
 
     @property
     def speed_weight(self):

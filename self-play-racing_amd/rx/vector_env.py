@@ -146,6 +146,7 @@ class RacingVectorEnv:
             ray_order = 2 if R <= 16 else 1
         self.D = R + 4 + 4 * (A - 1)
         self.max_steps = int(max_steps)
+        self.autoreset = autoreset  # read by rx.render.Renderer
         self.speed_weight = float(speed_weight)
         if half_cone is None:
             half_cone = np.pi / 3 if A == 1 else np.pi / 2
