@@ -768,6 +768,72 @@ int rx_raster_trail_host(const rx_raster_io* r, void* stream);
 int rx_raster_frame(const rx_raster_io* r, void* stream);
 int rx_raster_frame_host(const rx_raster_io* r, void* stream);
 
+/* ABI v25, additive: league play -- a policy forward in which every row picks
+ * its weights from a BANK of policies, and the two-car match loop built on it
+ * (rx.league: which of two self-play snapshots is the better racer; the
+ * reference compares models by solo metrics only, evaluate.py:68-122).
+ *
+ * rx_policy_act_bank: rx_policy_act with per-row parameters.  Row r is evaluated
+ * with policy p = policy_of_row[r]: parameters io.params + p * params_stride (the
+ * flat rx_policy_act layout), log-std io.log_std + 2 p, noise io.eps[r]; every
+ * output of row r (action, log-prob, value, the optional actions2 copy) equals bit
+ * for bit what rx_policy_act writes for that row when launched with policy p
+ * alone and the same eps, in both precisions (k_policy_act_bank, csrc/rx_ppo.hip:
+ * a batch row is one MFMA column, so a 16-row tile is evaluated once per distinct
+ * policy present in it and only that policy's rows store; a tile whose rows share
+ * one policy costs what rx_policy_act's tile costs).
+ *   tile_cars 1: a tile is rows 16 b .. 16 b + 15.
+ *   tile_cars 2: the rows are [n / 2][2] (env, car), n even; a tile is car q of 16
+ *     consecutive envs, so it holds one policy whenever those envs share a seating
+ *     (interleaved tiles would hold two every time).  Which tile a row falls in
+ *     never changes what is written for it.
+ * policy_of_row lives in device memory, so it cannot be checked here: every entry
+ * must lie in [0, n_policies).  A row whose entry is outside that range is
+ * skipped: nothing is read and nothing is written for it.
+ * Any params_stride >= rx_ppo_n_params(obs_dim) is accepted; rx.league pads it to a
+ * multiple of 64 floats, so every policy starts on a 256-byte boundary as a
+ * separately allocated one does.
+ * Checked before any HIP call (RX_EINVAL, the message names the field): null io,
+ * obs_dim not 15 or 19, n <= 0, n_policies <= 0, params_stride <
+ * rx_ppo_n_params(obs_dim), precision, tile_cars not 1 or 2 (or n odd with 2),
+ * row strides that overlap, null buffers. */
+typedef struct rx_policy_bank_io {
+  rx_policy_io io;               /* params / log_std: the bank bases [n_policies][params_stride] / [n_policies][2] */
+  int32_t n_policies;
+  int32_t tile_cars;             /* 1 or 2 (above) */
+  int64_t params_stride;         /* floats between two policies' parameters, >= rx_ppo_n_params(obs_dim) */
+  const int32_t* policy_of_row;  /* [n], device memory */
+} rx_policy_bank_io;
+int rx_policy_act_bank(const rx_policy_bank_io* b, void* stream);
+
+/* rx_match_steps: rx_eval_steps' policy mode with a seating.  Per step t: ONE
+ * rx_policy_act_bank launch over the N*A rows of io->obs (tile_cars = A) with
+ * eps[t], car q of env e driven by policy seat[e][q], actions into actions[t];
+ * rx_step of actions[t]; k_eval_acc.  Everything else is rx_eval_steps': the
+ * record layout, the caller's duties before the first call, io->obs written in
+ * place, active / n_active, any autoreset mode, the stream semantics.  A == 1 (any
+ * bank member per env) and A == 2 are accepted.  There is no open-loop mode
+ * (rx_eval_steps has one).  seat entries must lie in [0, n_policies): a car with
+ * an entry outside gets no action written (rx_policy_act_bank's skip rule). */
+typedef struct rx_match_io {
+  int32_t obs_dim;       /* the handle's D: 15 or 19 */
+  int32_t precision;     /* RX_PREC_* */
+  const float* params;   /* bank base [n_policies][params_stride] */
+  const float* log_std;  /* [n_policies][2] */
+  const float* eps;      /* [n_steps][N*A][2] N(0,1) noise; all zeros = deterministic mu */
+  float* actions;        /* [n_steps][N][A][2] out */
+  float* logp_sink;      /* [N*A] scratch */
+  float* value_sink;     /* [N*A] scratch */
+  double* acc;           /* [N][A][RX_EVAL_W] */
+  uint8_t* active;       /* [N] */
+  int32_t* n_active;     /* [1] */
+  int32_t n_policies;
+  int32_t reserved0;
+  int64_t params_stride; /* floats, >= rx_ppo_n_params(obs_dim) */
+  const int32_t* seat;   /* [N][A] device memory: the policy driving car q of env e, env order */
+} rx_match_io;
+int rx_match_steps(rx_env* h, const rx_io* io, const rx_match_io* m, int32_t n_steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1480,6 +1480,56 @@ int rx_eval_steps(rx_env* h, const rx_io* io, const rx_eval_io* ev, int32_t n_st
   return RX_OK;
 }
 
+// ABI v25, additive: rx_eval_steps' policy mode with a seating -- per step one bank launch
+// (car q of env e on policy seat[e][q]), rx_step, k_eval_acc.
+int rx_match_steps(rx_env* h, const rx_io* io, const rx_match_io* m, int32_t n_steps, void* stream) {
+  if (!h) return fail(RX_EINVAL, "rx_match_steps: null handle");
+  if (!io) return fail(RX_EINVAL, "rx_match_steps: null io");
+  if (!m) return fail(RX_EINVAL, "rx_match_steps: null match io");
+  if (n_steps <= 0) return fail(RX_EINVAL, "rx_match_steps: n_steps=%d must be > 0", n_steps);
+  if (m->obs_dim != 15 && m->obs_dim != 19)
+    return fail(RX_EINVAL, "rx_match_steps: obs_dim=%d has no policy kernel (15 or 19)", m->obs_dim);
+  if (m->precision != RX_PREC_FP32 && m->precision != RX_PREC_BF16)
+    return fail(RX_EINVAL, "rx_match_steps: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", m->precision);
+  if (m->n_policies <= 0) return fail(RX_EINVAL, "rx_match_steps: n_policies=%d must be > 0", m->n_policies);
+  if (m->params_stride < rx_ppo_n_params(m->obs_dim))
+    return fail(RX_EINVAL, "rx_match_steps: params_stride=%lld < the %d parameters of obs_dim %d",
+                (long long)m->params_stride, rx_ppo_n_params(m->obs_dim), m->obs_dim);
+  if (!m->params || !m->log_std || !m->eps || !m->seat || !m->actions || !m->logp_sink || !m->value_sink)
+    return fail(RX_EINVAL, "rx_match_steps: null %s",
+                !m->params ? "params" : !m->log_std ? "log_std" : !m->eps ? "eps" : !m->seat ? "seat"
+                : !m->actions ? "actions" : !m->logp_sink ? "logp_sink" : "value_sink");
+  if (!m->acc || !m->active || !m->n_active)
+    return fail(RX_EINVAL, "rx_match_steps: null %s", !m->acc ? "acc" : !m->active ? "active" : "n_active");
+  if (!io->obs || !io->reward64 || !io->info || !io->done_f32)
+    return fail(RX_EINVAL, "rx_match_steps: null io->%s",
+                !io->obs ? "obs" : !io->reward64 ? "reward64" : !io->info ? "info" : "done_f32");
+  // from here on the handle is read
+  if (m->obs_dim != h->D) return fail(RX_EINVAL, "rx_match_steps: obs_dim %d != the handle's %d", m->obs_dim, h->D);
+  if (h->n_tracks <= 0 || !h->assigned || !h->bound)
+    return fail(RX_ESTATE, "rx_match_steps: needs an assigned, bound handle");
+  const int64_t N = h->cfg.n_envs, A = h->cfg.n_agents, NA = N * A;
+  if (A != 1 && A != 2) return fail(RX_EINVAL, "rx_match_steps: n_agents=%d (1 or 2)", (int)A);
+  hipStream_t hs = (hipStream_t)stream;
+  int rc;
+  for (int32_t t = 0; t < n_steps; ++t) {
+    float* act = m->actions + (int64_t)t * NA * 2;
+    const rx_policy_bank_io b{{m->obs_dim, NA, io->obs, m->eps + (int64_t)t * NA * 2, m->params, m->log_std, act,
+                               m->logp_sink, m->value_sink, 0, 0, m->precision, nullptr, 0},
+                              m->n_policies, (int32_t)A, m->params_stride, m->seat};
+    if ((rc = rx_launch_policy_act_bank(&b, hs)) != 0)
+      return fail(RX_EHIP, "rx_match_steps: policy launch failed: %s", hipGetErrorString((hipError_t)rc));
+    rx_io s = *io;
+    s.actions = act;
+    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
+    // after launch(): its re-sort (if any) has been enqueued, so perm and the working rows agree
+    if ((rc = rx_launch_eval_acc((int)N, (int)A, h->perm[0].p, &h->work, io, m->acc, m->active, m->n_active,
+                                 hs)) != 0)
+      return fail(RX_EHIP, "k_eval_acc launch failed: %s", hipGetErrorString((hipError_t)rc));
+  }
+  return RX_OK;
+}
+
 static int gae(int32_t T, int32_t N, const float* r, const float* v, const float* d, const float* nv, const float* nd,
                double gamma, double lam, float* adv, float* ret, int scan, void* stream) {
   if (T <= 0 || N <= 0) return fail(RX_EINVAL, "rx_gae: T=%d N=%d must be > 0", T, N);
@@ -1867,6 +1917,36 @@ int rx_policy_act(const rx_policy_io* io, void* stream) {
     return fail(RX_EINVAL, "rx_policy_act: null buffer");
   const int rc = rx_launch_policy_act(io, (hipStream_t)stream);
   if (rc != 0) return fail(RX_EHIP, "policy launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+// ABI v25, additive: rx_policy_act with per-row parameters from a bank (k_policy_act_bank)
+int rx_policy_act_bank(const rx_policy_bank_io* b, void* stream) {
+  if (!b) return fail(RX_EINVAL, "rx_policy_act_bank: io is null");
+  const rx_policy_io* io = &b->io;
+  if (io->obs_dim != 15 && io->obs_dim != 19)
+    return fail(RX_EINVAL, "rx_policy_act_bank: obs_dim=%d (15 or 19)", io->obs_dim);
+  if (io->n <= 0) return fail(RX_EINVAL, "rx_policy_act_bank: n=%lld must be > 0", (long long)io->n);
+  if (b->n_policies <= 0) return fail(RX_EINVAL, "rx_policy_act_bank: n_policies=%d must be > 0", b->n_policies);
+  if (b->params_stride < rx_ppo_n_params(io->obs_dim))
+    return fail(RX_EINVAL, "rx_policy_act_bank: params_stride=%lld < the %d parameters of obs_dim %d",
+                (long long)b->params_stride, rx_ppo_n_params(io->obs_dim), io->obs_dim);
+  if (io->precision != RX_PREC_FP32 && io->precision != RX_PREC_BF16)
+    return fail(RX_EINVAL, "rx_policy_act_bank: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", io->precision);
+  if ((b->tile_cars != 1 && b->tile_cars != 2) || (b->tile_cars == 2 && (io->n & 1)))
+    return fail(RX_EINVAL, "rx_policy_act_bank: tile_cars=%d (1, or 2 with an even n; n=%lld)", b->tile_cars,
+                (long long)io->n);
+  if ((io->obs_stride != 0 && io->obs_stride < io->obs_dim) || (io->act_stride != 0 && io->act_stride < 2) ||
+      (io->act2_stride != 0 && io->act2_stride < 2))
+    return fail(RX_EINVAL, "rx_policy_act_bank: row strides overlap (obs_stride %lld, act_stride %lld, act2_stride %lld)",
+                (long long)io->obs_stride, (long long)io->act_stride, (long long)io->act2_stride);
+  if (!io->obs || !io->eps || !io->params || !io->log_std || !io->actions || !io->logprobs || !io->values ||
+      !b->policy_of_row)
+    return fail(RX_EINVAL, "rx_policy_act_bank: null %s",
+                !io->obs ? "obs" : !io->eps ? "eps" : !io->params ? "params" : !io->log_std ? "log_std"
+                : !io->actions ? "actions" : !io->logprobs ? "logprobs" : !io->values ? "values" : "policy_of_row");
+  const int rc = rx_launch_policy_act_bank(b, (hipStream_t)stream);
+  if (rc != 0) return fail(RX_EHIP, "bank policy launch failed: %s", hipGetErrorString((hipError_t)rc));
   return RX_OK;
 }
 

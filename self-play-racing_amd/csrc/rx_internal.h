@@ -308,6 +308,8 @@ extern "C" size_t rx_ppo_partial_floats(int obs_dim, int mb);
 extern "C" int rx_ppo_n_wg(int mb);
 // frag: NULL, or (bf16) the rollout's fragment image from rx_launch_policy_frag
 extern "C" int rx_launch_policy_act(const rx_policy_io* io, hipStream_t s, const void* frag = nullptr);
+// rx_policy_act with per-row parameters from a bank (k_policy_act_bank); b is validated by the caller
+extern "C" int rx_launch_policy_act_bank(const rx_policy_bank_io* b, hipStream_t s);
 extern "C" size_t rx_policy_frag_bytes();
 extern "C" int rx_launch_policy_frag(int obs_dim, const float* params, void* img, hipStream_t s);
 // both self-play policies of a rollout step in one launch (obs_dim 19; k_selfplay_act)

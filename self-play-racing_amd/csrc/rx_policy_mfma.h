@@ -255,4 +255,78 @@ __device__ __forceinline__ void policy_rows(const rx_policy_io& io, const float*
   }
 }
 
+// policy_rows with per-row parameters (rx_policy_act_bank): row r is evaluated
+// with policy id[r] of a bank, parameters io.params + id * params_stride, log-std
+// io.log_std + 2 id.  A batch row is one MFMA column, and a column's fmaf chain
+// (and, fp32 head, the xor-16 / xor-32 shuffles among the row's own 4 lanes) reads
+// only that row's inputs and the weights: so the tile is evaluated once per
+// DISTINCT id among its rows, with that policy's weights for all 16 columns, and
+// only the rows of that id store -- each gets exactly policy_rows' bits for its
+// policy.  The loop is wave-uniform (the id is read from the first lane of the
+// remaining-row ballot, all 64 lanes run every MFMA; the MFMA ignores EXEC, so
+// the masking is at the stores, as `live` is in policy_rows).  A tile with one id
+// runs the body once: policy_rows' cost plus the id load and two ballots.
+// cars = 2: the rows are [n / 2][2] (env, car) and tile t is car t & 1 of envs
+// 16 (t >> 1) .. + 15.  An id outside [0, n_policies) is never selected: nothing
+// is read (no parameters, no observation) or written for that row.
+struct policy_bank {
+  const int32_t* __restrict__ ids;  // [n] policy of each row
+  int64_t stride;                   // floats between two policies' parameters
+  int32_t n_policies;
+  int32_t cars;                     // 1 or 2
+};
+template <int D, int PREC, int NET>
+__device__ __forceinline__ void policy_rows_bank(const rx_policy_io& io, const policy_bank& bk, int64_t tile) {
+  using L = Lay<D>;
+  constexpr int XN = Geo<D>::template XN<PREC>, NOUT = NET ? 1 : kNA;
+  const int lane = threadIdx.x & 63, l15 = lane & 15, q = lane >> 4;
+  const int64_t nenv = bk.cars == 2 ? io.n >> 1 : io.n;
+  const int64_t eb = bk.cars == 2 ? tile >> 1 : tile;
+  if (eb * 16 >= nenv) return;
+  const int64_t env = eb * 16 + l15;
+  const int64_t row = bk.cars == 2 ? 2 * env + (tile & 1) : env;
+  int id = env < nenv ? bk.ids[row] : -1;
+  if (id >= bk.n_policies) id = -1;
+  const bool live = id >= 0;
+  const int64_t os = io.obs_stride > 0 ? io.obs_stride : D, as = io.act_stride > 0 ? io.act_stride : kNA;
+  float x[XN];
+#pragma unroll
+  for (int s = 0; s < XN; ++s) {
+    const int d = Geo<D>::template d_of<PREC>(s, q);
+    x[s] = (live && d < D) ? io.obs[row * os + d] : 0.0f;
+  }
+  unsigned long long todo = __ballot(live);
+  while (todo) {
+    const int p = __builtin_amdgcn_readlane(id, __ffsll(todo) - 1);  // wave-uniform: in [0, n_policies)
+    const float* __restrict__ P = io.params + (int64_t)p * bk.stride;
+    const bool mine = id == p;
+    todo &= ~__ballot(mine);
+    f4 H1[4], H2[4], y;
+    if constexpr (NET == 0) {
+      const WGlobal w{P + L::aW1, P + L::ab1, P + L::aW2, P + L::ab2, P + L::aW3, P + L::ab3, D};
+      mlp_forward<D, NOUT, PREC>(w, x, H1, H2, y, l15, q);
+      if (q == 0 && mine) {
+        const float* ls = io.log_std + 2 * p;
+        float logp = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kNA; ++j) {
+          const float mu = rx_policy::tanh_fast(y[j] + P[L::ab3 + j]);
+          const float scale = expf(ls[j]);
+          const float var = scale * scale;
+          const float smp = io.eps[row * kNA + j] * scale + mu;  // mul_(std).add_(mu): two roundings
+          const float a = fminf(fmaxf(smp, -1.0f), 1.0f);
+          io.actions[row * as + j] = a;
+          if (io.actions2) io.actions2[row * (io.act2_stride > 0 ? io.act2_stride : kNA) + j] = a;
+          logp += normal_logp(a - mu, var, logf(scale));
+        }
+        if (io.logprobs) io.logprobs[row] = logp;
+      }
+    } else {
+      const WGlobal w{P + L::cW1, P + L::cb1, P + L::cW2, P + L::cb2, P + L::cW3, P + L::cb3, D};
+      mlp_forward<D, NOUT, PREC>(w, x, H1, H2, y, l15, q);
+      if (q == 0 && mine) io.values[row] = y[0] + P[L::cb3];
+    }
+  }
+}
+
 }  // namespace

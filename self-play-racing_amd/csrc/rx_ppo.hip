@@ -122,6 +122,20 @@ __global__ __launch_bounds__(kT) void k_policy_act(rx_policy_io io, const float*
   policy_rows<D, PREC, FRAG>(io, P, critic, rb, frag);
 }
 
+// rx_policy_act_bank: k_policy_act's launch shape (a wave per 16-row tile and
+// trunk, a workgroup's 4 waves on one trunk), each row on the bank member
+// policy_of_row names (policy_rows_bank, rx_policy_mfma.h).  bf16 converts per
+// use (k_policy_act's FRAG = false path: the same bf16 values as the fragment
+// image); the parameters are plain global loads from the L2-resident bank.
+template <int D, int PREC>
+__global__ __launch_bounds__(kT) void k_policy_act_bank(rx_policy_io io, policy_bank bk) {
+  const int64_t tile = (int64_t)(blockIdx.x >> 1) * (kT / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (blockIdx.x & 1)
+    policy_rows_bank<D, PREC, 1>(io, bk, tile);
+  else
+    policy_rows_bank<D, PREC, 0>(io, bk, tile);
+}
+
 // The bf16 rollout's fragment image (rx_rollout_steps, once per rollout: the
 // parameters do not change inside it): per trunk (workgroup y) F1 | F2 | F3 in
 // mlp_forward_frag's layout, the same bf16 conversions mlp_forward's bf16 path
@@ -1413,6 +1427,27 @@ extern "C" int rx_launch_policy_act(const rx_policy_io* io, hipStream_t s, const
       hipLaunchKernelGGL((k_policy_act<19, kBF16>), dim3(n_wg), dim3(kT), 0, s, *io, io->params, fr);
     else
       hipLaunchKernelGGL((k_policy_act<19, kF32>), dim3(n_wg), dim3(kT), 0, s, *io, io->params, fr);
+  }
+  return (int)hipGetLastError();
+}
+
+extern "C" int rx_launch_policy_act_bank(const rx_policy_bank_io* b, hipStream_t s) {
+  // tiles: 16 rows (tile_cars 1) or one car of 16 envs (tile_cars 2); 4 tiles of one trunk per workgroup
+  const int64_t cars = b->tile_cars == 2 ? 2 : 1;
+  const int64_t tiles = cars * ((b->io.n / cars + 15) / 16);
+  const int n_wg = (int)(2 * ((tiles + 3) / 4));
+  const policy_bank bk{b->policy_of_row, b->params_stride, b->n_policies, (int32_t)cars};
+  const bool bf = b->io.precision == kBF16;
+  if (b->io.obs_dim == 15) {
+    if (bf)
+      hipLaunchKernelGGL((k_policy_act_bank<15, kBF16>), dim3(n_wg), dim3(kT), 0, s, b->io, bk);
+    else
+      hipLaunchKernelGGL((k_policy_act_bank<15, kF32>), dim3(n_wg), dim3(kT), 0, s, b->io, bk);
+  } else {
+    if (bf)
+      hipLaunchKernelGGL((k_policy_act_bank<19, kBF16>), dim3(n_wg), dim3(kT), 0, s, b->io, bk);
+    else
+      hipLaunchKernelGGL((k_policy_act_bank<19, kF32>), dim3(n_wg), dim3(kT), 0, s, b->io, bk);
   }
   return (int)hipGetLastError();
 }

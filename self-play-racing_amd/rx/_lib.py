@@ -34,7 +34,7 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_ppo_adv_workspace_doubles", "rx_ppo_adv_stats_ws", "rx_profile_waves", "rx_ray_waves", "rx_ray_tasks", "rx_set_start_draws",
            "rx_rollout_steps", "rx_selfplay_rollout_steps", "rx_steps", "rx_build_tracks", "rx_build_tracks_host",
            "rx_eval_steps", "rx_raster_static", "rx_raster_static_host", "rx_raster_trail", "rx_raster_trail_host",
-           "rx_raster_frame", "rx_raster_frame_host")
+           "rx_raster_frame", "rx_raster_frame_host", "rx_policy_act_bank", "rx_match_steps")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -125,6 +125,20 @@ class RxEvalIO(ctypes.Structure):
     _fields_ = [("obs_dim", ctypes.c_int32), ("precision", ctypes.c_int32)] + \
                [(k, _P) for k in ("params", "log_std", "eps", "actions", "logp_sink", "value_sink", "acc", "active",
                                   "n_active")]
+
+
+# league play (ABI v25, additive): the policy-bank forward and the match loop (include/rx.h)
+class RxPolicyBankIO(ctypes.Structure):
+    _fields_ = [("io", RxPolicyIO), ("n_policies", ctypes.c_int32), ("tile_cars", ctypes.c_int32),
+                ("params_stride", ctypes.c_int64), ("policy_of_row", _P)]
+
+
+class RxMatchIO(ctypes.Structure):
+    _fields_ = [("obs_dim", ctypes.c_int32), ("precision", ctypes.c_int32)] + \
+               [(k, _P) for k in ("params", "log_std", "eps", "actions", "logp_sink", "value_sink", "acc", "active",
+                                  "n_active")] + \
+               [("n_policies", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("params_stride", ctypes.c_int64),
+                ("seat", _P)]
 
 
 # rendering (ABI v25, additive): pixel classes / trail bits, size limits, edge record width (include/rx.h)
@@ -218,6 +232,8 @@ def load(build_if_missing=True):
     L.rx_build_tracks.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_P] * 9
     L.rx_build_tracks_host.argtypes = L.rx_build_tracks.argtypes
     L.rx_eval_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxEvalIO), ctypes.c_int32, _P]
+    L.rx_policy_act_bank.argtypes = [ctypes.POINTER(RxPolicyBankIO), _P]
+    L.rx_match_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxMatchIO), ctypes.c_int32, _P]
     for sfx in ("", "_host"):
         getattr(L, "rx_raster_static" + sfx).argtypes = [ctypes.c_int32] * 3 + [_P] * 4
         getattr(L, "rx_raster_trail" + sfx).argtypes = [ctypes.POINTER(RxRasterIO), _P]

@@ -201,6 +201,13 @@ class SelfPlayPPO(PPO):
         self._graphs_by_kind = graphs
         return super().collect_rollout(*bufs)
 
+    def league_bank(self):
+        """The learner and its pool as an rx.league.PolicyBank (row 0 = the current
+        agent, then the snapshots, oldest first) for League.play.  Training never
+        calls it."""
+        from .league import PolicyBank
+        return PolicyBank([self.agent] + self.opponent_pool)
+
     def load_checkpoint(self, path):
         ck = torch.load(path, map_location=self.device, weights_only=True)
         self.agent.load_state_dict(ck["agent_state_dict"])
