@@ -136,8 +136,11 @@ struct rx_env {
   bool split = true;
   // rx_steps' carried schedule: two snapshots of what the ray waves read -- the stepped
   // pose ([3][N] x, y, angle) and the sorted task ids -- written by a step's KIN part
-  DevBuf<double> snap_pose[2];
-  DevBuf<int32_t> snap_tasks[2];
+  // (the paired schedule: rings of RX_PAIR_RING, and a shadow of the obs rows for the older
+  // of two ray steps that would write the same rows -- stride-0 outputs)
+  DevBuf<double> snap_pose[RX_PAIR_RING];
+  DevBuf<int32_t> snap_tasks[RX_PAIR_RING];
+  DevBuf<float> obs_shadow;
   // rx_profile: per recorded launch, [RX_PROF_SLOTS] wave start + [RX_PROF_SLOTS] wave end stamps
   bool prof = false;
   DevBuf<unsigned long long> prof_buf;
@@ -450,10 +453,11 @@ int rx_destroy(rx_env* h) {
                   &h->slot_n, &h->tasks})
     b->release();
   h->cs_scratch.release();
-  for (int b = 0; b < 2; ++b) {
+  for (int b = 0; b < RX_PAIR_RING; ++b) {
     h->snap_pose[b].release();
     h->snap_tasks[b].release();
   }
+  h->obs_shadow.release();
   h->policy_frag.release();
   h->pos_slot.release();
   h->prof_buf.release();
@@ -747,13 +751,17 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
     if ((rc = upload(h->cs_scratch, z.data(), z.size()))) return rc;
   }
   // the carried schedule's snapshots (single-agent; here, not in rx_steps: it may run under capture)
-  for (int b = 0; b < 2 && RX_STEPS_CARRY && A == 1; ++b) {
+  for (int b = 0; b < (RX_STEPS_PAIR ? RX_PAIR_RING : 2) && RX_STEPS_CARRY && A == 1; ++b) {
     std::vector<double> z(3 * (size_t)N, 0.0);
     if ((rc = upload(h->snap_pose[b], z.data(), z.size()))) return rc;
     if (h->cfg.ray_order == 2) {
       std::vector<int32_t> t0((size_t)N * R, 0);
       if ((rc = upload(h->snap_tasks[b], t0.data(), t0.size()))) return rc;
     }
+  }
+  if (RX_STEPS_CARRY && RX_STEPS_PAIR && A == 1) {
+    std::vector<float> z((size_t)N * h->D, 0.0f);
+    if ((rc = upload(h->obs_shadow, z.data(), z.size()))) return rc;
   }
   if ((rc = upload(h->dyn_waves, dyn.data(), dyn.size()))) return rc;
   if ((rc = upload(h->ray_waves, ray.data(), ray.size()))) return rc;
@@ -1283,6 +1291,158 @@ static int steps_carry(rx_env* h, const rx_io* io, const rx_io_strides& st, int3
   return RX_OK;
 }
 
+// the paired schedule needs the snapshot rings and the shadow obs rows of rx_assign
+static bool steps_paired(const rx_env* h) {
+  if (!RX_STEPS_PAIR || !h->obs_shadow.p) return false;
+  for (int b = 0; b < RX_PAIR_RING; ++b)
+    if (!h->snap_pose[b].p || (h->cfg.ray_order == 2 && !h->lane_tracks && !h->snap_tasks[b].p)) return false;
+  return true;
+}
+
+// The carried schedule with two steps per launch (DESIGN.md §3 "The paired launch").  The ray
+// waves of step k read only what KIN k stored (the pose snapshot, the task row) and nothing
+// of a later step reads what they write, so once KIN k's launch has completed they can be
+// cast in ANY later launch of the window.  `pend` is the queue of such steps: KIN done, rays
+// not yet cast (never more than two).  Every launch casts all of them and its REWARD
+// workgroups advance up to two steps D_k = (REWARD k, KIN k + 1), which refills the queue:
+//   k_kin1(0) [D0 D1 | rays 0] [D2 D3 | rays 1 2] [D4 D5 | rays 3 4] [D6 | rays 5 6]
+//   k_step2(7, keys) sort k_kin1(8) ...
+// A step whose re-sort is due, and the call's last step, has no KIN behind its REWARD: the
+// plain k_step2 when its own rays are all that is pending, else the paired kernel with one
+// KIN-less sub-step (which writes the keys).  So the queue is empty before every sort (the
+// sort moves rows, and the rays name positions) and at the end of the call.  Pose snapshots
+// are a ring of RX_PAIR_RING by the step's index in the call, task rows a ring by the
+// call's sorts: a launch stores steps k + 1, k + 2 and reads k - 1, k.  Two ray steps that
+// would write the same obs rows (stride 0): the older one writes the handle's shadow rows,
+// so the caller's rows end with the newest step's.  The task buffer of the handle and the
+// bookkeeping are kept as steps_carry keeps them.
+static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32_t K, hipStream_t s) {
+  const size_t N = (size_t)h->cfg.n_envs;
+  rx_kargs a{};
+  make_kargs(h, io, RX_MODE_STEP, nullptr, a);
+  int32_t* const tasks_main = a.tasks_out;  // nullptr: this schedule sorts no ray tasks
+  const int32_t* ray_tasks = h->tasks.p;    // the row the last sort wrote: the handle's before the call's first
+  int tb = 0, rc;
+  bool main_behind = false;  // the last sort left the handle's task buffer out
+  struct ray_step {
+    int32_t k;
+    const int32_t* tasks;
+  } pend[2];
+  int n_pend = 0;
+  struct kin_out {
+    double* snap;
+    int32_t* tasks_out;
+    int32_t* tasks_snap;
+  };
+  // the KIN part of step k (the ray-task sort's turn as in launch()); reads_main: in a launch
+  // one of whose ray steps reads the handle's task buffer.  Step k joins the queue.
+  auto kin_args = [&](int32_t k, bool reads_main) {
+    kin_out o{h->snap_pose[k % RX_PAIR_RING].p, nullptr, nullptr};
+    if (tasks_main) {
+      if (h->tasks_stale || (h->task_calls % (uint64_t)h->task_sort) == 0) {
+        h->tasks_stale = false;
+        main_behind = reads_main;
+        int32_t* const row = h->snap_tasks[tb].p;
+        if (main_behind)
+          o.tasks_out = row;
+        else
+          o.tasks_out = tasks_main, o.tasks_snap = row;
+        ray_tasks = row;
+        tb = (tb + 1) % RX_PAIR_RING;
+      }
+      ++h->task_calls;
+    }
+    pend[n_pend++] = ray_step{k, ray_tasks};
+    return o;
+  };
+  auto kin1 = [&](int32_t k) {
+    const kin_out o = kin_args(k, false);
+    a.io = io_at(io, st, k);
+    a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
+    a.snap_x = o.snap, a.snap_y = o.snap + N, a.snap_angle = o.snap + 2 * N;
+    a.tasks_out = o.tasks_out, a.tasks_snap = o.tasks_snap;
+    return rx_launch_split(&a, 1, RX_SPLIT_KIN, s);
+  };
+  // the pending ray steps into p (emptying the queue); do they read the handle's task buffer?
+  auto take_rays = [&](rx_pair& p) {
+    bool reads_main = false;
+    p.n_rays = n_pend;
+    for (int r = 0; r < n_pend; ++r) {
+      p.ray_pose[r] = h->snap_pose[pend[r].k % RX_PAIR_RING].p;
+      p.ray_tasks[r] = pend[r].tasks;
+      p.ray_obs[r] = io_at(io, st, pend[r].k).obs;
+      reads_main = reads_main || (tasks_main && pend[r].tasks == tasks_main);
+    }
+    if (n_pend == 2 && p.ray_obs[0] == p.ray_obs[1]) p.ray_obs[0] = h->obs_shadow.p;
+    n_pend = 0;
+    return reads_main;
+  };
+  // (dyn_calls counts only while the re-sort is on, as launch() counts it)
+  const bool sorting_envs = h->cfg.sort_interval > 0 && h->sort_on;
+  auto resort_at = [&](int32_t ahead) {
+    return sorting_envs && ((h->dyn_calls + ahead) % h->cfg.sort_interval) == 0;
+  };
+  if ((rc = kin1(0)) != 0) return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
+  for (int32_t k = 0; k < K;) {
+    const bool resort = resort_at(0);
+    rx_pair p{};
+    p.n_envs = (int64_t)N;
+    a.io = p.io[0] = io_at(io, st, k);
+    a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
+    a.snap_x = a.snap_y = a.snap_angle = nullptr;
+    a.tasks_out = nullptr, a.tasks_snap = nullptr;
+    if (!resort && k + 1 < K) {  // D_k, and D_k+1 unless step k + 1 has no KIN behind it
+      const int32_t d = (k + 2 < K && !resort_at(1)) ? 2 : 1;
+      const bool reads_main = take_rays(p);
+      p.n_sub = d;
+      for (int32_t j = 0; j < d; ++j) {
+        const kin_out o = kin_args(k + j + 1, reads_main);
+        p.io[j + 1] = io_at(io, st, k + j + 1);
+        p.kin[j] = 1;
+        p.snap[j] = o.snap, p.tasks_out[j] = o.tasks_out, p.tasks_snap[j] = o.tasks_snap;
+      }
+      if ((rc = rx_launch_step2_pair(&a, &p, s)) != 0)
+        return fail(RX_EHIP, "k_step2_pair launch failed: %s", hipGetErrorString((hipError_t)rc));
+      if (sorting_envs) h->dyn_calls += (uint64_t)d;
+      k += d;
+      continue;
+    }
+    if (sorting_envs) ++h->dyn_calls;
+    if (resort) {  // as launch(): the REWARD half writes the keys and counts the bins
+      if (h->sort_hist_done) RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sort_bins * sizeof(uint32_t), s));
+      a.sort_keys = h->keys_in.p;
+      a.sort_hist = h->sort_hist.p;
+      a.sort_off = h->keys_off.p;
+    }
+    if (n_pend == 1) {  // only its own rays are pending: the plain k_step2
+      a.ray_x = h->snap_pose[pend[0].k % RX_PAIR_RING].p;
+      a.ray_y = a.ray_x + N;
+      a.ray_angle = a.ray_x + 2 * N;
+      a.tasks = pend[0].tasks;
+      n_pend = 0;
+      if ((rc = rx_launch_split(&a, 1, RX_SPLIT_REWARD_RAYS, s)) != 0)
+        return fail(RX_EHIP, "k_step2 launch failed: %s", hipGetErrorString((hipError_t)rc));
+    } else {
+      take_rays(p);
+      p.n_sub = 1;
+      if ((rc = rx_launch_step2_pair(&a, &p, s)) != 0)
+        return fail(RX_EHIP, "k_step2_pair launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    if (resort) {
+      h->sort_hist_done = false;
+      h->tasks_stale = true;  // the re-sort moves envs between blocks
+      rx_state work = h->work, tmp = h->work_tmp;
+      if ((rc = rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, 1, h->sort_hist.p, h->sort_cursor.p,
+                             h->sort_bins, h->perm[0].p, h->perm[1].p, &work, &tmp, s, 1)) != 0)
+        return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    if (++k < K && (rc = kin1(k)) != 0)
+      return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
+  }
+  if (main_behind) h->tasks_stale = true;
+  return RX_OK;
+}
+
 int rx_steps(rx_env* h, const rx_io* io, int32_t n_steps, const rx_io_strides* strides, void* stream) {
   if (!h) return fail(RX_EINVAL, "null handle");
   if (!io) return fail(RX_EINVAL, "io is null");
@@ -1292,7 +1452,9 @@ int rx_steps(rx_env* h, const rx_io* io, int32_t n_steps, const rx_io_strides* s
     return fail(RX_ESTATE, "rx_steps needs rx_upload_tracks, rx_assign and rx_bind_state");
   const rx_io_strides st = strides ? *strides : rx_io_strides{};
   int rc;
-  if (steps_carried(h, io) && n_steps > 0) return steps_carry(h, io, st, n_steps, (hipStream_t)stream);
+  if (steps_carried(h, io) && n_steps > 0)
+    return steps_paired(h) ? steps_pair(h, io, st, n_steps, (hipStream_t)stream)
+                           : steps_carry(h, io, st, n_steps, (hipStream_t)stream);
   for (int32_t k = 0; k < n_steps; ++k) {
     const rx_io o = io_at(io, st, k);
     if ((rc = launch(h, &o, RX_MODE_STEP, nullptr, stream)) != 0) return rc;

@@ -214,7 +214,38 @@ struct rx_kargs {
 #define RX_STEPS_CARRY 1
 #endif
 
+// rx_steps' paired schedule (DESIGN.md §3 "The paired launch"): a launch's REWARD workgroups
+// advance up to two steps (REWARD k, KIN k + 1, REWARD k + 1, KIN k + 2) and its ray
+// workgroups cast the rays of up to two EARLIER-stepped steps, whose KIN parts completed in
+// a previous launch -- half the launch boundaries, half the drains.  0 = the carried schedule.
+#ifndef RX_STEPS_PAIR
+#define RX_STEPS_PAIR 1
+#endif
+#define RX_PAIR_RING 4  // pose / task-row snapshots: a launch writes at most two and reads at most two others
+
+// What one k_step2_pair launch runs beside rx_kargs (whose io, io_next, ray_*, snap_*, tasks,
+// tasks_out and tasks_snap it ignores).
+struct rx_pair {
+  int32_t n_sub;   // REWARD sub-steps of the launch (1 or 2); the sort keys go with the last one
+  int32_t n_rays;  // ray steps of the launch (1 or 2), oldest first
+  // sub-step j: REWARD on io[j]'s rows, then -- with kin[j] -- KIN on io[j + 1]'s
+  rx_io io[3];
+  int32_t kin[2];
+  double* snap[2];         // KIN j's pose snapshot: x, y at + N, angle at + 2 N
+  int32_t* tasks_out[2];   // KIN j's ray-task sort (nullptr = not this step), and its second copy
+  int32_t* tasks_snap[2];
+  // ray step s: the pose snapshot and the task row its KIN stored, and the obs rows it writes
+  const double* ray_pose[2];
+  const int32_t* ray_tasks[2];
+  float* ray_obs[2];
+  int64_t n_envs;
+};
+
 extern "C" int rx_launch_step(const rx_kargs* a, int n_agents, int phases, hipStream_t s);
+// k_step2_pair (single-agent, one lane per env).  Refuses (hipErrorInvalidValue) a launch that
+// writes a snapshot or sorts into a row that one of its own ray steps reads, and two ray
+// steps that write the same obs rows.
+extern "C" int rx_launch_step2_pair(const rx_kargs* a, const rx_pair* p, hipStream_t s);
 // split step (STEP mode, next-step / no autoreset): k_kin1 / k_kin2, then k_step2<A>
 #define RX_SPLIT_KIN 0
 #define RX_SPLIT_REWARD 1

@@ -2288,6 +2288,124 @@ __global__ __launch_bounds__(64, LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW) void k_s
   step2_body<1, 1, LPR, LV, true>(a, n_rw);
 }
 
+// PAIR (k_step2_pair, rx_steps' paired schedule; DESIGN.md §3 "The paired launch"): the
+// carrying launch over two steps.  REWARD workgroup b runs a program of one or two
+// sub-steps -- REWARD k, KIN k + 1, REWARD k + 1, KIN k + 2 -- as a LOOP over the same
+// dyn1_env / sort_block_tasks calls (one copy of the code), every part reading what the
+// part before stored for its own lane.  The ray workgroups cast n_rays earlier steps, the
+// older one first: ray workgroup r is record r % n_ray_waves of step r / n_ray_waves, on
+// that step's pose snapshot, task row and obs rows.  Their KIN parts ran in an EARLIER
+// launch, so no wave of this launch waits on another.
+// Scheduling knobs, same-session A/B at 65,536 envs (profiles/steps_pair/): issue priority of
+// the REWARD workgroups 0 / 1 / 2 / 3 = 998 / 1,047 / 1,045 / 1,045 M env-steps/s (parent
+// 1,012 M); the two steps' ray records interleaved in octets 1,080 M against 1,085 M for the
+// older step's records first.
+#ifndef RX_PAIR_PRIO
+#define RX_PAIR_PRIO 1
+#endif
+#ifndef RX_PAIR_INTERLEAVE
+#define RX_PAIR_INTERLEAVE 0
+#endif
+__device__ __forceinline__ rx_io pair_io(const rx_io& x, const rx_io& y, bool second) {
+  rx_io o = x;  // ep_stats and counters are the call's, not the step's
+  o.actions = second ? y.actions : x.actions;
+  o.obs = second ? y.obs : x.obs;
+  o.reward = second ? y.reward : x.reward;
+  o.reward64 = second ? y.reward64 : x.reward64;
+  o.terminated = second ? y.terminated : x.terminated;
+  o.truncated = second ? y.truncated : x.truncated;
+  o.done_f32 = second ? y.done_f32 : x.done_f32;
+  o.info = second ? y.info : x.info;
+  o.ep_done = second ? y.ep_done : x.ep_done;
+  return o;
+}
+
+// The launch's one kernel argument.  The REWARD workgroups re-read it through a pointer to
+// the kernarg segment that passes through an empty asm in every iteration of the sub-step
+// loop: the loads of the ~100 argument words are then the iteration's own (as in
+// k_step2_carry) instead of being hoisted out of the loop and held -- or spilled -- across
+// it (64-VGPR cap: 317 SGPRs and 63 VGPRs spilled, 168 B/lane of scratch, without this).
+struct rx_pair_args {
+  rx_kargs a;
+  rx_pair p;
+  int32_t n_rw;
+};
+
+template <int LPR, bool LV>
+__device__ __forceinline__ void step2_pair_body(const rx_pair_args& ka) {
+  const int b = uniform((int)blockIdx.x);
+  if (b < ka.n_rw) {
+#if RX_PAIR_PRIO > 0
+    // issue priority over the ray waves sharing the SIMD: two links of REWARD + KIN are a
+    // latency chain as long as the launch (profiles/steps_pair/ab_pair_prio.jsonl)
+    __builtin_amdgcn_s_setprio(RX_PAIR_PRIO);
+#endif
+    // as k_kin1: 64 sector counters and the staging row (dynamic LDS, only when sorting)
+    extern __shared__ int32_t task_lds[];
+    int32_t* cnt = task_lds;
+    int32_t* stage = cnt + kTaskSectors;
+    typedef const __attribute__((address_space(4))) rx_pair_args* rx_kap;
+    rx_kap kp = (rx_kap)__builtin_amdgcn_kernarg_segment_ptr();  // the one argument: offset 0
+    const int n_sub = uniform(ka.p.n_sub);
+#pragma nounroll
+    for (int j = 0; j < n_sub; ++j) {
+      int bj = b;  // (likewise the block index: no per-lane state address is carried around the loop)
+      __asm__ volatile("" : "+s"(kp), "+s"(bj));
+      const rx_pair_args& k = *(const rx_pair_args*)kp;
+      const rx_pair& pp = k.p;
+      const bool second = j != 0;
+      rx_kargs an = k.a;
+      an.io = pair_io(pp.io[0], pp.io[1], second);
+      if (j + 1 < n_sub) an.sort_keys = nullptr;  // the keys are the launch's last REWARD's
+      an.snap_x = nullptr, an.tasks_out = nullptr, an.tasks_snap = nullptr;
+      double ang[1], ep[3] = {0.0, 0.0, 0.0};
+      int e = -1;
+      dyn1_env<1, RX_PART_REWARD, LV>(an, bj, ang, e, ep);
+      add_episode_stats(an, ep);
+      const bool kin = (second ? pp.kin[1] : pp.kin[0]) != 0;
+      if (kin && bj < an.n_dyn_waves) {  // (n_rw pads the REWARD workgroups to a multiple of 8)
+        an.io = pair_io(pp.io[1], pp.io[2], second);
+        an.sort_keys = nullptr;
+        an.snap_x = second ? pp.snap[1] : pp.snap[0];
+        an.snap_y = an.snap_x + pp.n_envs;
+        an.snap_angle = an.snap_x + 2 * pp.n_envs;
+        an.tasks_out = second ? pp.tasks_out[1] : pp.tasks_out[0];
+        an.tasks_snap = second ? pp.tasks_snap[1] : pp.tasks_snap[0];
+        const bool sorting = an.tasks_out != nullptr;
+        if (sorting) cnt[threadIdx.x & 63] = 0;
+        double ang1[1], ep1[3];
+        int p1 = -1;
+        dyn1_env<1, RX_PART_KIN, LV>(an, bj, ang1, p1, ep1);
+        if (sorting) sort_block_tasks<1>(an, uniform(an.dyn_waves[bj].perm_start), p1, ang1, cnt, stage);
+      }
+    }
+  } else {
+    const rx_kargs& a = ka.a;
+    const rx_pair& pp = ka.p;
+    const int r = b - ka.n_rw;
+#if RX_PAIR_INTERLEAVE
+    // the two steps' records interleaved in octets (an octet keeps its XCDs): record-major
+    const bool newer = pp.n_rays == 2 && ((r >> 3) & 1);
+    const int rec = pp.n_rays == 2 ? (((r >> 4) << 3) | (r & 7)) : r;
+#else
+    const bool newer = r >= a.n_ray_waves;  // (n_rays <= 2): the older step's records first
+    const int rec = newer ? r - a.n_ray_waves : r;
+#endif
+    rx_kargs ar = a;
+    ar.ray_x = newer ? pp.ray_pose[1] : pp.ray_pose[0];
+    ar.ray_y = ar.ray_x + pp.n_envs;
+    ar.ray_angle = ar.ray_x + 2 * pp.n_envs;
+    ar.tasks = newer ? pp.ray_tasks[1] : pp.ray_tasks[0];
+    ar.io.obs = newer ? pp.ray_obs[1] : pp.ray_obs[0];
+    rays_dispatch<1, LPR, LV, LPR == 4>(ar, rec);
+  }
+}
+
+template <int LPR, bool LV = false>
+__global__ __launch_bounds__(64, LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW) void k_step2_pair(rx_pair_args ka) {
+  step2_pair_body<LPR, LV>(ka);
+}
+
 // ============================================================ k_rollout
 // PPO.collect_rollout (agent/ppo.py:97-132) for few single-agent envs as ONE
 // persistent launch (rx_rollout): workgroup b = the env of dynamics wave b
@@ -2719,6 +2837,41 @@ extern "C" int rx_launch_step2_carry(const rx_kargs* a, hipStream_t s) {
     hipLaunchKernelGGL((k_step2_carry<2>), grid, dim3(64), lds, s, *a, n_rw);
   else
     hipLaunchKernelGGL((k_step2_carry<1>), grid, dim3(64), lds, s, *a, n_rw);
+  return (int)hipGetLastError();
+}
+
+// The paired k_step2: n_rw REWARD workgroups, then n_rays copies of the ray table (n_ray_waves
+// is a multiple of 8, so both copies keep the group -> XCD placement); the sort's LDS as the
+// carrying launch sizes it.  Checked here, on the host: no KIN part of the launch stores a
+// pose snapshot or sorts a task row that one of the launch's ray steps reads, and two ray
+// steps never write the same obs rows.
+extern "C" int rx_launch_step2_pair(const rx_kargs* a, const rx_pair* p, hipStream_t s) {
+  if (p->n_sub < 1 || p->n_sub > 2 || p->n_rays < 1 || p->n_rays > 2) return (int)hipErrorInvalidValue;
+  if (p->n_rays == 2 && p->ray_obs[0] == p->ray_obs[1]) return (int)hipErrorInvalidValue;
+  bool sorting = false;
+  for (int j = 0; j < p->n_sub; ++j) {
+    if (!p->kin[j]) continue;
+    if (j + 1 == p->n_sub && a->sort_keys) return (int)hipErrorInvalidValue;  // the sort comes before the next KIN
+    sorting = sorting || p->tasks_out[j];
+    for (int r = 0; r < p->n_rays; ++r) {
+      if (p->snap[j] == p->ray_pose[r]) return (int)hipErrorInvalidValue;
+      if (p->tasks_out[j] && (p->tasks_out[j] == p->ray_tasks[r] || p->tasks_snap[j] == p->ray_tasks[r]))
+        return (int)hipErrorInvalidValue;
+    }
+  }
+  if (p->n_sub == 2 && !p->kin[0]) return (int)hipErrorInvalidValue;  // REWARD k + 1 needs KIN k + 1
+  const int n_rw = (a->n_dyn_waves + 7) / 8 * 8;
+  const dim3 grid(n_rw + p->n_rays * a->n_ray_waves);
+  const size_t lds = sorting ? (size_t)(kTaskSectors + 64 * a->n_sensors) * sizeof(int32_t) : 0;
+  const rx_pair_args ka{*a, *p, n_rw};
+  if (a->lane_tracks)
+    hipLaunchKernelGGL((k_step2_pair<1, true>), grid, dim3(64), lds, s, ka);
+  else if (a->ray_lpr == 4)
+    hipLaunchKernelGGL((k_step2_pair<4>), grid, dim3(64), lds, s, ka);
+  else if (a->ray_lpr == 2)
+    hipLaunchKernelGGL((k_step2_pair<2>), grid, dim3(64), lds, s, ka);
+  else
+    hipLaunchKernelGGL((k_step2_pair<1>), grid, dim3(64), lds, s, ka);
   return (int)hipGetLastError();
 }
 

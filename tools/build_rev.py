@@ -39,12 +39,16 @@ def main():
     for f in _build.SOURCES + _build.HEADERS:
         open(os.path.join(csrc, f), "wb").write(read(f"self-play-racing_amd/csrc/{f}"))
     open(os.path.join(inc, "rx.h"), "wb").write(read("include/rx.h"))
+    os.makedirs(_build.LIBDIR, exist_ok=True)
     out = os.path.join(_build.LIBDIR, f"librx_{name}.so")
     flags = [x for x in _build.FLAGS if not x.startswith("-I")] + ["-I" + csrc, "-I" + inc] + extra
     objs = []
     for src in _build.SOURCES:
         obj = os.path.join(tmp, os.path.splitext(src)[0] + ".o")
-        subprocess.check_call([_build.hipcc()] + flags + ["-c", os.path.join(csrc, src), "-o", obj])
+        f = flags
+        if src in _build.HOST_ONLY:  # plain C++, as _build.build compiles it
+            f = [x for x in flags if not x.startswith("--offload-arch")] + ["-x", "c++"]
+        subprocess.check_call([_build.hipcc()] + f + ["-c", os.path.join(csrc, src), "-o", obj])
         objs.append(obj)
     subprocess.check_call([_build.hipcc(), f"--offload-arch={_build.ARCH}", "-shared", "-fPIC", "-o", out] + objs)
     print(out)
