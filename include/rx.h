@@ -834,6 +834,77 @@ typedef struct rx_match_io {
 } rx_match_io;
 int rx_match_steps(rx_env* h, const rx_io* io, const rx_match_io* m, int32_t n_steps, void* stream);
 
+/* ABI v25, additive: league TRAINING -- every env of a self-play rollout races
+ * its own opponent from a bank of frozen snapshots, drawn and tallied on the
+ * device (agent/self_play_ppo.py:40-50 draws ONE opponent per update on the host;
+ * rx.league_train).  The arithmetic lives in csrc/rx_league.h, shared by the
+ * kernels (csrc/rx_league.hip) and the *_host twins; DESIGN.md §4.
+ *
+ * Slots 0 .. n_live - 1 of the bank are live.  tally[k] = (games, learner wins,
+ * opponent wins) against slot k.
+ *
+ * rx_league_weights: tallies -> sampling table (one wave, a lane per slot; all
+ * float64, every operation separately rounded, sums in slot order):
+ *   p_k    = (w + 0.5 * (g - w - l) + prior) / (g + 2 * prior)
+ *   f_k    = (1 - p_k) multiplied `power` times into 1.0     (power 0: uniform)
+ *   F      = f_0 + f_1 + ...;  prob_k = (1 - mix) * (f_k / F) + mix / n_live
+ *            (F == 0: prob_k = 1 / n_live)
+ *   cdf_k  = cdf_{k-1} + prob_k;  cdf_k = 1.0 for n_live - 1 <= k < n_slots.
+ *
+ * rx_league_draw over n envs.  With `done` (float [n]): every env e with
+ * done[e] != 0 is first tallied with k = opp_id[e] from the RX_INFO_PLACEMENT
+ * column of `info` (f64 [n][2][RX_INFO_W], the terminal step's rx_io.info):
+ * tally[k][0] += 1, tally[k][1] += (car `agent`'s placement == 1), tally[k][2] +=
+ * (the other car's placement == 1), as int64 atomic adds (a k outside
+ * [0, n_slots) is not counted), and then redrawn; every other env is left alone.
+ * With done == NULL every env is redrawn and nothing is tallied (info is unused).
+ * The draw:
+ *   h = splitmix64(seed ^ splitmix64(((uint64)draw_count[e] << 32) ^ (uint64)e))
+ *   u = (double)(h >> 11) * 2^-53;  opp_id[e] = the smallest k with u < cdf_k
+ *   draw_count[e] += 1
+ * cdf is 1.0 from n_live - 1 on, so an id is always a live slot and the draw needs
+ * no n_live: a captured graph stays valid while the pool fills.
+ *
+ * All pointers are DEVICE pointers; the *_host twins take the same arguments as
+ * HOST pointers, ignore `stream`, make no HIP call and give the same bits.
+ *
+ * rx_league_rollout_steps: rx_selfplay_rollout_steps' contract and outputs with a
+ * per-env opponent (sp->opp_params, opp_log_std and opp_precision are ignored):
+ * per step t ONE policy launch (k_league_act, csrc/rx_ppo.hip: the learner's actor
+ * and critic as in k_selfplay_act, the opponent's actor through the bank forward
+ * with env e on member opp_id[e]), rx_step, then rx_league_draw's tally and redraw
+ * of that step's done row and io->info, so step t + 1 sees the new ids: done by
+ * step t + 1's opponent waves before they read the ids, and by one launch after
+ * the last step.  io->info is required (io->reward64 is not read).
+ * With every id = k the outputs equal rx_selfplay_rollout_steps' with bank member
+ * k as the opponent bit for bit.
+ *
+ * Checked before any HIP call (RX_EINVAL, the message names the field): null
+ * pointers, n_slots outside 1..64, n_live outside 1..n_slots, power outside 0..4,
+ * mix outside [0, 1] or NaN, prior <= 0 or NaN, agent not 0 or 1, n <= 0, the
+ * precisions, params_stride < rx_ppo_n_params(19), a handle that is not an
+ * assigned, bound two-car handle with obs_dim 19. */
+typedef struct rx_league_io {
+  int32_t n_slots;        /* bank capacity, 1..64 */
+  int32_t agent;          /* the learner's car, 0 or 1 */
+  const float* params;    /* bank [n_slots][params_stride], rx_policy_act layout (rollout only) */
+  const float* log_std;   /* [n_slots][2] (rollout only) */
+  int64_t params_stride;  /* floats, >= rx_ppo_n_params(19) (rollout only) */
+  int32_t* opp_id;        /* [N] */
+  int32_t* draw_count;    /* [N] */
+  int64_t* tally;         /* [n_slots][3] */
+  double* cdf;            /* [n_slots] */
+  uint64_t seed;
+  int32_t opp_precision;  /* RX_PREC_* of the opponents' forward (rollout only) */
+} rx_league_io;
+int rx_league_weights(const rx_league_io* lg, int32_t n_live, int32_t power, double mix, double prior, void* stream);
+int rx_league_weights_host(const rx_league_io* lg, int32_t n_live, int32_t power, double mix, double prior,
+                           void* stream);
+int rx_league_draw(const rx_league_io* lg, int64_t n, const float* done, const double* info, void* stream);
+int rx_league_draw_host(const rx_league_io* lg, int64_t n, const float* done, const double* info, void* stream);
+int rx_league_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
+                            const rx_league_io* lg, int32_t precision, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

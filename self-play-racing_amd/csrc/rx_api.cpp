@@ -2112,4 +2112,140 @@ int rx_policy_act_bank(const rx_policy_bank_io* b, void* stream) {
   return RX_OK;
 }
 
+// ABI v25, additive: league training (csrc/rx_league.h).  The checks of the three entry
+// points and their host twins, before any HIP call; what: 0 = weights, 1 = draw, 2 = rollout.
+static int league_args(const char* fn, const rx_league_io* lg, int what) {
+  if (!lg) return fail(RX_EINVAL, "%s: null league io", fn);
+  if (lg->n_slots < 1 || lg->n_slots > 64) return fail(RX_EINVAL, "%s: n_slots=%d outside 1..64", fn, lg->n_slots);
+  if (!lg->tally || !lg->cdf) return fail(RX_EINVAL, "%s: null %s", fn, !lg->tally ? "tally" : "cdf");
+  if (what == 0) return RX_OK;
+  if (lg->agent != 0 && lg->agent != 1) return fail(RX_EINVAL, "%s: agent=%d must be 0 or 1", fn, lg->agent);
+  if (!lg->opp_id || !lg->draw_count)
+    return fail(RX_EINVAL, "%s: null %s", fn, !lg->opp_id ? "opp_id" : "draw_count");
+  if (what == 1) return RX_OK;
+  if (!lg->params || !lg->log_std) return fail(RX_EINVAL, "%s: null %s", fn, !lg->params ? "params" : "log_std");
+  if (lg->params_stride < rx_ppo_n_params(19))
+    return fail(RX_EINVAL, "%s: params_stride=%lld < the %d parameters of obs_dim 19", fn,
+                (long long)lg->params_stride, rx_ppo_n_params(19));
+  if (lg->opp_precision != RX_PREC_FP32 && lg->opp_precision != RX_PREC_BF16)
+    return fail(RX_EINVAL, "%s: opp_precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", fn, lg->opp_precision);
+  return RX_OK;
+}
+
+static int league_weights_args(const char* fn, const rx_league_io* lg, int32_t n_live, int32_t power, double mix,
+                               double prior) {
+  const int rc = league_args(fn, lg, 0);
+  if (rc) return rc;
+  if (n_live < 1 || n_live > lg->n_slots)
+    return fail(RX_EINVAL, "%s: n_live=%d outside 1..n_slots=%d", fn, n_live, lg->n_slots);
+  if (power < 0 || power > 4) return fail(RX_EINVAL, "%s: power=%d outside 0..4", fn, power);
+  if (!(mix >= 0.0 && mix <= 1.0)) return fail(RX_EINVAL, "%s: mix=%g outside [0, 1]", fn, mix);
+  if (!(prior > 0.0)) return fail(RX_EINVAL, "%s: prior=%g must be > 0", fn, prior);
+  return RX_OK;
+}
+
+static int league_draw_args(const char* fn, const rx_league_io* lg, int64_t n, const float* done, const double* info) {
+  const int rc = league_args(fn, lg, 1);
+  if (rc) return rc;
+  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
+  if (done && !info) return fail(RX_EINVAL, "%s: null info (required with done)", fn);
+  return RX_OK;
+}
+
+int rx_league_weights(const rx_league_io* lg, int32_t n_live, int32_t power, double mix, double prior, void* stream) {
+  int rc = league_weights_args("rx_league_weights", lg, n_live, power, mix, prior);
+  if (rc) return rc;
+  if ((rc = rx_launch_league_weights(lg, n_live, power, mix, prior, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_league_weights: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_league_weights_host(const rx_league_io* lg, int32_t n_live, int32_t power, double mix, double prior,
+                           void* /*stream*/) {
+  const int rc = league_weights_args("rx_league_weights_host", lg, n_live, power, mix, prior);
+  if (rc) return rc;
+  rx_host_league_weights(lg, n_live, power, mix, prior);
+  return RX_OK;
+}
+
+int rx_league_draw(const rx_league_io* lg, int64_t n, const float* done, const double* info, void* stream) {
+  int rc = league_draw_args("rx_league_draw", lg, n, done, info);
+  if (rc) return rc;
+  if ((rc = rx_launch_league_draw(lg, n, done, info, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_league_draw: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_league_draw_host(const rx_league_io* lg, int64_t n, const float* done, const double* info, void* /*stream*/) {
+  const int rc = league_draw_args("rx_league_draw_host", lg, n, done, info);
+  if (rc) return rc;
+  rx_host_league_draw(lg, n, done, info);
+  return RX_OK;
+}
+
+// rx_selfplay_rollout_steps with a per-env opponent.  Per step: k_league_act, rx_step.  The tally and
+// redraw of step t's done flags is folded into step t + 1's k_league_act (its opponent waves are the
+// only readers of the ids), so one k_league_draw per rollout remains, for the last step.
+// RX_LEAGUE_FOLD=0 (an A/B build, tools/bench_league_train.py) launches k_league_draw after every
+// step instead: the same bits, one more launch per step.
+#ifndef RX_LEAGUE_FOLD
+#define RX_LEAGUE_FOLD 1
+#endif
+int rx_league_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
+                            const rx_league_io* lg, int32_t precision, void* stream) {
+  const char* fn = "rx_league_rollout_steps";
+  // the league io first: its refusals need no handle (tests/test_league_train_cpu.py)
+  int rc = league_args(fn, lg, 2);
+  if (rc) return rc;
+  if (precision != RX_PREC_FP32 && precision != RX_PREC_BF16)
+    return fail(RX_EINVAL, "%s: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", fn, precision);
+  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
+  if (!io || !r || !sp) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : !r ? "rollout io" : "self-play io");
+  if (!h->assigned || !h->bound || h->cfg.n_agents != 2 || h->D != 19)
+    return fail(RX_EINVAL, "%s: the handle must be an assigned, bound two-car handle with obs_dim 19", fn);
+  if (r->T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, r->T);
+  if (r->obs_dim != h->D) return fail(RX_EINVAL, "%s: obs_dim %d != the handle's %d", fn, r->obs_dim, h->D);
+  if (sp->agent != lg->agent)
+    return fail(RX_EINVAL, "%s: agent %d of the self-play io != agent %d of the league io", fn, sp->agent, lg->agent);
+  if (!r->params || !r->log_std || !r->eps || !r->obs || !r->actions || !r->logprobs || !r->values || !r->rewards ||
+      !r->dones || !r->next_obs || !r->next_done)
+    return fail(RX_EINVAL, "%s: null rollout buffer", fn);
+  if (!sp->opp_eps || !sp->env_actions || !sp->env_obs || !sp->env_reward || !sp->sink)
+    return fail(RX_EINVAL, "%s: null %s", fn,
+                !sp->opp_eps ? "opp_eps" : !sp->env_actions ? "env_actions" : !sp->env_obs ? "env_obs"
+                : !sp->env_reward ? "env_reward" : "sink");
+  if (!io->info) return fail(RX_EINVAL, "%s: null io->info (the tally reads the terminal step's placement)", fn);
+  const int64_t N = h->cfg.n_envs, D = h->D;
+  const int q = lg->agent, o = 1 - q;
+  hipStream_t hs = (hipStream_t)stream;
+  for (int32_t t = 0; t < r->T; ++t) {
+    const bool last = t + 1 == r->T;
+    // rx_selfplay_rollout_steps' two policy ios; the opponent's params / log_std are the bank bases
+    const rx_policy_io opp{(int32_t)D, N, sp->env_obs + o * D, sp->opp_eps + t * N * 2, lg->params, lg->log_std,
+                           sp->env_actions + 2 * o, nullptr, sp->sink, 2 * D, 4, lg->opp_precision, nullptr, 0};
+    const rx_policy_io pio{(int32_t)D, N, t == 0 ? r->obs : sp->env_obs + q * D, r->eps + t * N * 2, r->params,
+                           r->log_std, r->actions + t * N * 2, r->logprobs + t * N, r->values + t * N,
+                           t == 0 ? 0 : 2 * D, 0, precision, sp->env_actions + 2 * q, 4};
+    // io->info still holds step t - 1's rows here: rx_step writes it after this launch
+    const bool fold = RX_LEAGUE_FOLD && t > 0;
+    rc = rx_launch_league_act(&pio, &opp, lg, fold ? r->dones + t * N : nullptr, fold ? io->info : nullptr,
+                              t == 0 ? nullptr : r->obs + t * N * D, sp->env_reward,
+                              t == 0 ? nullptr : r->rewards + (t - 1) * N, hs);
+    if (rc) return fail(RX_EHIP, "league policy launch failed: %s", hipGetErrorString((hipError_t)rc));
+    rx_io s = *io;
+    s.actions = sp->env_actions;
+    s.obs = sp->env_obs;
+    s.reward = sp->env_reward;
+    s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;
+    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
+    // the envs that ended: count the result against their opponent, draw the next one
+    if ((last || !RX_LEAGUE_FOLD) && (rc = rx_launch_league_draw(lg, N, s.done_f32, io->info, hs)) != 0)
+      return fail(RX_EHIP, "league draw launch failed: %s", hipGetErrorString((hipError_t)rc));
+  }
+  rc = rx_launch_agent_rows((int)N, (int)D, q, sp->env_obs, sp->env_reward, r->next_obs, r->rewards + (r->T - 1) * N,
+                            hs);
+  if (rc) return fail(RX_EHIP, "agent-row copy launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
 }  // extern "C"

@@ -346,6 +346,21 @@ extern "C" int rx_launch_policy_frag(int obs_dim, const float* params, void* img
 // both self-play policies of a rollout step in one launch (obs_dim 19; k_selfplay_act)
 extern "C" int rx_launch_selfplay_act(const rx_policy_io* ag, const rx_policy_io* op, float* obs_out,
                                       const float* rew_src, float* rew_out, int agent, hipStream_t s);
+// a league rollout step's policies in one launch (obs_dim 19; k_league_act): op's params / log_std are
+// the bank bases, env e's opponent is bank member lg->opp_id[e]; with prev_done (the previous step's done
+// flags, prev_info its info rows) the opponent waves first tally and redraw the envs that ended, as
+// rx_launch_league_draw would have
+extern "C" int rx_launch_league_act(const rx_policy_io* ag, const rx_policy_io* op, const rx_league_io* lg,
+                                    const float* prev_done, const double* prev_info, float* obs_out,
+                                    const float* rew_src, float* rew_out, hipStream_t s);
+// rx_league.hip: tallies -> sampling table; tally + redraw of the opponent ids (arguments checked by rx_api.cpp)
+extern "C" int rx_launch_league_weights(const rx_league_io* lg, int n_live, int power, double mix, double prior,
+                                        hipStream_t s);
+extern "C" int rx_launch_league_draw(const rx_league_io* lg, int64_t n, const float* done, const double* info,
+                                     hipStream_t s);
+// rx_league_host.cpp: the same two as host loops (plain C++, no HIP call)
+extern "C" void rx_host_league_weights(const rx_league_io* lg, int n_live, int power, double mix, double prior);
+extern "C" void rx_host_league_draw(const rx_league_io* lg, int64_t n, const float* done, const double* info);
 extern "C" int rx_launch_adv_stats(const rx_ppo_batch* b, int n_mb, float* stats, double* moments, hipStream_t s);
 extern "C" int rx_adv_chunks(int mb);
 extern "C" int rx_launch_adv_stats_ws(const rx_ppo_batch* b, int n_mb, double* ws, float* stats, double* moments,

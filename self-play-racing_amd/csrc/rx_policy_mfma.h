@@ -275,8 +275,13 @@ struct policy_bank {
   int32_t n_policies;
   int32_t cars;                     // 1 or 2
 };
-template <int D, int PREC, int NET>
-__device__ __forceinline__ void policy_rows_bank(const rx_policy_io& io, const policy_bank& bk, int64_t tile) {
+// policy_rows_bank_ids: the same with the lane's id handed in (`id_in`: the id of
+// the row of lane l15, the same in all four lanes of a row; read only where the
+// row exists) instead of loaded from bk.ids -- k_league_act's opponent waves
+// redraw ids in registers before they use them.
+template <int D, int PREC, int NET, bool LOAD_IDS = false>
+__device__ __forceinline__ void policy_rows_bank_ids(const rx_policy_io& io, const policy_bank& bk, int64_t tile,
+                                                     int id_in) {
   using L = Lay<D>;
   constexpr int XN = Geo<D>::template XN<PREC>, NOUT = NET ? 1 : kNA;
   const int lane = threadIdx.x & 63, l15 = lane & 15, q = lane >> 4;
@@ -285,7 +290,7 @@ __device__ __forceinline__ void policy_rows_bank(const rx_policy_io& io, const p
   if (eb * 16 >= nenv) return;
   const int64_t env = eb * 16 + l15;
   const int64_t row = bk.cars == 2 ? 2 * env + (tile & 1) : env;
-  int id = env < nenv ? bk.ids[row] : -1;
+  int id = env < nenv ? (LOAD_IDS ? bk.ids[row] : id_in) : -1;
   if (id >= bk.n_policies) id = -1;
   const bool live = id >= 0;
   const int64_t os = io.obs_stride > 0 ? io.obs_stride : D, as = io.act_stride > 0 ? io.act_stride : kNA;
@@ -327,6 +332,10 @@ __device__ __forceinline__ void policy_rows_bank(const rx_policy_io& io, const p
       if (q == 0 && mine) io.values[row] = y[0] + P[L::cb3];
     }
   }
+}
+template <int D, int PREC, int NET>
+__device__ __forceinline__ void policy_rows_bank(const rx_policy_io& io, const policy_bank& bk, int64_t tile) {
+  policy_rows_bank_ids<D, PREC, NET, true>(io, bk, tile, -1);
 }
 
 }  // namespace

@@ -30,6 +30,7 @@
 
 #include "rx.h"
 #include "rx_internal.h"
+#include "rx_league.h"
 #include "rx_policy.h"
 
 // Profiling build only (-DRX_PPO_STAMPS, tools/ppo_stamps.py): per-wave
@@ -183,6 +184,19 @@ struct selfplay_copy {
   float* rew_out;        // [N]
   int32_t agent;
 };
+// the agent's critic waves' copy of the 16 observation rows they read and of the
+// previous step's agent rewards (k_selfplay_act, k_league_act)
+template <int D>
+__device__ __forceinline__ void agent_rows_copy(const rx_policy_io& ag, const selfplay_copy& cp, int64_t rb) {
+  const int lane = threadIdx.x & 63;
+  const int64_t os = ag.obs_stride > 0 ? ag.obs_stride : D;
+  const int64_t r0 = rb * 16, nr = min((int64_t)16, ag.n - r0);
+  for (int i = lane; i < nr * D; i += 64) {
+    const int64_t r = r0 + i / D;
+    cp.obs_out[r * D + i % D] = ag.obs[r * os + i % D];
+  }
+  if (lane < nr) cp.rew_out[r0 + lane] = cp.rew_src[(r0 + lane) * 2 + cp.agent];
+}
 template <int D, int PA, int PO>
 __global__ __launch_bounds__(kT) void k_selfplay_act(rx_policy_io ag, rx_policy_io op, selfplay_copy cp) {
   const int kind = (int)blockIdx.x % 3;
@@ -193,14 +207,61 @@ __global__ __launch_bounds__(kT) void k_selfplay_act(rx_policy_io ag, rx_policy_
   }
   policy_rows<D, PA>(ag, ag.params, kind == 1, rb);
   if (kind != 1 || !cp.obs_out || rb * 16 >= ag.n) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t os = ag.obs_stride > 0 ? ag.obs_stride : D;
-  const int64_t r0 = rb * 16, nr = min((int64_t)16, ag.n - r0);
-  for (int i = lane; i < nr * D; i += 64) {
-    const int64_t r = r0 + i / D;
-    cp.obs_out[r * D + i % D] = ag.obs[r * os + i % D];
+  agent_rows_copy<D>(ag, cp, rb);
+}
+
+// One league rollout step's policies in ONE launch (rx_league_rollout_steps):
+// k_selfplay_act with a per-env opponent.  Kinds 0 and 1 are the learner's actor
+// and critic exactly as above (the obs / reward copy included); kind 2 is the
+// opponent's actor trunk through policy_rows_bank: env e's opponent car is driven
+// by bank member opp_id[e], a 16-env tile evaluated once per distinct id in it.
+// The kind-2 wave of a tile is the only reader of its 16 ids in the rollout, so it
+// also does the PREVIOUS step's tally and redraw (rx_league.h; k_league_draw's
+// rules and bits) before it uses them: lane l < 16 owns env 16 rb + l, counts the
+// ended episode against the old id, draws and stores the new one, and the four
+// lanes of a row take the id from that lane's register -- no id is re-read from
+// memory after its store.  fold.done == nullptr (the first step): ids as they are.
+struct league_fold {
+  const float* done;    // [N] the previous step's done flags, or nullptr
+  const double* info;   // [N][2][RX_INFO_W] the previous step's info rows
+  int32_t* opp_id;      // [N]
+  int32_t* draw_count;  // [N]
+  int64_t* tally;       // [n_slots][3]
+  const double* cdf;    // [n_slots]
+  uint64_t seed;
+};
+template <int D, int PA, int PO>
+__global__ __launch_bounds__(kT) void k_league_act(rx_policy_io ag, rx_policy_io op, policy_bank bk, league_fold fd,
+                                                   selfplay_copy cp) {
+  const int kind = (int)blockIdx.x % 3;
+  const int64_t rb = (int64_t)(blockIdx.x / 3) * (kT / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (kind == 2) {
+    if (rb * 16 >= op.n) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t e = rb * 16 + lane;
+    int id = -1;
+    if (lane < 16 && e < op.n) {
+      id = fd.opp_id[e];
+      if (fd.done && fd.done[e] != 0.0f) {
+        if (id >= 0 && id < bk.n_policies) {
+          unsigned long long* row = reinterpret_cast<unsigned long long*>(fd.tally + (size_t)id * RX_LEAGUE_TALLY_W);
+          const int out = rx_lg_outcome(fd.info + (size_t)e * 2 * RX_INFO_W, cp.agent);
+          atomicAdd(row, 1ull);
+          if (out & 1) atomicAdd(row + 1, 1ull);
+          if (out & 2) atomicAdd(row + 2, 1ull);
+        }
+        const uint32_t count = (uint32_t)fd.draw_count[e];
+        id = rx_lg_pick(fd.cdf, bk.n_policies, rx_lg_uniform(fd.seed, count, (uint32_t)e));
+        fd.opp_id[e] = id;
+        fd.draw_count[e] = (int32_t)(count + 1u);
+      }
+    }
+    policy_rows_bank_ids<D, PO, 0>(op, bk, rb, __shfl(id, lane & 15, 64));
+    return;
   }
-  if (lane < nr) cp.rew_out[r0 + lane] = cp.rew_src[(r0 + lane) * 2 + cp.agent];
+  policy_rows<D, PA>(ag, ag.params, kind == 1, rb);
+  if (kind != 1 || !cp.obs_out || rb * 16 >= ag.n) return;
+  agent_rows_copy<D>(ag, cp, rb);
 }
 
 // LDS words of k_ppo_grad's workgroup
@@ -1404,6 +1465,26 @@ extern "C" int rx_launch_selfplay_act(const rx_policy_io* ag, const rx_policy_io
     hipLaunchKernelGGL((k_selfplay_act<19, kF32, kBF16>), dim3(n_wg), dim3(kT), 0, s, *ag, *op, cp);
   else
     hipLaunchKernelGGL((k_selfplay_act<19, kF32, kF32>), dim3(n_wg), dim3(kT), 0, s, *ag, *op, cp);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rx_launch_league_act(const rx_policy_io* ag, const rx_policy_io* op, const rx_league_io* lg,
+                                    const float* prev_done, const double* prev_info, float* obs_out,
+                                    const float* rew_src, float* rew_out, hipStream_t s) {
+  const int64_t blocks16 = (ag->n + 15) / 16;
+  const int n_wg = (int)(3 * ((blocks16 + 3) / 4));
+  const selfplay_copy cp{obs_out, rew_src, rew_out, lg->agent};
+  const policy_bank bk{nullptr, lg->params_stride, lg->n_slots, 1};  // the ids come through `fd`
+  const league_fold fd{prev_done, prev_info, lg->opp_id, lg->draw_count, lg->tally, lg->cdf, lg->seed};
+  const bool ba = ag->precision == kBF16, bo = op->precision == kBF16;
+  if (ba && bo)
+    hipLaunchKernelGGL((k_league_act<19, kBF16, kBF16>), dim3(n_wg), dim3(kT), 0, s, *ag, *op, bk, fd, cp);
+  else if (ba)
+    hipLaunchKernelGGL((k_league_act<19, kBF16, kF32>), dim3(n_wg), dim3(kT), 0, s, *ag, *op, bk, fd, cp);
+  else if (bo)
+    hipLaunchKernelGGL((k_league_act<19, kF32, kBF16>), dim3(n_wg), dim3(kT), 0, s, *ag, *op, bk, fd, cp);
+  else
+    hipLaunchKernelGGL((k_league_act<19, kF32, kF32>), dim3(n_wg), dim3(kT), 0, s, *ag, *op, bk, fd, cp);
   return (int)hipGetLastError();
 }
 

@@ -34,7 +34,9 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_ppo_adv_workspace_doubles", "rx_ppo_adv_stats_ws", "rx_profile_waves", "rx_ray_waves", "rx_ray_tasks", "rx_set_start_draws",
            "rx_rollout_steps", "rx_selfplay_rollout_steps", "rx_steps", "rx_build_tracks", "rx_build_tracks_host",
            "rx_eval_steps", "rx_raster_static", "rx_raster_static_host", "rx_raster_trail", "rx_raster_trail_host",
-           "rx_raster_frame", "rx_raster_frame_host", "rx_policy_act_bank", "rx_match_steps")
+           "rx_raster_frame", "rx_raster_frame_host", "rx_policy_act_bank", "rx_match_steps",
+           "rx_league_weights", "rx_league_weights_host", "rx_league_draw", "rx_league_draw_host",
+           "rx_league_rollout_steps")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -141,6 +143,16 @@ class RxMatchIO(ctypes.Structure):
                 ("seat", _P)]
 
 
+# league training (ABI v25, additive): per-env opponents drawn and tallied on the device (include/rx.h)
+RX_LEAGUE_MAX_SLOTS, RX_LEAGUE_MAX_POWER, RX_LEAGUE_TALLY_W = 64, 4, 3
+
+
+class RxLeagueIO(ctypes.Structure):
+    _fields_ = [("n_slots", ctypes.c_int32), ("agent", ctypes.c_int32), ("params", _P), ("log_std", _P),
+                ("params_stride", ctypes.c_int64), ("opp_id", _P), ("draw_count", _P), ("tally", _P), ("cdf", _P),
+                ("seed", ctypes.c_uint64), ("opp_precision", ctypes.c_int32)]
+
+
 # rendering (ABI v25, additive): pixel classes / trail bits, size limits, edge record width (include/rx.h)
 RX_PX_BACKGROUND, RX_PX_TRACK, RX_PX_BORDER, RX_PX_START, RX_PX_TRAIL0, RX_PX_TRAIL1 = 0, 1, 2, 3, 0x10, 0x20
 RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX, RX_RASTER_EDGE_W = 16, 2048, 6
@@ -234,7 +246,12 @@ def load(build_if_missing=True):
     L.rx_eval_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxEvalIO), ctypes.c_int32, _P]
     L.rx_policy_act_bank.argtypes = [ctypes.POINTER(RxPolicyBankIO), _P]
     L.rx_match_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxMatchIO), ctypes.c_int32, _P]
+    L.rx_league_rollout_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxRolloutIO),
+                                          ctypes.POINTER(RxSelfplayIO), ctypes.POINTER(RxLeagueIO), ctypes.c_int32, _P]
     for sfx in ("", "_host"):
+        getattr(L, "rx_league_weights" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_double, ctypes.c_double, _P]
+        getattr(L, "rx_league_draw" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int64, _P, _P, _P]
         getattr(L, "rx_raster_static" + sfx).argtypes = [ctypes.c_int32] * 3 + [_P] * 4
         getattr(L, "rx_raster_trail" + sfx).argtypes = [ctypes.POINTER(RxRasterIO), _P]
         getattr(L, "rx_raster_frame" + sfx).argtypes = [ctypes.POINTER(RxRasterIO), _P]

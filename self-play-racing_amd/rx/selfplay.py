@@ -221,8 +221,16 @@ class SelfPlayPPO(PPO):
             for p in o.parameters():
                 p.requires_grad = False
             self.opponent_pool.append(o)
+        self._checkpoint_loaded(ck)
         info = ck.get("training_info", {"steps": [], "rewards": [], "opponent_pool_size": []})
         return ck["update"], ck["global_step"], info
+
+    def _checkpoint_extra(self):
+        """Further entries of save_checkpoint's dict (rx.league_train adds "league_state")."""
+        return {}
+
+    def _checkpoint_loaded(self, ck):
+        """Called by load_checkpoint with the file's dict once the pool is rebuilt."""
 
     def train_iter(self, resume_from=None):
         """agent/self_play_ppo.py:70-187 as a generator: yields (update,
@@ -302,7 +310,8 @@ class SelfPlayPPO(PPO):
             torch.save({"update": update, "global_step": global_step, "agent_state_dict": self.agent.state_dict(),
                         "optimizer_state_dict": self.optimizer.state_dict(),
                         "opponent_pool": [o.state_dict() for o in self.opponent_pool],
-                        "config": json.loads(json.dumps(self.config)), "training_info": info}, path)
+                        "config": json.loads(json.dumps(self.config)), "training_info": info,
+                        **self._checkpoint_extra()}, path)
         except OSError as e:
             print(f"Warning: could not save checkpoint: {e}")
         return path
