@@ -402,6 +402,88 @@ int rx_build_tracks_host(int32_t n_tracks, int32_t factor, const int32_t* cp_off
                          const double* width, int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta,
                          void* stream);
 
+/* ABI v25, additive: the culling tables of a track table, handle-free like the
+ * builders above, and the device-resident door into a handle.  rx_upload_tracks
+ * derives these tables from its host arrays; the entry points below derive the
+ * same tables from a table that already lives in device memory (rx_build_tracks),
+ * so it is never downloaded.  The rules live in csrc/rx_cull.h, shared by the
+ * kernel (csrc/rx_cull.hip), the host twin and rx_upload_tracks; DESIGN.md §3.
+ *
+ * Per slot k with W = wp_off[k+1] - wp_off[k] waypoints and its 2 W boundary
+ * segments (left side, then right side), G = cull_chunk, S = cull_super:
+ *   leaf boxes   per side ceil(W / G) boxes (xmin, ymin, xmax, ymax) over both end
+ *                points of G consecutive segments: 2 ceil(W / G) per slot, left first;
+ *   super boxes  (S > 0) per side the union of S consecutive leaf boxes;
+ *   wchunk boxes the box of RX_WP_CHUNK = 8 consecutive waypoints; wsuper boxes the
+ *                union of RX_WP_SUPER = 4 consecutive wchunk boxes;
+ *   *_off [n+1]  first box of each slot in the four box arrays (running sums);
+ *   slot_geo     [n][4] = centre of the box of all segment end points, a radius
+ *                r * (1 + 1e-12) + 1e-9 with r the largest hypot distance from the
+ *                centre to an end point, and l * (1 + 1e-12) + 1e-12 with l the
+ *                longest segment sqrt(v2.x * v2.x + v2.y * v2.y);
+ *   chunk_box_f, super_box_f  float [5][count][4]: block 0 the boxes in float32
+ *                rounded outward (min corner towards -inf, max corner towards +inf),
+ *                block 1 + q the same boxes as (near.x, near.y, far.x, far.y) for a
+ *                ray whose x (bit 0 of q) / y (bit 1) direction is negative;
+ *   seg_f        float [2*Wtot][4], seg rounded to nearest;
+ *   slot_hdr     [n] rows of 128 bytes: int32 wp_off[k], W, chunk_off[k],
+ *                super_off[k], wchunk_off[k], wsuper_off[k], 0, 0; then f64
+ *                slot_geo[k][0..3], meta[k][0..7].
+ * G <= 0: only seg_f and slot_hdr are written (offsets and geo in the rows are 0)
+ * and the other pointers may be null.  S == 0: no super tables (super_off,
+ * super_box and super_box_f may be null, the rows hold 0).
+ *
+ * rx_cull_table_sizes: out[4] = the leaf, super, wchunk and wsuper box counts of
+ * the whole table.  Host only, no HIP call.
+ * rx_build_cull_tables_host: every pointer is a HOST pointer; no HIP call.
+ * rx_build_cull_tables: wp_off is a HOST array; wp, seg, meta and every pointer of
+ * `out` are DEVICE pointers.  One launch (a wavefront per slot) enqueued on
+ * `stream`; the call does not wait for it.  The offset arrays are computed on the
+ * host and travel as rx_build_tracks' do (stream-ordered allocation: not
+ * capturable).  Both write the same values, with one exception: slot_geo[k][2] and
+ * its copy in the row use the platform's hypot (ocml / libm), so the device's
+ * radius agrees with the host's to 1e-13 relative and stays an upper bound of the
+ * exact one.  Zeros may differ in sign (min / max of +0.0 and -0.0).
+ * Checked before any HIP call (RX_EINVAL, the message names the track and the
+ * field): n_tracks <= 0, a null pointer, wp_off[0] != 0, W < 2, W above
+ * 64 * RX_WP_CHUNK * RX_WP_SUPER, cull_super outside 0..64, a box count above int32. */
+typedef struct rx_cull_tables {
+  int32_t* chunk_off;   /* [n+1] */
+  int32_t* super_off;   /* [n+1] */
+  int32_t* wchunk_off;  /* [n+1] */
+  int32_t* wsuper_off;  /* [n+1] */
+  double* chunk_box;    /* [leaf][4] */
+  double* super_box;    /* [super][4] */
+  double* wchunk_box;   /* [wchunk][4] */
+  double* wsuper_box;   /* [wsuper][4] */
+  double* slot_geo;     /* [n][4] */
+  float* chunk_box_f;   /* [5][leaf][4] */
+  float* super_box_f;   /* [5][super][4] */
+  float* seg_f;         /* [2*Wtot][4] */
+  void* slot_hdr;       /* [n] rows of 128 bytes */
+} rx_cull_tables;
+int rx_cull_table_sizes(int32_t n_tracks, const int32_t* wp_off, int32_t cull_chunk, int32_t cull_super,
+                        int64_t* out);
+int rx_build_cull_tables_host(int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* seg,
+                              const double* meta, int32_t cull_chunk, int32_t cull_super, const rx_cull_tables* out,
+                              void* stream);
+int rx_build_cull_tables(int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* seg,
+                         const double* meta, int32_t cull_chunk, int32_t cull_super, const rx_cull_tables* out,
+                         void* stream);
+
+/* rx_upload_tracks for a table in DEVICE memory (wp_off stays a HOST array): the
+ * same per-track checks, the handle copies what it keeps (device to device, into
+ * buffers it reuses when they are large enough: a swap to a table of the same
+ * shape keeps every address) and builds its culling tables with
+ * rx_build_cull_tables' kernel; rx_assign is required again.  The only transfer to
+ * the host is the [n][8] meta block, for the width and max_track_distance checks:
+ * a NaN meta[k][4] (rx_build_tracks' mark of a bad track) is refused with the
+ * track named.  Everything is checked before anything is written, so a refused
+ * call leaves the handle stepping on its old table.  Synchronous: waits for the
+ * device before it starts and for `stream` before it returns; not capturable. */
+int rx_upload_tracks_device(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* nrm,
+                            const double* seg, const double* meta, void* stream);
+
 /* Fused optimizer step of PPO.ppo_update (agent/ppo.py:204-207):
  * nn.utils.clip_grad_norm_(params, max_grad_norm) then torch.optim.Adam.step()
  * (the default eps=1e-5 Adam of agent/ppo.py:83, no weight decay/amsgrad),

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rx.h"
+#include "rx_cull.h"
 #include "rx_internal.h"
 #include "rx_spline.h"
 
@@ -52,8 +53,9 @@ struct DevBuf {
   }
 };
 
+// room for n elements: the buffer is kept when it is large enough (its address then stays)
 template <class T>
-int upload(DevBuf<T>& b, const T* host, size_t n) {
+int reserve(DevBuf<T>& b, size_t n) {
   if (n > b.n) {
     b.release();
     if (hipMalloc(&b.p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
@@ -62,6 +64,13 @@ int upload(DevBuf<T>& b, const T* host, size_t n) {
     }
     b.n = n;
   }
+  return RX_OK;
+}
+
+template <class T>
+int upload(DevBuf<T>& b, const T* host, size_t n) {
+  const int rc = reserve(b, n);
+  if (rc != RX_OK) return rc;
   if (n) RX_HIP(hipMemcpy(b.p, host, n * sizeof(T), hipMemcpyHostToDevice));
   return RX_OK;
 }
@@ -155,170 +164,103 @@ struct rx_env {
 };
 
 namespace {
-// Culling tables for every slot: chunks of G consecutive boundary segments
-// (per side), their end-point boxes, and per slot the bounding circle of all
-// boundary points and the longest segment (kernel margins).
-int build_headers(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* meta,
-                  const std::vector<int32_t>& off, const std::vector<int32_t>& soff, const std::vector<int32_t>& woff,
-                  const std::vector<int32_t>& wsoff, const std::vector<double>& geo);
-int build_chunks(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* seg,
-                 const double* meta) {
-  const int G = h->cfg.cull_chunk;
-  if (G <= 0) return build_headers(h, n_tracks, wp_off, meta, {}, {}, {}, {}, {});
-  const int SG = h->cfg.cull_super;  // leaves per super-chunk (0 = one level)
-  std::vector<int32_t> off(n_tracks + 1, 0), woff(n_tracks + 1, 0), soff(n_tracks + 1, 0), wsoff(n_tracks + 1, 0);
-  std::vector<double> boxes, wboxes, sboxes, wsboxes, geo(4 * (size_t)n_tracks);
-  for (int k = 0; k < n_tracks; ++k) {
-    const int W = wp_off[k + 1] - wp_off[k];
-    const int nch = (W + G - 1) / G;
-    const double* s = seg + 8 * (size_t)wp_off[k];  // 2W segments x 4
-    double xmin = 1e300, ymin = 1e300, xmax = -1e300, ymax = -1e300, L = 0.0;
-    for (int j = 0; j < 2 * W; ++j) {
-      const double* g = s + 4 * j;
-      const double ex = g[0] + g[2], ey = g[1] + g[3];
-      xmin = std::min({xmin, g[0], ex});
-      xmax = std::max({xmax, g[0], ex});
-      ymin = std::min({ymin, g[1], ey});
-      ymax = std::max({ymax, g[1], ey});
-      L = std::max(L, std::sqrt(g[2] * g[2] + g[3] * g[3]));
-    }
-    const double cx = 0.5 * (xmin + xmax), cy = 0.5 * (ymin + ymax);
-    double rad = 0.0;
-    for (int j = 0; j < 2 * W; ++j) {
-      const double* g = s + 4 * j;
-      const double ex = g[0] + g[2], ey = g[1] + g[3];
-      rad = std::max({rad, std::hypot(g[0] - cx, g[1] - cy), std::hypot(ex - cx, ey - cy)});
-    }
-    geo[4 * k + 0] = cx;
-    geo[4 * k + 1] = cy;
-    geo[4 * k + 2] = rad * (1.0 + 1e-12) + 1e-9;  // round up: the kernel needs an upper bound
-    geo[4 * k + 3] = L * (1.0 + 1e-12) + 1e-12;
-    for (int side = 0; side < 2; ++side) {
-      for (int c = 0; c < nch; ++c) {
-        double bx0 = 1e300, by0 = 1e300, bx1 = -1e300, by1 = -1e300;
-        for (int j = side * W + c * G; j < side * W + std::min(W, (c + 1) * G); ++j) {
-          const double* g = s + 4 * j;
-          const double ex = g[0] + g[2], ey = g[1] + g[3];
-          bx0 = std::min({bx0, g[0], ex});
-          bx1 = std::max({bx1, g[0], ex});
-          by0 = std::min({by0, g[1], ey});
-          by1 = std::max({by1, g[1], ey});
-        }
-        boxes.insert(boxes.end(), {bx0, by0, bx1, by1});
-      }
-    }
-    off[k + 1] = off[k] + 2 * nch;
-    if (SG > 0) {  // super-chunk boxes: union of SG consecutive leaf boxes, per side
-      const int nsup = (nch + SG - 1) / SG;
-      const double* lb = boxes.data() + 4 * (size_t)off[k];
-      for (int side = 0; side < 2; ++side)
-        for (int u = 0; u < nsup; ++u) {
-          double bx0 = 1e300, by0 = 1e300, bx1 = -1e300, by1 = -1e300;
-          for (int c = u * SG; c < std::min(nch, (u + 1) * SG); ++c) {
-            const double* b = lb + 4 * (side * nch + c);
-            bx0 = std::min(bx0, b[0]);
-            by0 = std::min(by0, b[1]);
-            bx1 = std::max(bx1, b[2]);
-            by1 = std::max(by1, b[3]);
-          }
-          sboxes.insert(sboxes.end(), {bx0, by0, bx1, by1});
-        }
-      soff[k + 1] = soff[k] + 2 * nsup;
-    }
-    // waypoint chunks (argmin culling): RX_WP_CHUNK consecutive waypoints each
-    const double* w = wp + 2 * (size_t)wp_off[k];
-    const int nwc = (W + RX_WP_CHUNK - 1) / RX_WP_CHUNK;
-    for (int c = 0; c < nwc; ++c) {
-      double bx0 = 1e300, by0 = 1e300, bx1 = -1e300, by1 = -1e300;
-      for (int i = c * RX_WP_CHUNK; i < std::min(W, (c + 1) * RX_WP_CHUNK); ++i) {
-        bx0 = std::min(bx0, w[2 * i]);
-        bx1 = std::max(bx1, w[2 * i]);
-        by0 = std::min(by0, w[2 * i + 1]);
-        by1 = std::max(by1, w[2 * i + 1]);
-      }
-      wboxes.insert(wboxes.end(), {bx0, by0, bx1, by1});
-    }
-    woff[k + 1] = woff[k] + nwc;
-    const int nws = (nwc + RX_WP_SUPER - 1) / RX_WP_SUPER;
-    for (int u = 0; u < nws; ++u) {
-      double bx0 = 1e300, by0 = 1e300, bx1 = -1e300, by1 = -1e300;
-      for (int c = u * RX_WP_SUPER; c < std::min(nwc, (u + 1) * RX_WP_SUPER); ++c) {
-        const double* b = wboxes.data() + 4 * ((size_t)woff[k] + c);
-        bx0 = std::min(bx0, b[0]);
-        by0 = std::min(by0, b[1]);
-        bx1 = std::max(bx1, b[2]);
-        by1 = std::max(by1, b[3]);
-      }
-      wsboxes.insert(wsboxes.end(), {bx0, by0, bx1, by1});
-    }
-    wsoff[k + 1] = wsoff[k] + nws;
+// ---- culling tables (csrc/rx_cull.h) ------------------------------------------
+// What the host can check of a culling-table build, and the offsets: off receives
+// wp_off and the chunk / super / wchunk / wsuper offset arrays back to back
+// (n + 1 entries each), tot the four box totals.  sizes_only: the offsets alone are
+// checked (rx_cull_table_sizes; rx_upload_tracks_device, whose arrays are the handle's).
+int cull_check(const char* fn, int32_t n, const int32_t* wp_off, const void* wp, const void* seg, const void* meta,
+               int32_t G, int32_t SG, const rx_cull_tables* out, bool sizes_only, std::vector<int32_t>* off,
+               int64_t tot[4]) {
+  if (n <= 0) return fail(RX_EINVAL, "%s: n_tracks must be > 0 (got %d)", fn, n);
+  if (!wp_off) return fail(RX_EINVAL, "%s: wp_off is null", fn);
+  if (!sizes_only) {
+    if (!wp) return fail(RX_EINVAL, "%s: wp is null", fn);
+    if (!seg) return fail(RX_EINVAL, "%s: seg is null", fn);
+    if (!meta) return fail(RX_EINVAL, "%s: meta is null", fn);
+    if (!out) return fail(RX_EINVAL, "%s: out is null", fn);
+    const struct {
+      const void* p;
+      const char* name;
+      bool need;
+    } fields[] = {{out->seg_f, "seg_f", true},
+                  {out->slot_hdr, "slot_hdr", true},
+                  {out->chunk_off, "chunk_off", G > 0},
+                  {out->wchunk_off, "wchunk_off", G > 0},
+                  {out->wsuper_off, "wsuper_off", G > 0},
+                  {out->chunk_box, "chunk_box", G > 0},
+                  {out->wchunk_box, "wchunk_box", G > 0},
+                  {out->wsuper_box, "wsuper_box", G > 0},
+                  {out->slot_geo, "slot_geo", G > 0},
+                  {out->chunk_box_f, "chunk_box_f", G > 0},
+                  {out->super_off, "super_off", G > 0 && SG > 0},
+                  {out->super_box, "super_box", G > 0 && SG > 0},
+                  {out->super_box_f, "super_box_f", G > 0 && SG > 0}};
+    for (const auto& f : fields)
+      if (f.need && !f.p) return fail(RX_EINVAL, "%s: out->%s is null", fn, f.name);
   }
-  // float32 copies rounded outward (min corner down, max corner up): each f32
-  // box contains its f64 box, so a test that keeps the f32 box keeps the f64 one
-  auto to_f32 = [](const std::vector<double>& b) {
-    std::vector<float> f(b.size());
-    for (size_t i = 0; i < b.size(); ++i) {
-      float v = (float)b[i];
-      if ((i & 3) < 2 && (double)v > b[i]) v = std::nextafter(v, -HUGE_VALF);
-      if ((i & 3) >= 2 && (double)v < b[i]) v = std::nextafter(v, HUGE_VALF);
-      f[i] = v;
+  if (SG < 0 || SG > RX_CULL_MAX_SUPER)
+    return fail(RX_EINVAL, "%s: cull_super must be 0 .. %d (got %d)", fn, RX_CULL_MAX_SUPER, SG);
+  if (wp_off[0] != 0) return fail(RX_EINVAL, "%s: wp_off[0] must be 0 (got %d)", fn, wp_off[0]);
+  const size_t n1 = (size_t)n + 1;
+  if (off) off->assign(5 * n1, 0);
+  int64_t run[4] = {0, 0, 0, 0};
+  for (int32_t k = 0; k < n; ++k) {
+    const int64_t W = (int64_t)wp_off[k + 1] - wp_off[k];
+    if (W < 2) return fail(RX_EINVAL, "%s: track %d has W = %lld waypoints (need >= 2)", fn, k, (long long)W);
+    if (W > RX_CULL_MAX_W)
+      return fail(RX_EINVAL, "%s: track %d has W = %lld waypoints (at most %d)", fn, k, (long long)W, RX_CULL_MAX_W);
+    const rx_cull_counts c = rx_cull_slot_counts((int32_t)W, G, SG);
+    const int32_t add[4] = {c.leaf, c.super, c.wchunk, c.wsuper};
+    for (int a = 0; a < 4; ++a) {
+      run[a] += add[a];
+      if (run[a] > INT32_MAX)
+        return fail(RX_EINVAL, "%s: track %d: the box count overflows the int32 offsets", fn, k);
+      if (off) (*off)[(a + 1) * n1 + k + 1] = (int32_t)run[a];
     }
-    return f;
-  };
-  // then 4 quadrant-ordered copies: block q = (near.x, near.y, far.x, far.y) for
-  // a ray direction whose x (bit 0) / y (bit 1) component is negative -- the
-  // slab planes k_rays' single-quadrant waves enter and leave through
-  auto with_quadrants = [](std::vector<float> f) {
-    const size_t n = f.size();
-    f.resize(5 * n);
-    for (int q = 0; q < 4; ++q)
-      for (size_t i = 0; i < n; i += 4) {
-        float* o = f.data() + (q + 1) * n + i;
-        const float* b = f.data() + i;
-        o[0] = (q & 1) ? b[2] : b[0];
-        o[1] = (q & 2) ? b[3] : b[1];
-        o[2] = (q & 1) ? b[0] : b[2];
-        o[3] = (q & 2) ? b[1] : b[3];
-      }
-    return f;
-  };
-  const std::vector<float> boxes_f = with_quadrants(to_f32(boxes)), sboxes_f = with_quadrants(to_f32(sboxes));
-  h->n_chunk_boxes = (int32_t)(boxes.size() / 4);
-  h->n_super_boxes = (int32_t)(sboxes.size() / 4);
-  int rc;
-  if ((rc = upload(h->chunk_box_f, boxes_f.data(), boxes_f.size()))) return rc;
-  if (SG > 0 && (rc = upload(h->super_box_f, sboxes_f.data(), sboxes_f.size()))) return rc;
-  if ((rc = upload(h->chunk_off, off.data(), off.size()))) return rc;
-  if ((rc = upload(h->chunk_box, boxes.data(), boxes.size()))) return rc;
-  if ((rc = upload(h->slot_geo, geo.data(), geo.size()))) return rc;
-  if ((rc = upload(h->wchunk_off, woff.data(), woff.size()))) return rc;
-  if ((rc = upload(h->wchunk_box, wboxes.data(), wboxes.size()))) return rc;
-  if ((rc = upload(h->wsuper_off, wsoff.data(), wsoff.size()))) return rc;
-  if ((rc = upload(h->wsuper_box, wsboxes.data(), wsboxes.size()))) return rc;
-  if (SG > 0) {
-    if ((rc = upload(h->super_off, soff.data(), soff.size()))) return rc;
-    if ((rc = upload(h->super_box, sboxes.data(), sboxes.size()))) return rc;
+    if (off) (*off)[k + 1] = wp_off[k + 1];
   }
-  return build_headers(h, n_tracks, wp_off, meta, off, soff, woff, wsoff, geo);
+  for (int a = 0; a < 4; ++a) tot[a] = run[a];
+  return RX_OK;
 }
 
-// The per-slot headers (rx_slot_hdr) from the host tables rx_upload_tracks and
-// build_chunks produced.
-int build_headers(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* meta,
-                  const std::vector<int32_t>& off, const std::vector<int32_t>& soff, const std::vector<int32_t>& woff,
-                  const std::vector<int32_t>& wsoff, const std::vector<double>& geo) {
+// Culling tables for every slot (rx_cull.h through the host twin): chunks of G
+// consecutive boundary segments per side, their end-point boxes, per slot the
+// bounding circle of all boundary points and the longest segment (kernel margins,
+// DESIGN.md §3), the float32 copies and the per-slot headers.
+int build_chunks(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* seg,
+                 const double* meta) {
+  const int G = h->cfg.cull_chunk, SG = h->cfg.cull_super;  // SG: leaves per super-chunk (0 = one level)
+  int64_t tot[4];
+  int rc;
+  if ((rc = rx_cull_table_sizes(n_tracks, wp_off, G, SG, tot))) return rc;
+  const size_t n1 = (size_t)n_tracks + 1, Wt = (size_t)wp_off[n_tracks];
+  std::vector<int32_t> off(n1), soff(n1), woff(n1), wsoff(n1);
+  std::vector<double> boxes(4 * tot[0]), sboxes(4 * tot[1]), wboxes(4 * tot[2]), wsboxes(4 * tot[3]);
+  std::vector<double> geo(4 * (size_t)n_tracks);
+  std::vector<float> boxes_f(20 * tot[0]), sboxes_f(20 * tot[1]), sf(8 * Wt);
   std::vector<rx_slot_hdr> hd((size_t)n_tracks);
-  for (int k = 0; k < n_tracks; ++k) {
-    rx_slot_hdr& r = hd[k];
-    r.wp0 = wp_off[k];
-    r.W = wp_off[k + 1] - wp_off[k];
-    r.chunk_off = off.empty() ? 0 : off[k];
-    r.super_off = soff.empty() ? 0 : soff[k];
-    r.wchunk_off = woff.empty() ? 0 : woff[k];
-    r.wsuper_off = wsoff.empty() ? 0 : wsoff[k];
-    r.pad0 = r.pad1 = 0;
-    for (int i = 0; i < 4; ++i) r.geo[i] = geo.empty() ? 0.0 : geo[4 * (size_t)k + i];
-    for (int i = 0; i < 8; ++i) r.meta[i] = meta[8 * (size_t)k + i];
+  const rx_cull_tables t = {off.data(),    soff.data(),    woff.data(), wsoff.data(),   boxes.data(),
+                            sboxes.data(), wboxes.data(),  wsboxes.data(), geo.data(), boxes_f.data(),
+                            sboxes_f.data(), sf.data(), hd.data()};
+  if ((rc = rx_build_cull_tables_host(n_tracks, wp_off, wp, seg, meta, G, SG, &t, nullptr))) return rc;
+  if ((rc = upload(h->seg_f, sf.data(), sf.size()))) return rc;
+  if (G > 0) {
+    h->n_chunk_boxes = (int32_t)tot[0];
+    h->n_super_boxes = (int32_t)tot[1];
+    if ((rc = upload(h->chunk_box_f, boxes_f.data(), boxes_f.size()))) return rc;
+    if (SG > 0 && (rc = upload(h->super_box_f, sboxes_f.data(), sboxes_f.size()))) return rc;
+    if ((rc = upload(h->chunk_off, off.data(), off.size()))) return rc;
+    if ((rc = upload(h->chunk_box, boxes.data(), boxes.size()))) return rc;
+    if ((rc = upload(h->slot_geo, geo.data(), geo.size()))) return rc;
+    if ((rc = upload(h->wchunk_off, woff.data(), woff.size()))) return rc;
+    if ((rc = upload(h->wchunk_box, wboxes.data(), wboxes.size()))) return rc;
+    if ((rc = upload(h->wsuper_off, wsoff.data(), wsoff.size()))) return rc;
+    if ((rc = upload(h->wsuper_box, wsboxes.data(), wsboxes.size()))) return rc;
+    if (SG > 0) {
+      if ((rc = upload(h->super_off, soff.data(), soff.size()))) return rc;
+      if ((rc = upload(h->super_box, sboxes.data(), sboxes.size()))) return rc;
+    }
   }
   return upload(h->slot_hdr, hd.data(), hd.size());
 }
@@ -502,12 +444,9 @@ int rx_upload_tracks(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const d
   if ((rc = upload(h->wp, wp, 2 * Wt))) return rc;
   if ((rc = upload(h->nrm, nrm, 2 * Wt))) return rc;
   if ((rc = upload(h->seg, seg, 8 * Wt))) return rc;
-  {  // float32 copy of the segments (nearest rounding; the kernel's error bound covers it)
-    std::vector<float> sf(8 * (size_t)Wt);
-    for (size_t i = 0; i < sf.size(); ++i) sf[i] = (float)seg[i];
-    if ((rc = upload(h->seg_f, sf.data(), sf.size()))) return rc;
-  }
   if ((rc = upload(h->meta, meta, 8 * (size_t)n_tracks))) return rc;
+  // the culling tables, the per-slot headers and the float32 copy of the segments (nearest
+  // rounding; the kernel's error bound covers it)
   if ((rc = build_chunks(h, n_tracks, wp_off, wp, seg, meta))) return rc;
   h->wp_off_h.assign(wp_off, wp_off + n_tracks + 1);
   h->n_tracks = n_tracks;
@@ -1799,6 +1738,140 @@ int rx_build_tracks_host(int32_t n, int32_t factor, const int32_t* cp_off, const
     rx_track_meta(P, W, &ws, width[k], b, meta + 8 * (size_t)k, &dy, &dx);
     meta[8 * (size_t)k + 2] = atan2(dy, dx);
   }
+  return RX_OK;
+}
+
+// ---- culling tables (ABI v25, additive) -----------------------------------------
+int rx_cull_table_sizes(int32_t n, const int32_t* wp_off, int32_t G, int32_t SG, int64_t* out) {
+  if (!out) return fail(RX_EINVAL, "rx_cull_table_sizes: out is null");
+  return cull_check("rx_cull_table_sizes", n, wp_off, nullptr, nullptr, nullptr, G, SG, nullptr, true, nullptr, out);
+}
+
+int rx_build_cull_tables_host(int32_t n, const int32_t* wp_off, const double* wp, const double* seg,
+                              const double* meta, int32_t G, int32_t SG, const rx_cull_tables* t, void* /*stream*/) {
+  std::vector<int32_t> off;
+  int64_t tot[4];
+  const int rc = cull_check("rx_build_cull_tables_host", n, wp_off, wp, seg, meta, G, SG, t, false, &off, tot);
+  if (rc != RX_OK) return rc;
+  const size_t n1 = (size_t)n + 1;
+  for (int32_t k = 0; k < n; ++k) {  // the kernel's steps (rx_cull.hip) with one lane
+    const int32_t wp0 = wp_off[k], W = wp_off[k + 1] - wp0;
+    const double* s = seg + 8 * (size_t)wp0;
+    rx_cull_slot o = {0, 0, 0, 0, tot[0], tot[1], t->chunk_box, t->super_box, t->wchunk_box, t->wsuper_box,
+                      t->chunk_box_f, t->super_box_f};
+    double b[4], longest, geo[4] = {0.0, 0.0, 0.0, 0.0};
+    rx_cull_extent(s, W, 0, 1, t->seg_f + 8 * (size_t)wp0, b, &longest);
+    if (G > 0) {
+      rx_cull_geo(b, rx_cull_reach(s, W, 0, 1, 0.5 * (b[0] + b[2]), 0.5 * (b[1] + b[3])), longest, geo);
+      o.chunk0 = off[n1 + k];
+      o.super0 = SG > 0 ? off[2 * n1 + k] : 0;
+      o.wchunk0 = off[3 * n1 + k];
+      o.wsuper0 = off[4 * n1 + k];
+      rx_cull_boxes(s, wp + 2 * (size_t)wp0, W, G, SG, 0, 1, &o);
+      for (int c = 0; c < 4; ++c) t->slot_geo[4 * (size_t)k + c] = geo[c];
+    }
+    rx_cull_header((rx_slot_hdr*)t->slot_hdr + k, wp0, W, &o, geo, meta + 8 * (size_t)k);
+  }
+  if (G > 0) {
+    std::copy(off.begin() + n1, off.begin() + 2 * n1, t->chunk_off);
+    if (SG > 0) std::copy(off.begin() + 2 * n1, off.begin() + 3 * n1, t->super_off);
+    std::copy(off.begin() + 3 * n1, off.begin() + 4 * n1, t->wchunk_off);
+    std::copy(off.begin() + 4 * n1, off.begin() + 5 * n1, t->wsuper_off);
+  }
+  return RX_OK;
+}
+
+// The launch behind rx_build_cull_tables and rx_upload_tracks_device: `off` (cull_check's
+// five offset arrays) goes up through a stream-ordered allocation, as rx_build_tracks'
+// offsets do (a pageable source: the copy has left `off` when hipMemcpyAsync returns).
+static int cull_launch(const char* fn, int32_t n, const std::vector<int32_t>& off, const int64_t tot[4],
+                       const double* wp, const double* seg, const double* meta, int32_t G, int32_t SG,
+                       const rx_cull_tables* t, hipStream_t s) {
+  int32_t* off_dev = nullptr;
+  const size_t bytes = off.size() * sizeof(int32_t);
+  if (hipMallocAsync((void**)&off_dev, bytes, s) != hipSuccess || !off_dev)
+    return fail(RX_ENOMEM, "%s: hipMallocAsync(%zu bytes) failed", fn, bytes);
+  hipError_t e = hipMemcpyAsync(off_dev, off.data(), bytes, hipMemcpyHostToDevice, s);
+  int lrc = 0;
+  if (e == hipSuccess) lrc = rx_launch_cull_tables(n, G, SG, off_dev, wp, seg, meta, t, tot[0], tot[1], s);
+  const hipError_t ef = hipFreeAsync(off_dev, s);
+  if (e != hipSuccess) return fail(RX_EHIP, "%s: offset copy failed: %s", fn, hipGetErrorString(e));
+  if (lrc != 0) return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)lrc));
+  if (ef != hipSuccess) return fail(RX_EHIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(ef));
+  return RX_OK;
+}
+
+int rx_build_cull_tables(int32_t n, const int32_t* wp_off, const double* wp, const double* seg, const double* meta,
+                         int32_t G, int32_t SG, const rx_cull_tables* t, void* stream) {
+  std::vector<int32_t> off;
+  int64_t tot[4];
+  const int rc = cull_check("rx_build_cull_tables", n, wp_off, wp, seg, meta, G, SG, t, false, &off, tot);
+  if (rc != RX_OK) return rc;
+  return cull_launch("rx_build_cull_tables", n, off, tot, wp, seg, meta, G, SG, t, (hipStream_t)stream);
+}
+
+int rx_upload_tracks_device(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* nrm,
+                            const double* seg, const double* meta, void* stream) {
+  if (!h) return fail(RX_EINVAL, "rx_upload_tracks_device: null handle");
+  if (n_tracks <= 0 || !wp_off || !wp || !nrm || !seg || !meta)
+    return fail(RX_EINVAL, "rx_upload_tracks_device: bad arguments");
+  const int G = h->cfg.cull_chunk, SG = h->cfg.cull_super;
+  std::vector<int32_t> off;
+  int64_t tot[4];
+  {  // the offsets' checks (rx_upload_tracks' W limits); the output pointers are the handle's, set below
+    const int rc = cull_check("rx_upload_tracks_device", n_tracks, wp_off, nullptr, nullptr, nullptr, G, SG, nullptr,
+                              true, &off, tot);
+    if (rc != RX_OK) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  RX_HIP(hipSetDevice(h->cfg.device));
+  // launches of the old table may be in flight on any stream, and buffers may be re-allocated
+  RX_HIP(hipDeviceSynchronize());
+  std::vector<double> meta_h(8 * (size_t)n_tracks);  // the one transfer to the host
+  RX_HIP(hipMemcpyAsync(meta_h.data(), meta, meta_h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  RX_HIP(hipStreamSynchronize(s));
+  for (int k = 0; k < n_tracks; ++k) {
+    if (!(meta_h[8 * (size_t)k + 3] >= 0)) return fail(RX_EINVAL, "rx_upload_tracks_device: track %d width invalid", k);
+    if (!(meta_h[8 * (size_t)k + 4] > 0))
+      return fail(RX_EINVAL, "rx_upload_tracks_device: track %d max_track_distance must be > 0 (got %g; NaN marks a "
+                             "track rx_build_tracks found invalid)", k, meta_h[8 * (size_t)k + 4]);
+  }
+  // nothing of the handle has changed so far; from here on the old table is gone
+  const size_t n1 = (size_t)n_tracks + 1, Wt = (size_t)wp_off[n_tracks];
+  int rc;
+  if ((rc = reserve(h->wp_off, n1)) || (rc = reserve(h->wp, 2 * Wt)) || (rc = reserve(h->nrm, 2 * Wt)) ||
+      (rc = reserve(h->seg, 8 * Wt)) || (rc = reserve(h->meta, 8 * (size_t)n_tracks)) ||
+      (rc = reserve(h->seg_f, 8 * Wt)) || (rc = reserve(h->slot_hdr, (size_t)n_tracks)))
+    return rc;
+  if (G > 0) {
+    if ((rc = reserve(h->chunk_off, n1)) || (rc = reserve(h->wchunk_off, n1)) || (rc = reserve(h->wsuper_off, n1)) ||
+        (rc = reserve(h->chunk_box, 4 * (size_t)tot[0])) || (rc = reserve(h->chunk_box_f, 20 * (size_t)tot[0])) ||
+        (rc = reserve(h->wchunk_box, 4 * (size_t)tot[2])) || (rc = reserve(h->wsuper_box, 4 * (size_t)tot[3])) ||
+        (rc = reserve(h->slot_geo, 4 * (size_t)n_tracks)))
+      return rc;
+    if (SG > 0 && ((rc = reserve(h->super_off, n1)) || (rc = reserve(h->super_box, 4 * (size_t)tot[1])) ||
+                   (rc = reserve(h->super_box_f, 20 * (size_t)tot[1]))))
+      return rc;
+  }
+  h->n_tracks = 0;  // until the new table stands
+  h->assigned = false;
+  RX_HIP(hipMemcpyAsync(h->wp_off.p, wp_off, n1 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  RX_HIP(hipMemcpyAsync(h->wp.p, wp, 2 * Wt * sizeof(double), hipMemcpyDeviceToDevice, s));
+  RX_HIP(hipMemcpyAsync(h->nrm.p, nrm, 2 * Wt * sizeof(double), hipMemcpyDeviceToDevice, s));
+  RX_HIP(hipMemcpyAsync(h->seg.p, seg, 8 * Wt * sizeof(double), hipMemcpyDeviceToDevice, s));
+  RX_HIP(hipMemcpyAsync(h->meta.p, meta, 8 * (size_t)n_tracks * sizeof(double), hipMemcpyDeviceToDevice, s));
+  const rx_cull_tables t = {h->chunk_off.p, h->super_off.p,  h->wchunk_off.p, h->wsuper_off.p,  h->chunk_box.p,
+                            h->super_box.p, h->wchunk_box.p, h->wsuper_box.p, h->slot_geo.p,    h->chunk_box_f.p,
+                            h->super_box_f.p, h->seg_f.p,    h->slot_hdr.p};
+  if ((rc = cull_launch("rx_upload_tracks_device", n_tracks, off, tot, h->wp.p, h->seg.p, h->meta.p, G, SG, &t, s)))
+    return rc;
+  RX_HIP(hipStreamSynchronize(s));
+  if (G > 0) {
+    h->n_chunk_boxes = (int32_t)tot[0];
+    h->n_super_boxes = (int32_t)tot[1];
+  }
+  h->wp_off_h.assign(wp_off, wp_off + n1);
+  h->n_tracks = n_tracks;
   return RX_OK;
 }
 

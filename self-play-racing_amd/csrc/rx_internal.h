@@ -274,6 +274,12 @@ extern "C" int rx_launch_gae(int T, int N, const float* r, const float* v, const
 extern "C" int rx_launch_build_tracks(int n_tracks, int factor, const int32_t* cp_off, const double* cp,
                                       const double* width, double* wp, double* nrm, double* seg, double* meta,
                                       hipStream_t s);
+// rx_cull.hip: the culling tables of n_tracks slots, a wavefront per slot.  off (device): wp_off and the
+// chunk / super / wchunk / wsuper offset arrays back to back, n_tracks + 1 entries each; n_leaf / n_super:
+// the leaf and super box totals (the float tables' block stride); arguments checked by rx_api.cpp
+extern "C" int rx_launch_cull_tables(int n_tracks, int G, int SG, const int32_t* off, const double* wp,
+                                     const double* seg, const double* meta, const rx_cull_tables* t, int64_t n_leaf,
+                                     int64_t n_super, hipStream_t s);
 // rx_render.hip: the renderer's three kernels (arguments checked by rx_api.cpp)
 extern "C" int rx_launch_raster_static(int n, int size, int n_edges, const int32_t* edge_off, const int32_t* edges,
                                        uint8_t* layer, hipStream_t s);

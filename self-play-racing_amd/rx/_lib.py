@@ -36,7 +36,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_eval_steps", "rx_raster_static", "rx_raster_static_host", "rx_raster_trail", "rx_raster_trail_host",
            "rx_raster_frame", "rx_raster_frame_host", "rx_policy_act_bank", "rx_match_steps",
            "rx_league_weights", "rx_league_weights_host", "rx_league_draw", "rx_league_draw_host",
-           "rx_league_rollout_steps")
+           "rx_league_rollout_steps", "rx_cull_table_sizes", "rx_build_cull_tables", "rx_build_cull_tables_host",
+           "rx_upload_tracks_device")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -164,6 +165,16 @@ class RxRasterIO(ctypes.Structure):
                [(k, _P) for k in RASTER_PTR_FIELDS] + [("out_pitch", ctypes.c_int64), ("out_size", ctypes.c_int64)]
 
 
+# culling tables of a device-resident track table (ABI v25, additive; include/rx.h)
+RX_WP_CHUNK, RX_WP_SUPER, RX_SLOT_HDR_BYTES = 8, 4, 128
+CULL_FIELDS = ("chunk_off", "super_off", "wchunk_off", "wsuper_off", "chunk_box", "super_box", "wchunk_box",
+               "wsuper_box", "slot_geo", "chunk_box_f", "super_box_f", "seg_f", "slot_hdr")
+
+
+class RxCullTables(ctypes.Structure):
+    _fields_ = [(k, _P) for k in CULL_FIELDS]
+
+
 class RxError(RuntimeError):
     pass
 
@@ -243,6 +254,11 @@ def load(build_if_missing=True):
     L.rx_set_start_draws.argtypes = [_P, _P, ctypes.c_int64, _P]
     L.rx_build_tracks.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_P] * 9
     L.rx_build_tracks_host.argtypes = L.rx_build_tracks.argtypes
+    L.rx_cull_table_sizes.argtypes = [ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, _P]
+    L.rx_build_cull_tables.argtypes = [ctypes.c_int32, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.POINTER(RxCullTables), _P]
+    L.rx_build_cull_tables_host.argtypes = L.rx_build_cull_tables.argtypes
+    L.rx_upload_tracks_device.argtypes = [_P, ctypes.c_int32, _P, _P, _P, _P, _P, _P]
     L.rx_eval_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxEvalIO), ctypes.c_int32, _P]
     L.rx_policy_act_bank.argtypes = [ctypes.POINTER(RxPolicyBankIO), _P]
     L.rx_match_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxMatchIO), ctypes.c_int32, _P]

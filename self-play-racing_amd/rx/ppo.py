@@ -76,9 +76,17 @@ def build_vector_env(env_fn, num_envs, seed, device, **kw):
 class PPO:
     log_std_schedule = (-0.5, -1.6)  # agent/ppo.py:250-251
     info_path = "data/training_info_single_3.json"
+    resamples_tracks = True  # config["track_resample_every"]: single-agent PPO on one rank only
 
     def __init__(self, env_fn, config, device="cuda"):
         self.config = config
+        if config.get("track_resample_every", 0):
+            if not self.resamples_tracks:
+                raise ValueError(f"config['track_resample_every'] is not supported by {type(self).__name__} "
+                                 "(single-agent PPO only, DESIGN.md §8)")
+            if rdist.world() > 1:
+                raise ValueError("config['track_resample_every'] is not supported with more than one rank "
+                                 "(DESIGN.md §8)")
         want = device if torch.cuda.is_available() and config.get("cuda", True) else "cpu"
         self.device = torch.device(want)
         if self.device.type != "cuda":
@@ -641,16 +649,51 @@ class PPO:
         z = lambda *s: torch.zeros(s, device=self.device)  # noqa: E731
         return (z(T, N, *obs_shape), z(T, N, *act_shape), z(T, N), z(T, N), z(T, N), z(T, N))
 
+    def resample_tracks(self, control_points=None, widths=None):
+        """Swap the envs onto a fresh track pool without rebuilding them
+        (RacingVectorEnv.set_tracks: the table is built and handed over on the
+        device).  With no arguments the pool of swap g (1 for the first) is
+        ``num_envs`` tracks of ``gen_tracks(seed=None)`` and then one
+        ``randint(6, 10)`` width each, all drawn from
+        ``RandomState(seed + 7919 * g)``: np.random, which shuffles the minibatches,
+        does not move.  Every env is reset; the captured rollout graphs are dropped
+        (they hold the old table's pointers and wave counts).  Returns the new
+        (next_obs, next_done) for the next rollout."""
+        from .track import gen_tracks
+        from .track_device import DeviceTrackTable
+        if not self.resamples_tracks or rdist.world() > 1 or not hasattr(self.envs, "set_tracks"):
+            raise ValueError("resample_tracks: single-agent PPO on one rank only (DESIGN.md §8)")
+        n = self.num_local_envs
+        if control_points is None or widths is None:
+            g = self.envs.track_generation + 1
+            rng = np.random.RandomState((self.config["seed"] + 7919 * g) % 2 ** 32)
+            if control_points is None:
+                control_points = gen_tracks(n, seed=None, rng=rng)
+            if widths is None:
+                widths = [int(rng.randint(6, 10)) for _ in range(len(control_points))]
+        table = DeviceTrackTable.build(control_points, widths, device=self.device)
+        next_obs = self.envs.set_tracks(table)
+        self._graphs = {}
+        return next_obs, torch.zeros(n, device=self.device)
+
     def train_iter(self):
         """agent/ppo.py:211-281 as a generator: yields (update, num_updates,
-        global_step, EpisodeSummary) after every update (evaluation hooks)."""
+        global_step, EpisodeSummary) after every update (evaluation hooks).
+        With config["track_resample_every"] = K > 0 (default 0: off) the envs move
+        to a fresh track pool (``resample_tracks``) before update u for every
+        u > 0 with u % K == 0."""
         c = self.config
         obs, actions, logprobs, dones, rewards, values = self._buffers()
         next_obs = self.envs.buf["obs"].clone()  # obs of the reset done at construction
         next_done = torch.zeros(self.num_local_envs, device=self.device)
         num_updates = c["total_timesteps"] // c["batch_size"]
         global_step = 0
+        resample = int(c.get("track_resample_every", 0))
         for update in range(num_updates):
+            if resample > 0 and update > 0 and update % resample == 0:
+                o, d = self.resample_tracks()  # into the same tensors: captured graphs key on their addresses
+                next_obs.copy_(o)
+                next_done.copy_(d)
             frac = self._anneal(update, num_updates)
             self._speed_weight_anneal(frac)
             obs, actions, logprobs, dones, rewards, values, next_obs, next_done, ep = self.collect_rollout(

@@ -101,6 +101,7 @@ class SelfPlayPPO(PPO):
     log_std_schedule = (-0.3, -1.2)  # agent/self_play_ppo.py:128-129
     info_path = "data/training_info_self_play_3.json"
     checkpoint_fmt = "models/checkpoint_update_{}.pth"
+    resamples_tracks = False  # track swaps during self-play and league training are out of scope
 
     def __init__(self, env_fn, config, device="cuda"):
         self.opponent_pool = []

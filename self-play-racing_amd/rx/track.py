@@ -37,12 +37,14 @@ DEFAULT_WIDTH = 6.0  # environment/track.py:77-80
 
 
 def gen_random_track(num_points=15, base_radius=50, radius_variation=15, angle_jitter=0.2, smoothness=0.5,
-                     seed=None):
+                     seed=None, rng=None):
     """Random closed control polygon -- environment/track.py:4-45.
 
     Same global-RNG draws in the same order: n jitter offsets, then n radius
-    variations (drawn one per point, as the reference's loop does)."""
-    rs = np.random
+    variations (drawn one per point, as the reference's loop does).  ``rng`` (a
+    ``np.random.RandomState``): the same draws from it instead, the global RNG
+    untouched."""
+    rs = np.random if rng is None else rng
     if seed is not None:
         rs.seed(seed)
     ang = np.linspace(0, TWO_PI, num_points, endpoint=False)
@@ -58,18 +60,21 @@ def gen_random_track(num_points=15, base_radius=50, radius_variation=15, angle_j
     return np.column_stack([r * np.cos(ang), r * np.sin(ang)])
 
 
-def _draw_params():
-    # environment/track.py:50-54, global RNG
-    n = np.random.randint(10, 15)
-    base = np.random.randint(50, 80)
-    var = np.random.randint(10, base // 2 - 10)
-    jit = np.random.uniform(0.2, 0.7)
-    smooth = np.random.uniform(0.2, 0.7)
+def _draw_params(rs=np.random):
+    # environment/track.py:50-54, global RNG (or the caller's RandomState)
+    n = rs.randint(10, 15)
+    base = rs.randint(50, 80)
+    var = rs.randint(10, base // 2 - 10)
+    jit = rs.uniform(0.2, 0.7)
+    smooth = rs.uniform(0.2, 0.7)
     return n, base, var, jit, smooth
 
 
-def gen_tracks(num_tracks=10, seed=None):
-    """environment/track.py:47-56, with the reseed cycle memoised.
+def gen_tracks(num_tracks=10, seed=None, rng=None):
+    """environment/track.py:47-56, with the reseed cycle memoised.  ``rng`` (a
+    ``np.random.RandomState``) takes the place of the global RNG: the same
+    distributions in the same order from it, ``np.random`` left as it was (a track
+    swap in the middle of training must not move the stream the updates shuffle with).
 
     With ``seed`` set, every track's draws start from the RNG state that
     ``np.random.seed(seed)`` plus the previous track's 2*n uniform draws left
@@ -79,12 +84,13 @@ def gen_tracks(num_tracks=10, seed=None):
     the same read-only object.  The global RNG ends in the reference's state.
     """
     out = []
+    rs = np.random if rng is None else rng
     if seed is None or num_tracks <= 0:
         for _ in range(num_tracks):
-            out.append(gen_random_track(*_draw_params(), seed))
+            out.append(gen_random_track(*_draw_params(rs), seed, rng))
         return out
-    p = _draw_params()
-    cp = gen_random_track(*p, seed)
+    p = _draw_params(rs)
+    cp = gen_random_track(*p, seed, rng)
     cp.setflags(write=False)
     out.append(cp)
     prev_n = p[0]
@@ -94,16 +100,16 @@ def gen_tracks(num_tracks=10, seed=None):
         hit = memo.get(prev_n)
         if hit is None:
             if state_after is not None:  # resync the real RNG before drawing anew
-                np.random.set_state(state_after)
-            q = _draw_params()
-            c = gen_random_track(*q, seed)
+                rs.set_state(state_after)
+            q = _draw_params(rs)
+            c = gen_random_track(*q, seed, rng)
             c.setflags(write=False)
-            hit = (c, q[0], np.random.get_state())
+            hit = (c, q[0], rs.get_state())
             memo[prev_n] = hit
         cp, prev_n, state_after = hit
         out.append(cp)
     if state_after is not None:
-        np.random.set_state(state_after)
+        rs.set_state(state_after)
     return out
 
 

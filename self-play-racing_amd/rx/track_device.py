@@ -1,0 +1,111 @@
+"""A track table that lives in device memory.
+
+``rx.track.TrackSet`` is a host object: even its "device" backend downloads the
+table rx_build_tracks wrote, walks it on the host and hands host arrays to
+rx_upload_tracks, which derives the culling tables in a host loop and uploads
+everything again.  ``DeviceTrackTable`` keeps the four arrays where the kernel
+left them; ``RacingVectorEnv.set_tracks`` hands them to rx_upload_tracks_device,
+which copies them device to device and builds the culling tables with a kernel
+(include/rx.h, csrc/rx_cull.hip).  Only the [n + 1] offsets and the control
+points exist on the host; the table itself comes down when someone asks for it
+(``download``, ``track_set``: the renderer, ``save_table``).
+
+The table is the C level's, unchanged: meta[:, 2] and meta[:, 4] are
+rx_build_tracks' values (ocml atan2, x * x), which ``TrackSet`` replaces by the
+reference's numpy expressions.  ``from_arrays`` uploads a
+``TrackSet.arrays()`` dict as it is, so an env swapped onto it steps bit for bit
+like one constructed on that TrackSet.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .track import DEFAULT_CONTROL_POINTS, DEFAULT_WIDTH, TrackSet
+
+KEYS = ("wp", "nrm", "seg", "meta")
+
+
+class DeviceTrackTable:
+    """Slots packed as rx_upload_tracks' layout, the arrays on ``device``:
+    ``wp_off`` (host int32 [n + 1]), ``wp`` / ``nrm`` [Wtot, 2], ``seg``
+    [2 Wtot, 4], ``meta`` [n, 8] (float64 tensors), plus what the host knows of
+    the slots: ``control_points``, ``widths`` (None when built ``from_arrays``
+    without them) and ``factor``."""
+
+    def __init__(self, wp_off, wp, nrm, seg, meta, control_points=None, widths=None, factor=30):
+        self.wp_off = np.ascontiguousarray(wp_off, dtype=np.int32)
+        self.wp, self.nrm, self.seg, self.meta = wp, nrm, seg, meta
+        self.device = meta.device
+        self.control_points, self.widths, self.factor = control_points, widths, factor
+        self._track_set = None
+
+    def __len__(self):
+        return len(self.wp_off) - 1
+
+    @classmethod
+    def build(cls, control_points, widths, factor=30, device=None):
+        """One slot per given track, in order, no dedup: ONE rx_build_tracks launch
+        on torch's current stream of ``device``, no download and no wait.  What the
+        host can see is checked here (RxError names the track and the field); a
+        track only device memory shows to be bad (a repeated control point, a
+        non-finite coordinate, a negative width) is marked by the kernel and refused
+        by ``RacingVectorEnv.set_tracks``."""
+        L = _lib.load()
+        dev = torch.device("cuda" if device is None else device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        cps = [DEFAULT_CONTROL_POINTS if c is None else c for c in control_points]
+        ws = [DEFAULT_WIDTH if w is None else w for w in widths]
+        n = len(cps)
+        if n == 0 or len(ws) != n:
+            raise ValueError("need at least one track and one width per track")
+        flat = [np.asarray(c, dtype=np.float64) for c in cps]
+        for k, c in enumerate(flat):
+            if c.ndim != 2 or c.shape[1] != 2:
+                raise ValueError(f"track {k}: control points must be [P, 2], got {c.shape}")
+        cp_off = np.concatenate([[0], np.cumsum([len(c) for c in flat])]).astype(np.int32)
+        cp = np.ascontiguousarray(np.concatenate(flat))
+        w = np.ascontiguousarray(ws, dtype=np.float64)
+        wt = max(int(cp_off[-1]) * max(int(factor), 0), 0)
+        cuts = np.concatenate([[0], np.cumsum((2 * wt, 2 * wt, 8 * wt, 8 * n))])
+        wp_off = np.zeros(n + 1, dtype=np.int32)
+        with torch.cuda.device(dev):
+            cp_d, w_d = torch.from_numpy(cp).to(dev), torch.from_numpy(w).to(dev)
+            flat_d = torch.empty(int(cuts[-1]), dtype=torch.float64, device=dev)
+            parts = [flat_d[cuts[i]:cuts[i + 1]] for i in range(4)]
+            _lib.check(L.rx_build_tracks(n, factor, _lib.ptr(cp_off), _lib.ptr(cp_d), _lib.ptr(w_d), _lib.ptr(wp_off),
+                                         *[_lib.ptr(x) for x in parts], _lib.stream_ptr()), "rx_build_tracks")
+        return cls(wp_off, parts[0].view(wt, 2), parts[1].view(wt, 2), parts[2].view(2 * wt, 4), parts[3].view(n, 8),
+                   control_points=cps, widths=ws, factor=factor)
+
+    @classmethod
+    def from_arrays(cls, arrays, device):
+        """Upload a packed host table (``TrackSet.arrays()``: wp_off, wp, nrm, seg,
+        meta) unchanged.  The control points are not part of it: ``track_set()``
+        then gives slots without them (widths from meta[:, 3])."""
+        dev = torch.device(device)
+        up = {k: torch.from_numpy(np.ascontiguousarray(arrays[k], dtype=np.float64)).to(dev) for k in KEYS}
+        return cls(arrays["wp_off"], up["wp"], up["nrm"], up["seg"], up["meta"])
+
+    def download(self):
+        """The raw table as a dict of host arrays (rx_upload_tracks' layout)."""
+        out = {k: getattr(self, k).cpu().numpy() for k in KEYS}
+        return dict(wp_off=self.wp_off.copy(), **out)
+
+    def track_set(self):
+        """A ``TrackSet`` of backend "device" over the downloaded table (through
+        ``TrackSet._adopt``, so a slot equals ``TrackGeometry.from_waypoints`` of its
+        waypoints); the download happens on first use only."""
+        if self._track_set is None:
+            a = self.download()
+            n = len(self)
+            cps = self.control_points if self.control_points is not None else [None] * n
+            ws = self.widths if self.widths is not None else [float(x) for x in a["meta"][:, 3]]
+            ts = TrackSet(self.factor, "device")
+            ts.device = self.device
+            ts._adopt(list(zip(cps, ws)), a)
+            for k, (c, w) in enumerate(zip(cps, ws)):
+                if c is not None:
+                    ts._index.setdefault(TrackSet._key(c, w), k)
+            self._track_set = ts
+        return self._track_set

@@ -150,6 +150,8 @@ class RacingVectorEnv:
         self.speed_weight = float(speed_weight)
         if half_cone is None:
             half_cone = np.pi / 3 if A == 1 else np.pi / 2
+        self._table = None  # set_tracks: the device-resident table the envs run on
+        self.track_generation = 0  # track swaps so far (set_tracks)
         if track_set is not None:
             self.tracks = track_set
         elif track_backend == "scipy":
@@ -227,6 +229,56 @@ class RacingVectorEnv:
         self._closed = False
 
     # ------------------------------------------------------------ plumbing
+    @property
+    def tracks(self):
+        """The TrackSet the envs run on.  After ``set_tracks`` it is the device
+        table's ``track_set()``: downloaded on first use (the renderer, save_table),
+        not by the swap."""
+        if self._tracks is None:
+            self._tracks = self._table.track_set()
+        return self._tracks
+
+    @tracks.setter
+    def tracks(self, track_set):
+        self._tracks = track_set
+
+    def set_tracks(self, table, track_of_env=None):
+        """Swap the track pool of the live env for ``table`` (an
+        rx.track_device.DeviceTrackTable on this env's device): env i runs slot
+        ``track_of_env[i]`` (default i % len(table)).  rx_upload_tracks_device (device
+        to device, the culling tables built by a kernel), rx_assign, then every env is
+        reset; returns the reset observations.  Episodes in flight are dropped without
+        being tallied; tallies already made stay (``episode_stats``).  A table librx
+        refuses (RxError naming the track) leaves the env on its old tracks."""
+        N, n = self.num_envs, len(table)
+        dev_idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        if table.device.type != "cuda" or table.device.index != dev_idx:
+            raise ValueError(f"the table lives on {table.device}, the envs on {self.device}")
+        if track_of_env is None:
+            toe = (np.arange(N) % n).astype(np.int32)
+        else:
+            toe = np.ascontiguousarray(track_of_env, dtype=np.int32).reshape(-1)
+            if toe.shape != (N,) or toe.min() < 0 or toe.max() >= n:
+                raise ValueError(f"track_of_env must assign each of the {N} envs a slot in [0, {n})")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.rx_upload_tracks_device(self._h, n, _lib.ptr(table.wp_off), _lib.ptr(table.wp),
+                                                      _lib.ptr(table.nrm), _lib.ptr(table.seg), _lib.ptr(table.meta),
+                                                      _lib.stream_ptr()), "rx_upload_tracks_device")
+            # the bound arrays as construction left them: rx_assign re-reads them into the
+            # new wave order, and the reset below starts every episode afresh
+            for k, t in self._st.items():
+                if t is not None and k not in ("track", "speed_weight"):
+                    t.fill_(-1) if k == "finished_step" else t.zero_()
+            torch.cuda.synchronize(self.device)
+            _lib.check(self.L.rx_assign(self._h, _lib.ptr(toe)), "rx_assign")
+        self.track_of_env = toe
+        self._table, self._tracks = table, None
+        self.track_generation += 1
+        self._dev_newer = False  # rx_assign loaded the working copy from the bound arrays
+        obs = self.reset_device()
+        self._episode_start[:] = time.perf_counter()
+        return obs
+
     def _upload_tracks(self):
         t = self.tracks.arrays()
         n = len(t["meta"])
