@@ -987,6 +987,77 @@ int rx_league_draw_host(const rx_league_io* lg, int64_t n, const float* done, co
 int rx_league_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
                             const rx_league_io* lg, int32_t precision, void* stream);
 
+/* ABI v25, additive: the TRACK CURRICULUM -- every finished episode of a
+ * single-agent rollout is tallied against its track slot on the device, and the
+ * envs are redrawn over the slots weighted towards the tracks the learner still
+ * fails (a pool-level prioritised level replay; train.py:78,94-99 draws the pool
+ * once and every env keeps its track; rx.curriculum).  The arithmetic lives in
+ * csrc/rx_curriculum.h, shared by the kernels (csrc/rx_curriculum.hip) and the
+ * *_host twins; DESIGN.md §4.
+ *
+ * tally[k] = (episodes, finishes, crashes, progress_q) of slot k, int64.
+ *
+ * rx_track_tally over n envs: every env e with done[e] != 0 (float [n]) and
+ * 0 <= track[e] < n_tracks adds to row track[e]: episodes += 1; finishes += (info
+ * [e][RX_INFO_PROGRESS] == 1.0, which the env reports for a finished lap only,
+ * racing_env.py:158-159); crashes += (terminated[e] != 0 and not finished);
+ * progress_q += (int64)(progress * 1048576.0).  `info` is f64 [n][RX_INFO_W], the
+ * terminal step's rx_io.info of a single-agent handle.  A slot outside the table is
+ * not counted.  A wave whose envs are all running returns after one ballot; the
+ * envs that ended are summed per slot inside the wave, and one lane per slot
+ * issues the int64 atomic adds: integer sums, so the result does not depend on the
+ * order of arrival.  cdf, p, track_of_env and seed are not read.
+ *
+ * rx_track_scores: tallies -> p and the integer sampling table (one workgroup
+ * walks the table in chunks; float64, every operation separately rounded):
+ *   p_k   = (finishes + prior) / (episodes + 2 * prior)        (unseen slot: 0.5)
+ *   q_k   = 1 - p_k (score 0, "fail")  or  4 * p_k * (1 - p_k) (score 1, "potential")
+ *   f_k   = q_k multiplied `power` times into 1.0               (power 0: uniform)
+ *   W_k   = (uint64)(f_k * 4294967296.0)
+ *   cdf_k = W_0 + ... + W_k, an exact integer (non-negative int64);  F = cdf_{n-1}.
+ * track and track_of_env are not read.
+ *
+ * rx_track_draw: track_of_env[e] for e < n at `generation` g:
+ *   h1 = splitmix64(seed ^ splitmix64(((uint64)g << 32) ^ (uint64)e));  h2 = splitmix64(h1)
+ *   u  = (double)(h1 >> 11) * 2^-53
+ *   F == 0 or u < mix:  slot = mulhi64(h2, n_tracks)           (the uniform part)
+ *   otherwise:          r = mulhi64(h2, F);  slot = the smallest k with r < cdf_k
+ * (binary search), so a slot with W_k == 0 is drawn by the uniform part only.
+ * track, tally and p are not read.
+ *
+ * All pointers are DEVICE pointers; the *_host twins take the same arguments as
+ * HOST pointers, ignore `stream`, make no HIP call and give the same bits.
+ *
+ * rx_track_rollout_steps: rx_rollout_steps' contract and outputs bit for bit, plus
+ * after every step's launches ONE rx_track_tally of that step's done row,
+ * io->terminated and io->info (both required), ordered after the step on `stream`.
+ * No host wait and no allocation: a stream capture records it.
+ *
+ * Checked before any HIP call (RX_EINVAL, the message names the field): null
+ * pointers, n_tracks <= 0, score not 0 or 1, power outside 0..4, prior <= 0 or
+ * NaN, mix outside [0, 1] or NaN, n <= 0, the precision, a handle that is not an
+ * assigned, bound single-agent handle. */
+typedef struct rx_track_io {
+  int32_t n_tracks;        /* track slots, > 0 */
+  int32_t score;           /* 0 = fail, 1 = potential (scores only) */
+  const int32_t* track;    /* [N] the slot of env e, env order: rx_state.track (tally only) */
+  int64_t* tally;          /* [n_tracks][4] */
+  int64_t* cdf;            /* [n_tracks] */
+  double* p;               /* [n_tracks] p_k (scores only) */
+  int32_t* track_of_env;   /* [N] out (draw only) */
+  uint64_t seed;
+} rx_track_io;
+int rx_track_tally(const rx_track_io* tc, int64_t n, const float* done, const uint8_t* terminated, const double* info,
+                   void* stream);
+int rx_track_tally_host(const rx_track_io* tc, int64_t n, const float* done, const uint8_t* terminated,
+                        const double* info, void* stream);
+int rx_track_scores(const rx_track_io* tc, int32_t power, double prior, void* stream);
+int rx_track_scores_host(const rx_track_io* tc, int32_t power, double prior, void* stream);
+int rx_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, void* stream);
+int rx_track_draw_host(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, void* stream);
+int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
+                           int32_t precision, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

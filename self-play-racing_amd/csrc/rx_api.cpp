@@ -2321,4 +2321,144 @@ int rx_league_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, 
   return RX_OK;
 }
 
+// ABI v25, additive: the track curriculum (csrc/rx_curriculum.h).  The checks of the four entry
+// points and their host twins, before any HIP call; what: 0 = tally, 1 = scores, 2 = draw.
+static int track_args(const char* fn, const rx_track_io* tc, int what) {
+  if (!tc) return fail(RX_EINVAL, "%s: null track io", fn);
+  if (tc->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, tc->n_tracks);
+  if (what == 0 && (!tc->track || !tc->tally))
+    return fail(RX_EINVAL, "%s: null %s", fn, !tc->track ? "track" : "tally");
+  if (what == 1) {
+    if (!tc->tally || !tc->cdf || !tc->p)
+      return fail(RX_EINVAL, "%s: null %s", fn, !tc->tally ? "tally" : !tc->cdf ? "cdf" : "p");
+    if (tc->score != 0 && tc->score != 1) return fail(RX_EINVAL, "%s: score=%d must be 0 or 1", fn, tc->score);
+  }
+  if (what == 2 && (!tc->cdf || !tc->track_of_env))
+    return fail(RX_EINVAL, "%s: null %s", fn, !tc->cdf ? "cdf" : "track_of_env");
+  return RX_OK;
+}
+
+static int track_tally_args(const char* fn, const rx_track_io* tc, int64_t n, const float* done,
+                            const uint8_t* terminated, const double* info) {
+  const int rc = track_args(fn, tc, 0);
+  if (rc) return rc;
+  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
+  if (!done || !terminated || !info)
+    return fail(RX_EINVAL, "%s: null %s", fn, !done ? "done" : !terminated ? "terminated" : "info");
+  return RX_OK;
+}
+
+static int track_scores_args(const char* fn, const rx_track_io* tc, int32_t power, double prior) {
+  const int rc = track_args(fn, tc, 1);
+  if (rc) return rc;
+  if (power < 0 || power > 4) return fail(RX_EINVAL, "%s: power=%d outside 0..4", fn, power);
+  if (!(prior > 0.0)) return fail(RX_EINVAL, "%s: prior=%g must be > 0", fn, prior);
+  return RX_OK;
+}
+
+static int track_draw_args(const char* fn, const rx_track_io* tc, int64_t n, double mix) {
+  const int rc = track_args(fn, tc, 2);
+  if (rc) return rc;
+  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
+  if (!(mix >= 0.0 && mix <= 1.0)) return fail(RX_EINVAL, "%s: mix=%g outside [0, 1]", fn, mix);
+  return RX_OK;
+}
+
+int rx_track_tally(const rx_track_io* tc, int64_t n, const float* done, const uint8_t* terminated, const double* info,
+                   void* stream) {
+  int rc = track_tally_args("rx_track_tally", tc, n, done, terminated, info);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_tally(tc, n, done, terminated, info, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_tally: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_tally_host(const rx_track_io* tc, int64_t n, const float* done, const uint8_t* terminated,
+                        const double* info, void* /*stream*/) {
+  const int rc = track_tally_args("rx_track_tally_host", tc, n, done, terminated, info);
+  if (rc) return rc;
+  rx_host_track_tally(tc, n, done, terminated, info);
+  return RX_OK;
+}
+
+int rx_track_scores(const rx_track_io* tc, int32_t power, double prior, void* stream) {
+  int rc = track_scores_args("rx_track_scores", tc, power, prior);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_scores(tc, power, prior, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_scores: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_scores_host(const rx_track_io* tc, int32_t power, double prior, void* /*stream*/) {
+  const int rc = track_scores_args("rx_track_scores_host", tc, power, prior);
+  if (rc) return rc;
+  rx_host_track_scores(tc, power, prior);
+  return RX_OK;
+}
+
+int rx_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, void* stream) {
+  int rc = track_draw_args("rx_track_draw", tc, n, mix);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_draw(tc, n, generation, mix, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_draw: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_draw_host(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, void* /*stream*/) {
+  const int rc = track_draw_args("rx_track_draw_host", tc, n, mix);
+  if (rc) return rc;
+  rx_host_track_draw(tc, n, generation, mix);
+  return RX_OK;
+}
+
+// rx_rollout_steps with one k_track_tally after every step: the same policy and env launches in the
+// same order, so every rollout output is rx_rollout_steps'; the tally reads the done row the step just
+// wrote and the env's terminated / info rows before the next step overwrites them (one stream).
+int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
+                           int32_t precision, void* stream) {
+  const char* fn = "rx_track_rollout_steps";
+  // the track io first: its refusals need no handle (tests/test_curriculum_cpu.py)
+  int rc = track_args(fn, tc, 0);
+  if (rc) return rc;
+  if (precision != RX_PREC_FP32 && precision != RX_PREC_BF16)
+    return fail(RX_EINVAL, "%s: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", fn, precision);
+  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
+  if (!io || !r) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : "rollout io");
+  if (!h->assigned || !h->bound || h->cfg.n_agents != 1)
+    return fail(RX_EINVAL, "%s: the handle must be an assigned, bound single-agent handle", fn);
+  if (r->T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, r->T);
+  if (r->obs_dim != h->D) return fail(RX_EINVAL, "%s: obs_dim %d != the handle's %d", fn, r->obs_dim, h->D);
+  if (!r->params || !r->log_std || !r->eps || !r->obs || !r->actions || !r->logprobs || !r->values || !r->rewards ||
+      !r->dones || !r->next_obs || !r->next_done)
+    return fail(RX_EINVAL, "%s: null rollout buffer", fn);
+  if (!io->terminated || !io->info)
+    return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
+                !io->terminated ? "terminated" : "info");
+  const int64_t N = h->cfg.n_envs, D = h->D;
+  hipStream_t hs = (hipStream_t)stream;
+  const void* frag = nullptr;
+  if (precision == RX_PREC_BF16) {  // as rx_rollout_steps: the bf16 operand fragments once per call
+    if (rx_launch_policy_frag(r->obs_dim, r->params, h->policy_frag.p, hs))
+      return fail(RX_EHIP, "%s: fragment launch failed", fn);
+    frag = h->policy_frag.p;
+  }
+  for (int32_t t = 0; t < r->T; ++t) {
+    const bool last = t + 1 == r->T;
+    const rx_policy_io pio{r->obs_dim, N, r->obs + t * N * D, r->eps + t * N * 2, r->params, r->log_std,
+                           r->actions + t * N * 2, r->logprobs + t * N, r->values + t * N, 0, 0, precision,
+                           nullptr, 0};
+    if ((rc = rx_launch_policy_act(&pio, hs, frag)) != 0)
+      return fail(RX_EHIP, "%s: policy launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+    rx_io s = *io;
+    s.actions = r->actions + t * N * 2;
+    s.obs = last ? r->next_obs : r->obs + (t + 1) * N * D;
+    s.reward = r->rewards + t * N;
+    s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;
+    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
+    if ((rc = rx_launch_track_tally(tc, N, s.done_f32, io->terminated, io->info, hs)) != 0)
+      return fail(RX_EHIP, "%s: tally launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+  }
+  return RX_OK;
+}
+
 }  // extern "C"

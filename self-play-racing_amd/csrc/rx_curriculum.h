@@ -1,0 +1,86 @@
+// rx_curriculum.h -- the rules of the TRACK CURRICULUM (rx_track_tally /
+// rx_track_scores / rx_track_draw / rx_track_rollout_steps, ABI v25 additive) as one
+// set of inline functions compiled twice: by hipcc for gfx950 (rx_curriculum.hip)
+// and as plain C++ for the host twins (rx_curriculum_host.cpp).  The scores are
+// float64 with every step ONE separately rounded IEEE operation (both translation
+// units are compiled with -ffp-contract=off; no pow, no exp); the sampling weights
+// and every sum are INTEGERS, so any summation order gives the same bits: the
+// kernel's parallel scan, the host twin's serial loop and a Python restatement
+// (tests/test_curriculum_cpu.py) agree bit for bit.
+//
+// Rules (DESIGN.md §4 "Track curriculum"):
+//  * tally[k] = (episodes, finishes, crashes, progress_q) of track slot k, int64.
+//    An env whose episode ended on slot k counts one episode; finished = the
+//    terminal step's info progress == 1.0 (the env reports exactly 1.0 only for a
+//    finished lap, racing_env.py:158-159); crashed = terminated and not finished;
+//    everything else is a timeout.  progress_q += (int64)(progress * 2^20).
+//  * sampling weights:
+//      p_k = (finishes + prior) / (episodes + 2 * prior)          (unseen: 0.5)
+//      q_k = 1 - p_k                 score 0, "fail": the tracks still failed
+//      q_k = 4 * p_k * (1 - p_k)     score 1, "potential": sometimes solved
+//      f_k = q_k multiplied `power` times into 1.0
+//      W_k = (uint64)(f_k * 2^32);   cdf_k = W_0 + ... + W_k (exact);  F = cdf_{n-1}
+//  * the draw of env e at generation g:
+//      h1 = splitmix64(seed ^ splitmix64(((uint64)g << 32) ^ e));  h2 = splitmix64(h1)
+//      u  = (h1 >> 11) * 2^-53
+//      F == 0 or u < mix:  slot = mulhi64(h2, n_tracks)            (uniform)
+//      otherwise:          r = mulhi64(h2, F), slot = the smallest k with r < cdf_k
+//    so a slot with W_k == 0 is reached through the uniform part only.
+#pragma once
+
+#include <stdint.h>
+
+#include "rx.h"
+#include "rx_league.h"  // rx_lg_splitmix64
+#include "rx_math.h"
+
+#define RX_TRACK_TALLY_W 4         // episodes, finishes, crashes, progress_q
+#define RX_TRACK_MAX_POWER 4
+#define RX_TRACK_SCORES_CHUNK 1024 // slots k_track_scores scans per pass (one lane each)
+#define RX_TRACK_SCORE_FAIL 0
+#define RX_TRACK_SCORE_POTENTIAL 1
+
+RX_FN uint64_t rx_tc_mulhi64(uint64_t a, uint64_t b) {
+#if defined(__HIPCC__)
+  return __umul64hi(a, b);
+#else
+  return (uint64_t)(((unsigned __int128)a * (unsigned __int128)b) >> 64);
+#endif
+}
+
+// the outcome of an ended episode: bit 0 = finished, bit 1 = crashed, 0 = timeout
+RX_FN int rx_tc_outcome(double progress, uint8_t terminated) {
+  const int fin = progress == 1.0 ? 1 : 0;
+  return fin | ((terminated != 0 && !fin) ? 2 : 0);
+}
+
+RX_FN int64_t rx_tc_progress_q(double progress) { return (int64_t)(progress * 1048576.0); }
+
+// W_k of one slot from its tally row; *p_out = p_k
+RX_FN uint64_t rx_tc_weight(const int64_t* t, int score, int power, double prior, double* p_out) {
+  const double n = (double)t[0], fin = (double)t[1];
+  const double p = (fin + prior) / (n + 2.0 * prior);
+  *p_out = p;
+  const double fail = 1.0 - p;
+  const double q = score == RX_TRACK_SCORE_POTENTIAL ? (4.0 * p) * fail : fail;
+  double f = 1.0;
+  for (int i = 0; i < power; ++i) f = f * q;
+  const double w = f * 4294967296.0;
+  return w > 0.0 ? (uint64_t)w : 0ull;  // a tally with finishes > episodes (never written here) weighs nothing
+}
+
+// the slot of env e at generation g from the inclusive integer table cdf[0 .. n_tracks - 1]
+RX_FN int32_t rx_tc_draw(const int64_t* cdf, int32_t n_tracks, uint64_t seed, uint32_t g, uint32_t e, double mix) {
+  const uint64_t h1 = rx_lg_splitmix64(seed ^ rx_lg_splitmix64(((uint64_t)g << 32) ^ (uint64_t)e));
+  const uint64_t h2 = rx_lg_splitmix64(h1);
+  const double u = (double)(h1 >> 11) * 0x1p-53;
+  const uint64_t F = (uint64_t)cdf[n_tracks - 1];
+  if (F == 0 || u < mix) return (int32_t)rx_tc_mulhi64(h2, (uint64_t)n_tracks);
+  const uint64_t r = rx_tc_mulhi64(h2, F);  // r < F = cdf[n_tracks - 1]: the search ends inside the table
+  int32_t lo = 0, hi = n_tracks - 1;
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (r < (uint64_t)cdf[mid]) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}

@@ -1,0 +1,142 @@
+// rx_curriculum.hip -- the track curriculum's three kernels (ABI v25 additive;
+// rules in rx_curriculum.h, DESIGN.md §4 "Track curriculum"):
+//   k_track_tally   once per rollout step, a lane per env: the envs whose episode
+//                   ended are summed per track slot INSIDE the wave and one lane
+//                   per slot issues the int64 atomic adds;
+//   k_track_scores  once per resample, ONE workgroup: per-slot weight and the
+//                   inclusive integer scan into cdf, RX_TRACK_SCORES_CHUNK slots
+//                   per pass with the running total carried along;
+//   k_track_draw    once per resample, a lane per env: two hashes and a binary
+//                   search over cdf in global memory.
+// Arguments are checked by rx_api.cpp.
+#include <hip/hip_runtime.h>
+
+#include "rx.h"
+#include "rx_curriculum.h"
+
+namespace {
+
+struct track_tally_args {
+  const int32_t* track;
+  int64_t* tally;
+  const float* done;
+  const uint8_t* terminated;
+  const double* info;  // [n][RX_INFO_W]
+  int64_t n;
+  int32_t n_tracks;
+};
+
+// In steady state almost no env ends in a step: the wave ballots `done` and leaves.
+// Early in training thousands of envs can end in one step on a handful of slots, and
+// every adder on one row serialises in the L2 atomic unit, so the wave first folds
+// its lanes per slot (the wave-uniform loop of k_league_act): a leader
+// slot is read from the lowest pending lane, its lanes are balloted, the counts are
+// popcounts against the finished / crashed ballots, progress_q is a butterfly sum
+// over the wave, and ONE lane adds the non-zero columns.  Integer adds: the result
+// does not depend on the order in which waves arrive.
+__global__ __launch_bounds__(256) void k_track_tally(track_tally_args a) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool ended = e < a.n && a.done[e] != 0.0f;
+  if (__ballot(ended) == 0ull) return;
+  int32_t slot = -1;
+  int out = 0;
+  long long pq = 0;
+  if (ended) {
+    const int32_t k = a.track[e];
+    if (k >= 0 && k < a.n_tracks) {  // a slot outside the table is not counted
+      const double progress = a.info[(size_t)e * RX_INFO_W + RX_INFO_PROGRESS];
+      slot = k;
+      out = rx_tc_outcome(progress, a.terminated[e]);
+      pq = (long long)rx_tc_progress_q(progress);
+    }
+  }
+  const bool live = slot >= 0;
+  unsigned long long todo = __ballot(live);
+  const unsigned long long fin = __ballot(live && (out & 1)), crash = __ballot(live && (out & 2));
+  const int lane = (int)(threadIdx.x & 63);
+  while (todo) {
+    const int leader = __ffsll(todo) - 1;
+    const int32_t s = __builtin_amdgcn_readlane(slot, leader);  // wave-uniform: in [0, n_tracks)
+    const bool mine = live && slot == s;
+    const unsigned long long same = __ballot(mine);
+    long long sum = mine ? pq : 0;
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == leader) {
+      unsigned long long* row = reinterpret_cast<unsigned long long*>(a.tally + (size_t)s * RX_TRACK_TALLY_W);
+      const unsigned long long nf = (unsigned long long)__popcll(same & fin);
+      const unsigned long long nc = (unsigned long long)__popcll(same & crash);
+      atomicAdd(row, (unsigned long long)__popcll(same));
+      if (nf) atomicAdd(row + 1, nf);
+      if (nc) atomicAdd(row + 2, nc);
+      if (sum) atomicAdd(row + 3, (unsigned long long)sum);
+    }
+    todo &= ~same;
+  }
+}
+
+constexpr int kScoreThreads = RX_TRACK_SCORES_CHUNK;
+constexpr int kScoreWaves = kScoreThreads / 64;
+
+// One workgroup; per pass lane i takes slot base + i: W_k, an inclusive wave scan by
+// shuffles, the wave totals through LDS, and the running total of the passes before
+// (every lane keeps its own copy: the same integer).
+__global__ __launch_bounds__(kScoreThreads) void k_track_scores(const int64_t* __restrict__ tally,
+                                                                int64_t* __restrict__ cdf, double* __restrict__ p,
+                                                                int n_tracks, int score, int power, double prior) {
+  __shared__ unsigned long long wave_total[kScoreWaves];
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  unsigned long long carry = 0;
+  for (int base = 0; base < n_tracks; base += kScoreThreads) {
+    const int k = base + (int)threadIdx.x;
+    unsigned long long x = 0;
+    if (k < n_tracks) {
+      double pk;
+      x = rx_tc_weight(tally + (size_t)k * RX_TRACK_TALLY_W, score, power, prior, &pk);
+      p[k] = pk;
+    }
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned long long y = __shfl_up(x, o, 64);
+      if (lane >= o) x += y;
+    }
+    if (lane == 63) wave_total[wave] = x;
+    __syncthreads();
+    unsigned long long before = 0, total = 0;
+    for (int j = 0; j < kScoreWaves; ++j) {
+      const unsigned long long t = wave_total[j];
+      if (j < wave) before += t;
+      total += t;
+    }
+    if (k < n_tracks) cdf[k] = (int64_t)(carry + before + x);
+    carry += total;
+    __syncthreads();  // the next pass overwrites wave_total
+  }
+}
+
+__global__ __launch_bounds__(256) void k_track_draw(const int64_t* __restrict__ cdf, int32_t* __restrict__ track_of_env,
+                                                    int64_t n, int32_t n_tracks, uint64_t seed, uint32_t generation,
+                                                    double mix) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  track_of_env[e] = rx_tc_draw(cdf, n_tracks, seed, generation, (uint32_t)e, mix);
+}
+
+}  // namespace
+
+extern "C" int rx_launch_track_tally(const rx_track_io* tc, int64_t n, const float* done, const uint8_t* terminated,
+                                     const double* info, hipStream_t s) {
+  const track_tally_args a{tc->track, tc->tally, done, terminated, info, n, tc->n_tracks};
+  hipLaunchKernelGGL(k_track_tally, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rx_launch_track_scores(const rx_track_io* tc, int power, double prior, hipStream_t s) {
+  hipLaunchKernelGGL(k_track_scores, dim3(1), dim3(kScoreThreads), 0, s, tc->tally, tc->cdf, tc->p, tc->n_tracks,
+                     tc->score, power, prior);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rx_launch_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, hipStream_t s) {
+  hipLaunchKernelGGL(k_track_draw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tc->cdf, tc->track_of_env, n,
+                     tc->n_tracks, tc->seed, generation, mix);
+  return (int)hipGetLastError();
+}

@@ -367,6 +367,17 @@ extern "C" int rx_launch_league_draw(const rx_league_io* lg, int64_t n, const fl
 // rx_league_host.cpp: the same two as host loops (plain C++, no HIP call)
 extern "C" void rx_host_league_weights(const rx_league_io* lg, int n_live, int power, double mix, double prior);
 extern "C" void rx_host_league_draw(const rx_league_io* lg, int64_t n, const float* done, const double* info);
+// rx_curriculum.hip: per-slot tally of the envs that ended; tallies -> integer sampling table; env -> slot draw
+// (arguments checked by rx_api.cpp)
+extern "C" int rx_launch_track_tally(const rx_track_io* tc, int64_t n, const float* done, const uint8_t* terminated,
+                                     const double* info, hipStream_t s);
+extern "C" int rx_launch_track_scores(const rx_track_io* tc, int power, double prior, hipStream_t s);
+extern "C" int rx_launch_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, hipStream_t s);
+// rx_curriculum_host.cpp: the same three as host loops (plain C++, no HIP call)
+extern "C" void rx_host_track_tally(const rx_track_io* tc, int64_t n, const float* done, const uint8_t* terminated,
+                                    const double* info);
+extern "C" void rx_host_track_scores(const rx_track_io* tc, int power, double prior);
+extern "C" void rx_host_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double mix);
 extern "C" int rx_launch_adv_stats(const rx_ppo_batch* b, int n_mb, float* stats, double* moments, hipStream_t s);
 extern "C" int rx_adv_chunks(int mb);
 extern "C" int rx_launch_adv_stats_ws(const rx_ppo_batch* b, int n_mb, double* ws, float* stats, double* moments,

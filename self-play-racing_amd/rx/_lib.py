@@ -37,7 +37,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_raster_frame", "rx_raster_frame_host", "rx_policy_act_bank", "rx_match_steps",
            "rx_league_weights", "rx_league_weights_host", "rx_league_draw", "rx_league_draw_host",
            "rx_league_rollout_steps", "rx_cull_table_sizes", "rx_build_cull_tables", "rx_build_cull_tables_host",
-           "rx_upload_tracks_device")
+           "rx_upload_tracks_device", "rx_track_tally", "rx_track_tally_host", "rx_track_scores", "rx_track_scores_host",
+           "rx_track_draw", "rx_track_draw_host", "rx_track_rollout_steps")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -154,6 +155,16 @@ class RxLeagueIO(ctypes.Structure):
                 ("seed", ctypes.c_uint64), ("opp_precision", ctypes.c_int32)]
 
 
+# track curriculum (ABI v25, additive): per-slot tallies and prioritised env -> slot draws (include/rx.h)
+RX_TRACK_TALLY_W, RX_TRACK_MAX_POWER, RX_TRACK_SCORES_CHUNK = 4, 4, 1024
+TRACK_SCORES = {"fail": 0, "potential": 1}
+
+
+class RxTrackIO(ctypes.Structure):
+    _fields_ = [("n_tracks", ctypes.c_int32), ("score", ctypes.c_int32), ("track", _P), ("tally", _P), ("cdf", _P),
+                ("p", _P), ("track_of_env", _P), ("seed", ctypes.c_uint64)]
+
+
 # rendering (ABI v25, additive): pixel classes / trail bits, size limits, edge record width (include/rx.h)
 RX_PX_BACKGROUND, RX_PX_TRACK, RX_PX_BORDER, RX_PX_START, RX_PX_TRAIL0, RX_PX_TRAIL1 = 0, 1, 2, 3, 0x10, 0x20
 RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX, RX_RASTER_EDGE_W = 16, 2048, 6
@@ -264,7 +275,13 @@ def load(build_if_missing=True):
     L.rx_match_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxMatchIO), ctypes.c_int32, _P]
     L.rx_league_rollout_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxRolloutIO),
                                           ctypes.POINTER(RxSelfplayIO), ctypes.POINTER(RxLeagueIO), ctypes.c_int32, _P]
+    L.rx_track_rollout_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxRolloutIO),
+                                         ctypes.POINTER(RxTrackIO), ctypes.c_int32, _P]
     for sfx in ("", "_host"):
+        getattr(L, "rx_track_tally" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.c_int64, _P, _P, _P, _P]
+        getattr(L, "rx_track_scores" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.c_int32, ctypes.c_double, _P]
+        getattr(L, "rx_track_draw" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.c_int64, ctypes.c_uint32,
+                                                      ctypes.c_double, _P]
         getattr(L, "rx_league_weights" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int32, ctypes.c_int32,
                                                          ctypes.c_double, ctypes.c_double, _P]
         getattr(L, "rx_league_draw" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int64, _P, _P, _P]

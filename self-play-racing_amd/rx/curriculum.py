@@ -1,0 +1,334 @@
+"""Track curriculum: per-track tallies and prioritised draws on the device.
+
+``PPO.resample_tracks`` throws the whole pool away and draws a new one blindly,
+env i always runs slot i % n, and the only training statistics are three global
+sums.  Here every finished episode is counted against its track slot where it
+happens (one small kernel per rollout step), and at every
+``config["track_resample_every"]`` boundary the envs are redrawn over the slots,
+weighted towards the tracks the learner still fails -- a pool-level form of
+prioritised level replay; optionally the mastered slots are retired for fresh
+tracks.  The rollout stays one library call (rx_track_rollout_steps,
+include/rx.h) that a HIP graph can record.
+
+``TrackCurriculum``        the device tensors (tally, cdf, p, track_of_env) and
+                           the three kernels (rx_track_tally / _scores / _draw);
+``CurriculumStepRollout``  ppo_fused.StepRollout on rx_track_rollout_steps;
+``CurriculumPPO``          the trainer: PPO with the tally in the rollout and the
+                           prioritised ``resample_tracks``.
+
+The rules (tally, scores, draw) are csrc/rx_curriculum.h; DESIGN.md §4.
+
+Episodes in flight at a reassignment are dropped untallied (``set_tracks``'
+semantics), which biases the tallies against long episodes: keep
+``track_resample_every * num_steps`` well above an episode's length.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import dist as rdist
+from .ppo import PPO
+from .ppo_fused import StepRollout
+
+PROGRESS_Q = 1048576.0  # progress_q's fixed point (csrc/rx_curriculum.h)
+
+
+def _score_id(score):
+    if score not in _lib.TRACK_SCORES:
+        raise ValueError(f"curriculum score must be one of {sorted(_lib.TRACK_SCORES)}, got {score!r}")
+    return _lib.TRACK_SCORES[score]
+
+
+def check_rules(power, mix, prior, score):
+    """The ranges rx_track_scores / rx_track_draw accept, as ValueErrors naming the config key."""
+    if not 0 <= int(power) <= _lib.RX_TRACK_MAX_POWER:
+        raise ValueError(f"curriculum_power={power} outside 0..{_lib.RX_TRACK_MAX_POWER}")
+    if not 0.0 <= float(mix) <= 1.0:
+        raise ValueError(f"curriculum_mix={mix} outside [0, 1]")
+    if not float(prior) > 0.0:
+        raise ValueError(f"curriculum_prior={prior} must be > 0")
+    return int(power), float(mix), float(prior), _score_id(score)
+
+
+class TrackCurriculum:
+    """The tallies of ``venv``'s track slots and the draw of its envs over them.
+
+    ``tally`` int64 [n_tracks, 4] = (episodes, finishes, crashes, progress_q),
+    ``cdf`` int64 [n_tracks], ``p`` float64 [n_tracks], ``track_of_env`` int32 [N]:
+    device tensors at fixed addresses, so one struct serves every call and any
+    captured graph.  The slot of env e is read from the env's bound ``track`` array,
+    which rx_assign rewrites in place."""
+
+    def __init__(self, venv, seed, power=1, mix=0.1, prior=1.0, score="fail"):
+        if venv.n_agents != 1:
+            raise ValueError("the track curriculum tallies single-agent envs only (DESIGN.md §8)")
+        self.power, self.mix, self.prior, self.score = check_rules(power, mix, prior, score)
+        self.L = _lib.load()
+        self.venv, self.seed = venv, int(seed) & (2**64 - 1)
+        self.n_tracks = len(venv._table) if venv._table is not None else len(venv.tracks)
+        n, dev = venv.num_envs, venv.device
+        self.tally = torch.zeros((self.n_tracks, _lib.RX_TRACK_TALLY_W), dtype=torch.int64, device=dev)
+        self.cdf = torch.zeros(self.n_tracks, dtype=torch.int64, device=dev)
+        self.p = torch.full((self.n_tracks,), 0.5, dtype=torch.float64, device=dev)
+        self.track_of_env = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.tc = _lib.RxTrackIO(self.n_tracks, self.score, _lib.ptr(venv._st["track"]), _lib.ptr(self.tally),
+                                 _lib.ptr(self.cdf), _lib.ptr(self.p), _lib.ptr(self.track_of_env), self.seed)
+
+    def tally_step(self, done=None, stream=None):
+        """Count the envs whose episode ended in the step just enqueued (rx_track_tally on
+        the env's own terminated / info rows; ``done``: the step's done row when it went
+        into a rollout buffer).  The step must have run with ``full_info=True``."""
+        b = self.venv.buf
+        _lib.check(self.L.rx_track_tally(ctypes.byref(self.tc), self.venv.num_envs,
+                                         _lib.ptr(b["done_f32"] if done is None else done), _lib.ptr(b["terminated"]),
+                                         _lib.ptr(b["info"]), _lib.stream_ptr(stream)), "rx_track_tally")
+
+    def scores(self, stream=None):
+        """tallies -> ``p`` and the integer sampling table ``cdf`` (rx_track_scores)."""
+        _lib.check(self.L.rx_track_scores(ctypes.byref(self.tc), self.power, self.prior, _lib.stream_ptr(stream)),
+                   "rx_track_scores")
+
+    def draw(self, generation, stream=None):
+        """A slot for every env from the current table (rx_track_draw) -> ``track_of_env``."""
+        _lib.check(self.L.rx_track_draw(ctypes.byref(self.tc), self.venv.num_envs, int(generation) & 0xFFFFFFFF,
+                                        self.mix, _lib.stream_ptr(stream)), "rx_track_draw")
+        return self.track_of_env
+
+    def reset_slots(self, idx):
+        """Zero the tallies of the slots ``idx`` (their tracks were replaced)."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if idx.size:
+            if idx.min() < 0 or idx.max() >= self.n_tracks:
+                raise ValueError(f"slots must lie in [0, {self.n_tracks})")
+            self.tally[torch.from_numpy(idx).to(self.tally.device)] = 0
+
+    def table(self):
+        """The host view per slot, arrays of length n_tracks: episodes, finishes,
+        crashes, mean_progress (NaN before the first episode), p, prob (the draw
+        probability of the slot under the current tallies).  Runs ``scores`` and
+        downloads; call it between updates."""
+        self.scores()
+        t = self.tally.cpu().numpy()
+        cdf = self.cdf.cpu().numpy().astype(np.uint64)
+        w = np.diff(np.concatenate([[np.uint64(0)], cdf])).astype(np.float64)
+        n, F = self.n_tracks, float(cdf[-1])
+        prob = np.full(n, 1.0 / n) if F == 0 else (1.0 - self.mix) * (w / F) + self.mix / n
+        ep = t[:, 0].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean_progress = np.where(ep > 0, t[:, 3] / PROGRESS_Q / ep, np.nan)
+        return {"episodes": t[:, 0].copy(), "finishes": t[:, 1].copy(), "crashes": t[:, 2].copy(),
+                "mean_progress": mean_progress, "p": self.p.cpu().numpy(), "prob": prob}
+
+
+class CurriculumStepRollout(StepRollout):
+    """rx_track_rollout_steps driver: StepRollout's call with one rx_track_tally
+    after every step.  The step runs with the env's terminated and info rows, which
+    the tally reads; every rollout output equals StepRollout's bit for bit
+    (tests/test_curriculum_gpu.py).  Every address handed to the library is fixed, so
+    a captured graph of the call stays valid until the tracks are swapped."""
+
+    def __init__(self, agent, flat, venv, T, curriculum, prec=_lib.RX_PREC_FP32):
+        super().__init__(agent, flat, venv, T, prec)
+        self.curriculum = curriculum
+
+    def __call__(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done, eps=None, stream=None):
+        T, n, D = self.T, self.n, self.obs_dim
+        e = self.eps if eps is None else eps
+        key = tuple(t.data_ptr() for t in (obs, actions, logprobs, dones, rewards, values, next_obs, next_done, e))
+        r = self._cache.get(key)
+        if r is None:
+            shapes = {"obs": (obs, (T, n, D)), "actions": (actions, (T, n, 2)), "logprobs": (logprobs, (T, n)),
+                      "values": (values, (T, n)), "rewards": (rewards, (T, n)), "dones": (dones, (T, n)),
+                      "next_obs": (next_obs, (n, D)), "next_done": (next_done, (n,)), "eps": (e, (T, n, 2))}
+            for k, (t, shp) in shapes.items():
+                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError(f"rx_track_rollout_steps: {k} must be a contiguous float32 {shp}, got "
+                                     f"{tuple(t.shape)} {t.dtype}")
+            if len(self._cache) > 64:
+                self._cache.clear()
+            r = self._cache[key] = _lib.RxRolloutIO(
+                T, D, _lib.ptr(self.flat.flat_param), _lib.ptr(self.agent.log_std), _lib.ptr(e), _lib.ptr(obs),
+                _lib.ptr(actions), _lib.ptr(logprobs), _lib.ptr(values), _lib.ptr(rewards), _lib.ptr(dones),
+                _lib.ptr(next_obs), _lib.ptr(next_done))
+        if eps is None:
+            self.eps.normal_()
+        # the step's plain io plus the info rows the tally reads (no float64 reward copy); once per rollout
+        base = self.venv._io()
+        io = _lib.RxIO(*(getattr(base, k) for k in _lib.IO_FIELDS))
+        io.info = _lib.ptr(self.venv.buf["info"])
+        _lib.check(self.L.rx_track_rollout_steps(self.venv._h, io, r, ctypes.byref(self.curriculum.tc), self.prec,
+                                                 _lib.stream_ptr(stream)), "rx_track_rollout_steps")
+        self.venv._launched(stream)
+
+
+class CurriculumPPO(PPO):
+    """PPO that tallies every finished episode against its track slot and, every
+    ``config["track_resample_every"]`` updates, redraws the envs over the slots
+    weighted towards the tracks it still fails.
+
+    Config keys (defaults): ``curriculum_power`` 1, ``curriculum_mix`` 0.1,
+    ``curriculum_prior`` 1.0, ``curriculum_score`` "fail" (or "potential"),
+    ``curriculum_refresh`` 0.25 (the largest fraction of the slots retired per
+    resample), ``curriculum_mastery`` 0.8 and ``curriculum_min_episodes`` 4 (a slot
+    is retired once it has that many episodes and p at least the mastery).  With
+    ``track_resample_every`` 0 it only tallies: ``track_table()`` still answers
+    which tracks fail.
+
+    The slots are the distinct (control points, width) pairs the envs were built
+    on.  The rollout always goes through rx_track_rollout_steps or the per-step
+    loop; the persistent small-N rollout (``fused_rollout``) does not tally and is
+    bypassed.
+
+    Refused (ValueError): a world size above 1 (per-rank tallies would need an
+    all-reduce) and two-car envs."""
+
+    def __init__(self, env_fn, config, device="cuda"):
+        if rdist.world() > 1:
+            raise ValueError("CurriculumPPO needs world size 1: the per-track tallies are per rank and the "
+                             "sampling table would need their all-reduce (DESIGN.md §8)")
+        c = config
+        self._rules = check_rules(c.get("curriculum_power", 1), c.get("curriculum_mix", 0.1),
+                                  c.get("curriculum_prior", 1.0), c.get("curriculum_score", "fail"))
+        self.refresh = float(c.get("curriculum_refresh", 0.25))
+        self.mastery = float(c.get("curriculum_mastery", 0.8))
+        self.min_episodes = int(c.get("curriculum_min_episodes", 4))
+        if not 0.0 <= self.refresh <= 1.0:
+            raise ValueError(f"curriculum_refresh={self.refresh} outside [0, 1]")
+        # one spec, built and dropped with np.random put back: a train.py env_fn may draw its track id there
+        state = np.random.get_state()
+        spec = env_fn(0)
+        np.random.set_state(state)
+        if getattr(spec, "num_agents", 1) != 1:
+            raise ValueError("CurriculumPPO trains single-agent envs: two-car envs are not tallied per track "
+                             "(DESIGN.md §8)")
+        super().__init__(env_fn, config, device)
+        if not hasattr(self.envs, "reassign_tracks") or self.envs.n_agents != 1:
+            raise ValueError("CurriculumPPO needs a single-agent RacingVectorEnv")
+        geoms = self.envs.tracks.geoms
+        self._cps = [g.control_points for g in geoms]
+        self._widths = [g.track_width for g in geoms]
+        power, mix, prior, _ = self._rules
+        self.curriculum = TrackCurriculum(self.envs, c["seed"], power, mix, prior, c.get("curriculum_score", "fail"))
+        self.retired = []  # the slots each resample replaced, oldest first
+
+    # ------------------------------------------------------------ rollout
+    def _fused_rollout(self, T):
+        return None  # k_rollout does not tally
+
+    def _step_rollout(self, obs):
+        from . import ppo_fused
+        c = self.config
+        if self._fused_policy(obs) is None or not StepRollout.supported(self.envs, self.agent, c):
+            return None
+        T, prec = obs.shape[0], ppo_fused.precision(c)
+        sr = self.__dict__.get("_tc_steps_rollout")
+        if sr is None or sr.T != T or sr.n != self.envs.num_envs or sr.prec != prec:
+            sr = self._tc_steps_rollout = CurriculumStepRollout(self.agent, self._flat, self.envs, T,
+                                                                 self.curriculum, prec)
+        return sr
+
+    def _rollout_body(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done):
+        sr = self._step_rollout(obs)
+        if sr is not None:
+            obs[0].copy_(next_obs)
+            dones[0].copy_(next_done)
+            sr(obs, actions, logprobs, dones, rewards, values, next_obs, next_done)
+            return
+        # PPO's per-step loop with the info rows and the tally of every step
+        T = obs.shape[0]
+        obs[0].copy_(next_obs)
+        dones[0].copy_(next_done)
+        fused = self._fused_policy(obs)
+        for step in range(T):
+            if fused is not None:
+                action = fused(obs[step], actions[step], logprobs[step], values[step])
+            else:
+                with self._policy_ctx():
+                    action, logprob, _, value = self.agent.get_action_and_value(obs[step])
+                actions[step].copy_(action)
+                logprobs[step].copy_(logprob)
+                values[step].copy_(value.flatten())
+            last = step + 1 == T
+            _, _, done = self.envs.step_device(action, obs_out=next_obs if last else obs[step + 1],
+                                               reward_out=rewards[step],
+                                               done_out=next_done if last else dones[step + 1], full_info=True)
+            self.curriculum.tally_step(done)
+
+    # ------------------------------------------------------------ resampling
+    def _mastered(self):
+        """Up to floor(refresh * n_tracks) slots with enough episodes and p at least the
+        mastery, highest p first, ties by slot (from the scores just computed)."""
+        cur = self.curriculum
+        budget = int(math.floor(self.refresh * cur.n_tracks))
+        if budget <= 0:
+            return np.zeros(0, dtype=np.int64)
+        episodes = cur.tally[:, 0].cpu().numpy()
+        p = cur.p.cpu().numpy()
+        ok = np.nonzero((episodes >= self.min_episodes) & (p >= self.mastery))[0]
+        return ok[np.lexsort((ok, -p[ok]))][:budget].astype(np.int64)
+
+    def resample_tracks(self, control_points=None, widths=None):
+        """Redraw the envs over the track slots from the tallies.  With no arguments:
+        the scores; up to floor(curriculum_refresh * n_tracks) mastered slots are
+        retired for fresh tracks (``gen_tracks(seed=None)`` and one ``randint(6, 10)``
+        width each from ``RandomState(seed + 7919 * g)``, as ``PPO.resample_tracks``
+        draws them: np.random does not move), their tallies start again and the table
+        is rebuilt on the device; then every env draws its slot (generation g) and is
+        reset.  With nothing retired the table stays and only the assignment moves
+        (``reassign_tracks``).  ``control_points`` and ``widths`` (one per slot)
+        replace the whole pool instead.  The captured rollout graphs are dropped.
+        Returns the new (next_obs, next_done)."""
+        from .track import gen_tracks
+        from .track_device import DeviceTrackTable
+        cur, envs = self.curriculum, self.envs
+        g = envs.track_generation + 1
+        cur.scores()
+        if control_points is not None or widths is not None:
+            if control_points is None or widths is None or len(control_points) != cur.n_tracks \
+                    or len(widths) != cur.n_tracks:
+                raise ValueError(f"resample_tracks: pass control_points and widths for all {cur.n_tracks} slots")
+            retired = np.arange(cur.n_tracks, dtype=np.int64)
+            new_cps, new_widths = list(control_points), list(widths)
+        else:
+            retired = self._mastered()
+            if len(retired):
+                rng = np.random.RandomState((self.config["seed"] + 7919 * g) % 2 ** 32)
+                new_cps = gen_tracks(len(retired), seed=None, rng=rng)
+                new_widths = [int(rng.randint(6, 10)) for _ in range(len(retired))]
+        if len(retired):
+            for k, cp, w in zip(retired, new_cps, new_widths):
+                self._cps[k], self._widths[k] = cp, w
+            cur.reset_slots(retired)
+            cur.scores()  # a fresh slot weighs what an unseen one does
+            table = DeviceTrackTable.build(self._cps, self._widths, device=self.device)
+            toe = cur.draw(g).cpu().numpy()
+            next_obs = envs.set_tracks(table, toe)
+        else:
+            toe = cur.draw(g).cpu().numpy()
+            next_obs = envs.reassign_tracks(toe)
+        self.retired.append([int(k) for k in retired])
+        self._graphs = {}
+        return next_obs, torch.zeros(self.num_local_envs, device=self.device)
+
+    def track_table(self):
+        """``TrackCurriculum.table()``: which tracks this policy still fails."""
+        return self.curriculum.table()
+
+
+def format_track_table(table, limit=None):
+    """The per-slot table as text, the most failed slots first."""
+    order = np.lexsort((np.arange(len(table["p"])), table["p"]))
+    if limit is not None:
+        order = order[:limit]
+    lines = [f"{'slot':>6} {'episodes':>9} {'finishes':>9} {'crashes':>9} {'progress':>9} {'p':>7} {'prob':>9}"]
+    for k in order:
+        mp = table["mean_progress"][k]
+        lines.append(f"{k:>6} {table['episodes'][k]:>9} {table['finishes'][k]:>9} {table['crashes'][k]:>9} "
+                     f"{'-' if np.isnan(mp) else f'{mp:.3f}':>9} {table['p'][k]:>7.3f} {table['prob'][k]:>9.2e}")
+    return "\n".join(lines)
+
+
+__all__ = ["TrackCurriculum", "CurriculumStepRollout", "CurriculumPPO", "format_track_table", "check_rules"]

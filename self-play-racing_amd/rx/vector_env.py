@@ -279,6 +279,30 @@ class RacingVectorEnv:
         self._episode_start[:] = time.perf_counter()
         return obs
 
+    def reassign_tracks(self, track_of_env):
+        """Move the envs over the slots of the table they already run on: env i
+        runs slot ``track_of_env[i]`` from now on.  The second half of ``set_tracks``
+        without the upload: the bound arrays as construction left them, rx_assign
+        (which builds the wave order in host code), then every env is reset; returns
+        the reset observations and counts as a track swap (``track_generation``).
+        Episodes in flight are dropped without being tallied."""
+        N, n = self.num_envs, len(self._table) if self._table is not None else len(self.tracks)
+        toe = np.ascontiguousarray(track_of_env, dtype=np.int32).reshape(-1)
+        if toe.shape != (N,) or toe.min() < 0 or toe.max() >= n:
+            raise ValueError(f"track_of_env must assign each of the {N} envs a slot in [0, {n})")
+        with torch.cuda.device(self.device):
+            for k, t in self._st.items():
+                if t is not None and k not in ("track", "speed_weight"):
+                    t.fill_(-1) if k == "finished_step" else t.zero_()
+            torch.cuda.synchronize(self.device)
+            _lib.check(self.L.rx_assign(self._h, _lib.ptr(toe)), "rx_assign")
+        self.track_of_env = toe
+        self.track_generation += 1
+        self._dev_newer = False  # rx_assign loaded the working copy from the bound arrays
+        obs = self.reset_device()
+        self._episode_start[:] = time.perf_counter()
+        return obs
+
     def _upload_tracks(self):
         t = self.tracks.arrays()
         n = len(t["meta"])

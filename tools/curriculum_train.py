@@ -1,0 +1,115 @@
+"""Single-agent training with the track curriculum (rx.curriculum), against uniform sampling.
+
+    python tools/curriculum_train.py --envs 4096 --steps 128 --updates 60 --tracks 512 --resample-every 4
+    python tools/curriculum_train.py --envs 64 --steps 32 --updates 6 --tracks 8 --resample-every 2 --no-uniform
+
+``CurriculumPPO`` on a pool of ``--tracks`` distinct tracks (env i starts on slot
+i % tracks): every finished episode is tallied against its slot on the device;
+every ``--resample-every`` updates the envs are redrawn over the slots, weighted
+towards the tracks the learner still fails, and the mastered slots are retired for
+fresh tracks.  Unless ``--no-uniform``, a plain ``PPO`` run of equal env-steps on
+the same pool and the same cadence (``PPO.resample_tracks``: a blind new pool)
+follows.  Both are evaluated every ``--eval-every`` updates and at the end with
+rx.evaluate's protocol (40 held-out tracks x 5 runs, fused backend); the success
+rates over env-steps, the first evaluation at or above 90 % and the curriculum's
+per-slot table go to ``--out`` as JSON, and the table's most failed slots are
+printed.
+"""
+import argparse
+import json
+import os
+import random
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "self-play-racing_amd"))
+
+
+def run(kind, args, evaluator):
+    from rx.configs import base_config
+    from rx.curriculum import CurriculumPPO
+    from rx.envs import RacingEnv
+    from rx.ppo import PPO
+    from rx.track import gen_tracks
+    cfg = base_config(num_envs=args.envs, num_steps=args.steps, seed=args.seed, shuffle="device",
+                      track_resample_every=args.resample_every, policy_dtype=args.prec,
+                      curriculum_power=args.power, curriculum_mix=args.mix, curriculum_prior=args.prior,
+                      curriculum_score=args.score, curriculum_refresh=args.refresh, curriculum_mastery=args.mastery,
+                      curriculum_min_episodes=args.min_episodes)
+    cfg["total_timesteps"] = args.updates * cfg["batch_size"]
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    rng = np.random.RandomState(args.seed)
+    pool = gen_tracks(args.tracks, seed=None, rng=rng)
+    widths = [int(rng.randint(6, 10)) for _ in range(args.tracks)]
+    n = args.tracks
+    cls = CurriculumPPO if kind == "curriculum" else PPO
+    t = cls(lambda i: RacingEnv(num_sensors=11, track_pool=pool, track_id=i % n, track_width=widths[i % n]), cfg,
+            device="cuda")
+    info, curve = {"steps": [], "rewards": []}, []
+    for update, num_updates, gstep, ep in t.train_iter():
+        t._log(update, num_updates, gstep, ep, info)
+        if (update + 1) % args.eval_every == 0 or update + 1 == num_updates:
+            s = evaluator.run(t.agent)
+            curve.append({"update": update + 1, "env_steps": gstep, "success_rate": s["success_rate"],
+                          "crash_rate": s["crash_rate"]})
+            print(f"[{kind}] update {update + 1}: eval success {s['success_rate']:.3f} crash {s['crash_rate']:.3f}",
+                  flush=True)
+    first90 = next((c["env_steps"] for c in curve if c["success_rate"] >= 0.9), None)
+    out = {"kind": kind, "eval": curve, "env_steps_to_90": first90, "track_generation": t.envs.track_generation}
+    if kind == "curriculum":
+        from rx.curriculum import format_track_table
+        tab = t.track_table()
+        print(format_track_table(tab, limit=args.show))
+        out["track_table"] = {k: [None if isinstance(x, float) and np.isnan(x) else x for x in v.tolist()]
+                              for k, v in tab.items()}
+        out["retired_per_resample"] = [len(r) for r in t.retired]
+    t.envs.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--updates", type=int, default=60)
+    ap.add_argument("--tracks", type=int, default=512)
+    ap.add_argument("--resample-every", type=int, default=4)
+    ap.add_argument("--eval-every", type=int, default=5)
+    ap.add_argument("--power", type=int, default=1)
+    ap.add_argument("--mix", type=float, default=0.1)
+    ap.add_argument("--prior", type=float, default=1.0)
+    ap.add_argument("--score", choices=("fail", "potential"), default="fail")
+    ap.add_argument("--refresh", type=float, default=0.25)
+    ap.add_argument("--mastery", type=float, default=0.8)
+    ap.add_argument("--min-episodes", type=int, default=4)
+    ap.add_argument("--prec", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--show", type=int, default=20, help="slots of the table to print, the most failed first")
+    ap.add_argument("--no-uniform", action="store_true", help="skip the uniform PPO run")
+    ap.add_argument("--out", default="bench_out/curriculum_train.json")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("curriculum_train.py trains on the GPU: no device found")
+    from rx.evaluate import Evaluator
+    evaluator = Evaluator(backend="fused", device="cuda")
+    res = {"command": "python tools/curriculum_train.py " + " ".join(sys.argv[1:]),
+           "shape": {"envs": args.envs, "num_steps": args.steps, "updates": args.updates, "tracks": args.tracks,
+                     "resample_every": args.resample_every},
+           "protocol": "rx.evaluate.Evaluator: 40 held-out tracks x 5 runs, stochastic policy, fused backend",
+           "runs": []}
+    for kind in ("curriculum",) + (() if args.no_uniform else ("uniform",)):
+        res["runs"].append(run(kind, args, evaluator))
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:  # after every run: a later failure keeps what was measured
+            json.dump(res, f, indent=1)
+    evaluator.close()
+    print("->", args.out)
+
+
+if __name__ == "__main__":
+    main()
