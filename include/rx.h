@@ -543,7 +543,9 @@ typedef struct rx_ppo_batch {
   const float* advantages;  /* [B] */
   const float* returns;     /* [B] */
   const float* values;      /* [B] */
-  const int64_t* perm;      /* [n_mb*mb] this epoch's shuffled row indices (b_inds) */
+  const int64_t* perm;      /* [n_mb*mb] this epoch's shuffled row indices (b_inds); an entry outside
+                             * [0, n_rows) is an absent row: it adds nothing to the gradient, the KL sum
+                             * or the advantage moments (the divisors stay mb) */
   const float* params;      /* [P] flat parameters */
   const float* log_std;     /* [2] Agent.log_std buffer */
   const float* adv_stats;   /* [n_mb][2] (mean, unbiased std) from rx_ppo_adv_stats */
