@@ -1060,6 +1060,79 @@ int rx_track_draw_host(const rx_track_io* tc, int64_t n, uint32_t generation, do
 int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
                            int32_t precision, void* stream);
 
+/* ABI v25, additive: the track curriculum's REPLAY SCORES -- the learning-potential
+ * score, rank prioritisation and staleness of prioritised level replay (Jiang et
+ * al. 2021) over the track slots, from the advantages of the rollout just
+ * collected (rx.track_replay).  rx_track_io and its entry points above are
+ * untouched; this block stands beside them.  The arithmetic lives in
+ * csrc/rx_track_replay.h, shared by the kernels (csrc/rx_track_replay.hip) and the
+ * *_host twins; DESIGN.md §4.  Floating point is float64, every operation
+ * separately rounded; every sum is an integer.
+ *
+ * learn[k] = (samples, mag_q) of slot k, int64.
+ *
+ * rx_track_learn_tally over adv, f32 [T][n]: every a = adv[t][e] that is finite, of
+ * an env with 0 <= track[e] < n_tracks, adds to row track[e]: samples += 1;
+ * mag_q += (int64)((double)m * 1048576.0) with m = |a| (kind 0, the L1 value loss)
+ * or max(a, 0) (kind 1, the positive value loss), at most 1048576.0f.  Non-finite
+ * values and slots outside the table add nothing.  A lane per env column sums a
+ * chunk of rows in registers, the wave folds its lanes per slot, and one lane per
+ * slot issues the two int64 atomic adds: integer sums, so the result does not
+ * depend on the grid or on the order of arrival.  Only track and learn are read.
+ *
+ * rx_track_learn_fold(update u, alpha), per slot with samples > 0:
+ *   mean  = ((double)mag_q / 1048576.0) / (double)samples
+ *   score = seen < 0 ? mean : score + alpha * (mean - score);  seen = u;  learn row = 0
+ * Slots without samples are untouched.  Reads and writes learn, score, seen.
+ *
+ * rx_track_learn_tables(power, now): the rank, then the two integer tables.
+ *   key_k  = seen_k < 0 ? +inf : score_k        (a score is never negative)
+ *   rank_k = 1 + #{ j : key_j > key_k or (key_j == key_k and j < k) }   (1-based)
+ *   h = 1.0 / (double)rank_k;  f = h multiplied `power` times into 1.0   (beta = 1 / power)
+ *   W_k = (uint64)(f * 4294967296.0);  cdf_score_k = W_0 + ... + W_k   (exact)
+ *   S_k = seen_k < 0 ? 0 : max(now - seen_k, 0);  cdf_stale_k = S_0 + ... + S_k
+ * Reads score and seen, writes rank, cdf_score, cdf_stale.  F_stale may be 0.
+ *
+ * rx_track_learn_draw: track_of_env[e] for e < n at `generation` g, with h1, h2 and
+ * u of rx_track_draw:
+ *   u < mix:                              slot = mulhi64(h2, n_tracks)
+ *   u < mix + stale_mix and F_stale > 0:  r = mulhi64(h2, F_stale), the smallest k with r < cdf_stale_k
+ *   otherwise:                            rx_track_draw's search of cdf_score (uniform when F == 0)
+ * With stale_mix == 0 it is rx_track_draw on cdf_score bit for bit (cdf_stale may
+ * then be null).
+ *
+ * All pointers are DEVICE pointers; the *_host twins take the same arguments as
+ * HOST pointers, ignore `stream`, make no HIP call and give the same bits.  No
+ * host wait and no allocation: a stream capture records every one of them.
+ *
+ * Checked before any HIP call (RX_EINVAL, the message names the field): null
+ * pointers among the ones the entry point reads, n_tracks <= 0, T <= 0, n <= 0,
+ * kind not 0 or 1, alpha outside (0, 1] or NaN, power outside 0..10, now < 0,
+ * mix or stale_mix outside [0, 1] or NaN, mix + stale_mix > 1. */
+typedef struct rx_track_learn_io {
+  int32_t n_tracks;        /* track slots, > 0 */
+  int32_t kind;            /* 0 = |A|, 1 = max(A, 0) (tally only) */
+  const int32_t* track;    /* [N] the slot of env e, env order: rx_state.track (tally only) */
+  int64_t* learn;          /* [n_tracks][2] = (samples, mag_q) */
+  double* score;           /* [n_tracks] */
+  int32_t* seen;           /* [n_tracks] update index of the last fold with samples; -1 = never */
+  int32_t* rank;           /* [n_tracks] 1-based */
+  int64_t* cdf_score;      /* [n_tracks] */
+  int64_t* cdf_stale;      /* [n_tracks] */
+  int32_t* track_of_env;   /* [N] out (draw only) */
+  uint64_t seed;
+} rx_track_learn_io;
+int rx_track_learn_tally(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv, void* stream);
+int rx_track_learn_tally_host(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv, void* stream);
+int rx_track_learn_fold(const rx_track_learn_io* lt, int32_t update, double alpha, void* stream);
+int rx_track_learn_fold_host(const rx_track_learn_io* lt, int32_t update, double alpha, void* stream);
+int rx_track_learn_tables(const rx_track_learn_io* lt, int32_t power, int32_t now, void* stream);
+int rx_track_learn_tables_host(const rx_track_learn_io* lt, int32_t power, int32_t now, void* stream);
+int rx_track_learn_draw(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix, double stale_mix,
+                        void* stream);
+int rx_track_learn_draw_host(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix,
+                             double stale_mix, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

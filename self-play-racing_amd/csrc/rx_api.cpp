@@ -2461,4 +2461,126 @@ int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, c
   return RX_OK;
 }
 
+// ABI v25, additive: the curriculum's replay scores (csrc/rx_track_replay.h).  The checks of the four
+// entry points and their host twins, before any HIP call.
+static int learn_null(const char* fn, const char* name) { return fail(RX_EINVAL, "%s: null %s", fn, name); }
+
+static int learn_io(const char* fn, const rx_track_learn_io* lt) {
+  if (!lt) return fail(RX_EINVAL, "%s: null track learn io", fn);
+  if (lt->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, lt->n_tracks);
+  return RX_OK;
+}
+
+static int learn_tally_args(const char* fn, const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv) {
+  const int rc = learn_io(fn, lt);
+  if (rc) return rc;
+  if (lt->kind != 0 && lt->kind != 1) return fail(RX_EINVAL, "%s: kind=%d must be 0 or 1", fn, lt->kind);
+  if (!lt->track) return learn_null(fn, "track");
+  if (!lt->learn) return learn_null(fn, "learn");
+  if (T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, T);
+  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
+  if (!adv) return learn_null(fn, "adv");
+  return RX_OK;
+}
+
+static int learn_fold_args(const char* fn, const rx_track_learn_io* lt, double alpha) {
+  const int rc = learn_io(fn, lt);
+  if (rc) return rc;
+  if (!lt->learn) return learn_null(fn, "learn");
+  if (!lt->score) return learn_null(fn, "score");
+  if (!lt->seen) return learn_null(fn, "seen");
+  if (!(alpha > 0.0 && alpha <= 1.0)) return fail(RX_EINVAL, "%s: alpha=%g outside (0, 1]", fn, alpha);
+  return RX_OK;
+}
+
+static int learn_tables_args(const char* fn, const rx_track_learn_io* lt, int32_t power, int32_t now) {
+  const int rc = learn_io(fn, lt);
+  if (rc) return rc;
+  if (!lt->score) return learn_null(fn, "score");
+  if (!lt->seen) return learn_null(fn, "seen");
+  if (!lt->rank) return learn_null(fn, "rank");
+  if (!lt->cdf_score) return learn_null(fn, "cdf_score");
+  if (!lt->cdf_stale) return learn_null(fn, "cdf_stale");
+  if (power < 0 || power > 10) return fail(RX_EINVAL, "%s: power=%d outside 0..10", fn, power);
+  if (now < 0) return fail(RX_EINVAL, "%s: now=%d must be >= 0", fn, now);
+  return RX_OK;
+}
+
+static int learn_draw_args(const char* fn, const rx_track_learn_io* lt, int64_t n, double mix, double stale_mix) {
+  const int rc = learn_io(fn, lt);
+  if (rc) return rc;
+  if (!lt->cdf_score) return learn_null(fn, "cdf_score");
+  if (!lt->track_of_env) return learn_null(fn, "track_of_env");
+  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
+  if (!(mix >= 0.0 && mix <= 1.0)) return fail(RX_EINVAL, "%s: mix=%g outside [0, 1]", fn, mix);
+  if (!(stale_mix >= 0.0 && stale_mix <= 1.0))
+    return fail(RX_EINVAL, "%s: stale_mix=%g outside [0, 1]", fn, stale_mix);
+  if (!(mix + stale_mix <= 1.0))
+    return fail(RX_EINVAL, "%s: mix + stale_mix = %g + %g above 1", fn, mix, stale_mix);
+  if (stale_mix > 0.0 && !lt->cdf_stale) return learn_null(fn, "cdf_stale");
+  return RX_OK;
+}
+
+int rx_track_learn_tally(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv, void* stream) {
+  int rc = learn_tally_args("rx_track_learn_tally", lt, T, n, adv);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_learn_tally(lt, T, n, adv, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_learn_tally: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_learn_tally_host(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv, void* /*stream*/) {
+  const int rc = learn_tally_args("rx_track_learn_tally_host", lt, T, n, adv);
+  if (rc) return rc;
+  rx_host_track_learn_tally(lt, T, n, adv);
+  return RX_OK;
+}
+
+int rx_track_learn_fold(const rx_track_learn_io* lt, int32_t update, double alpha, void* stream) {
+  int rc = learn_fold_args("rx_track_learn_fold", lt, alpha);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_learn_fold(lt, update, alpha, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_learn_fold: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_learn_fold_host(const rx_track_learn_io* lt, int32_t update, double alpha, void* /*stream*/) {
+  const int rc = learn_fold_args("rx_track_learn_fold_host", lt, alpha);
+  if (rc) return rc;
+  rx_host_track_learn_fold(lt, update, alpha);
+  return RX_OK;
+}
+
+int rx_track_learn_tables(const rx_track_learn_io* lt, int32_t power, int32_t now, void* stream) {
+  int rc = learn_tables_args("rx_track_learn_tables", lt, power, now);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_learn_tables(lt, power, now, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_learn_tables: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_learn_tables_host(const rx_track_learn_io* lt, int32_t power, int32_t now, void* /*stream*/) {
+  const int rc = learn_tables_args("rx_track_learn_tables_host", lt, power, now);
+  if (rc) return rc;
+  rx_host_track_learn_tables(lt, power, now);
+  return RX_OK;
+}
+
+int rx_track_learn_draw(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix, double stale_mix,
+                        void* stream) {
+  int rc = learn_draw_args("rx_track_learn_draw", lt, n, mix, stale_mix);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_learn_draw(lt, n, generation, mix, stale_mix, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_learn_draw: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_learn_draw_host(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix,
+                             double stale_mix, void* /*stream*/) {
+  const int rc = learn_draw_args("rx_track_learn_draw_host", lt, n, mix, stale_mix);
+  if (rc) return rc;
+  rx_host_track_learn_draw(lt, n, generation, mix, stale_mix);
+  return RX_OK;
+}
+
 }  // extern "C"

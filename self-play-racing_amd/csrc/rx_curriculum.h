@@ -69,6 +69,16 @@ RX_FN uint64_t rx_tc_weight(const int64_t* t, int score, int power, double prior
   return w > 0.0 ? (uint64_t)w : 0ull;  // a tally with finishes > episodes (never written here) weighs nothing
 }
 
+// the smallest k with r < cdf_k, for r < cdf[n_tracks - 1]: the search ends inside the table
+RX_FN int32_t rx_tc_search(const int64_t* cdf, int32_t n_tracks, uint64_t r) {
+  int32_t lo = 0, hi = n_tracks - 1;
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (r < (uint64_t)cdf[mid]) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
 // the slot of env e at generation g from the inclusive integer table cdf[0 .. n_tracks - 1]
 RX_FN int32_t rx_tc_draw(const int64_t* cdf, int32_t n_tracks, uint64_t seed, uint32_t g, uint32_t e, double mix) {
   const uint64_t h1 = rx_lg_splitmix64(seed ^ rx_lg_splitmix64(((uint64_t)g << 32) ^ (uint64_t)e));
@@ -76,11 +86,5 @@ RX_FN int32_t rx_tc_draw(const int64_t* cdf, int32_t n_tracks, uint64_t seed, ui
   const double u = (double)(h1 >> 11) * 0x1p-53;
   const uint64_t F = (uint64_t)cdf[n_tracks - 1];
   if (F == 0 || u < mix) return (int32_t)rx_tc_mulhi64(h2, (uint64_t)n_tracks);
-  const uint64_t r = rx_tc_mulhi64(h2, F);  // r < F = cdf[n_tracks - 1]: the search ends inside the table
-  int32_t lo = 0, hi = n_tracks - 1;
-  while (lo < hi) {
-    const int32_t mid = lo + ((hi - lo) >> 1);
-    if (r < (uint64_t)cdf[mid]) hi = mid; else lo = mid + 1;
-  }
-  return lo;
+  return rx_tc_search(cdf, n_tracks, rx_tc_mulhi64(h2, F));
 }

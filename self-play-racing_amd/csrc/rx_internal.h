@@ -378,6 +378,20 @@ extern "C" void rx_host_track_tally(const rx_track_io* tc, int64_t n, const floa
                                     const double* info);
 extern "C" void rx_host_track_scores(const rx_track_io* tc, int power, double prior);
 extern "C" void rx_host_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double mix);
+// rx_track_replay.hip: advantages -> per-slot (samples, mag_q); the score fold; rank + the two integer tables;
+// the three-way env -> slot draw (arguments checked by rx_api.cpp)
+extern "C" int rx_launch_track_learn_tally(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
+                                           hipStream_t s);
+extern "C" int rx_launch_track_learn_fold(const rx_track_learn_io* lt, int32_t update, double alpha, hipStream_t s);
+extern "C" int rx_launch_track_learn_tables(const rx_track_learn_io* lt, int32_t power, int32_t now, hipStream_t s);
+extern "C" int rx_launch_track_learn_draw(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix,
+                                          double stale_mix, hipStream_t s);
+// rx_track_replay_host.cpp: the same four as host loops (plain C++, no HIP call)
+extern "C" void rx_host_track_learn_tally(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv);
+extern "C" void rx_host_track_learn_fold(const rx_track_learn_io* lt, int32_t update, double alpha);
+extern "C" void rx_host_track_learn_tables(const rx_track_learn_io* lt, int32_t power, int32_t now);
+extern "C" void rx_host_track_learn_draw(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix,
+                                         double stale_mix);
 extern "C" int rx_launch_adv_stats(const rx_ppo_batch* b, int n_mb, float* stats, double* moments, hipStream_t s);
 extern "C" int rx_adv_chunks(int mb);
 extern "C" int rx_launch_adv_stats_ws(const rx_ppo_batch* b, int n_mb, double* ws, float* stats, double* moments,

@@ -38,7 +38,9 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_league_weights", "rx_league_weights_host", "rx_league_draw", "rx_league_draw_host",
            "rx_league_rollout_steps", "rx_cull_table_sizes", "rx_build_cull_tables", "rx_build_cull_tables_host",
            "rx_upload_tracks_device", "rx_track_tally", "rx_track_tally_host", "rx_track_scores", "rx_track_scores_host",
-           "rx_track_draw", "rx_track_draw_host", "rx_track_rollout_steps")
+           "rx_track_draw", "rx_track_draw_host", "rx_track_rollout_steps", "rx_track_learn_tally",
+           "rx_track_learn_tally_host", "rx_track_learn_fold", "rx_track_learn_fold_host", "rx_track_learn_tables",
+           "rx_track_learn_tables_host", "rx_track_learn_draw", "rx_track_learn_draw_host")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -165,6 +167,17 @@ class RxTrackIO(ctypes.Structure):
                 ("p", _P), ("track_of_env", _P), ("seed", ctypes.c_uint64)]
 
 
+# the curriculum's replay scores (ABI v25, additive): value-loss scores, rank and staleness draws (include/rx.h)
+RX_TRACK_LEARN_W, RX_TRACK_LEARN_MAX_POWER, RX_TRACK_LEARN_CHUNK, RX_TRACK_RANK_TILE = 2, 10, 1024, 1024
+TRACK_LEARN_KINDS = {"value_l1": 0, "value_pos": 1}
+TRACK_LEARN_FIELDS = ("track", "learn", "score", "seen", "rank", "cdf_score", "cdf_stale", "track_of_env")
+
+
+class RxTrackLearnIO(ctypes.Structure):
+    _fields_ = [("n_tracks", ctypes.c_int32), ("kind", ctypes.c_int32)] + [(k, _P) for k in TRACK_LEARN_FIELDS] + \
+               [("seed", ctypes.c_uint64)]
+
+
 # rendering (ABI v25, additive): pixel classes / trail bits, size limits, edge record width (include/rx.h)
 RX_PX_BACKGROUND, RX_PX_TRACK, RX_PX_BORDER, RX_PX_START, RX_PX_TRAIL0, RX_PX_TRAIL1 = 0, 1, 2, 3, 0x10, 0x20
 RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX, RX_RASTER_EDGE_W = 16, 2048, 6
@@ -282,6 +295,12 @@ def load(build_if_missing=True):
         getattr(L, "rx_track_scores" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.c_int32, ctypes.c_double, _P]
         getattr(L, "rx_track_draw" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.c_int64, ctypes.c_uint32,
                                                       ctypes.c_double, _P]
+        lt = ctypes.POINTER(RxTrackLearnIO)
+        getattr(L, "rx_track_learn_tally" + sfx).argtypes = [lt, ctypes.c_int32, ctypes.c_int64, _P, _P]
+        getattr(L, "rx_track_learn_fold" + sfx).argtypes = [lt, ctypes.c_int32, ctypes.c_double, _P]
+        getattr(L, "rx_track_learn_tables" + sfx).argtypes = [lt, ctypes.c_int32, ctypes.c_int32, _P]
+        getattr(L, "rx_track_learn_draw" + sfx).argtypes = [lt, ctypes.c_int64, ctypes.c_uint32, ctypes.c_double,
+                                                            ctypes.c_double, _P]
         getattr(L, "rx_league_weights" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int32, ctypes.c_int32,
                                                          ctypes.c_double, ctypes.c_double, _P]
         getattr(L, "rx_league_draw" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int64, _P, _P, _P]

@@ -270,6 +270,11 @@ class CurriculumPPO(PPO):
         ok = np.nonzero((episodes >= self.min_episodes) & (p >= self.mastery))[0]
         return ok[np.lexsort((ok, -p[ok]))][:budget].astype(np.int64)
 
+    def _draw_tracks(self, generation, retired):
+        """The slot of every env for ``generation`` (device int32 [N]); ``retired``: the slots
+        whose tracks were just replaced.  The one place a subclass changes the draw."""
+        return self.curriculum.draw(generation)
+
     def resample_tracks(self, control_points=None, widths=None):
         """Redraw the envs over the track slots from the tallies.  With no arguments:
         the scores; up to floor(curriculum_refresh * n_tracks) mastered slots are
@@ -304,10 +309,10 @@ class CurriculumPPO(PPO):
             cur.reset_slots(retired)
             cur.scores()  # a fresh slot weighs what an unseen one does
             table = DeviceTrackTable.build(self._cps, self._widths, device=self.device)
-            toe = cur.draw(g).cpu().numpy()
+            toe = self._draw_tracks(g, retired).cpu().numpy()
             next_obs = envs.set_tracks(table, toe)
         else:
-            toe = cur.draw(g).cpu().numpy()
+            toe = self._draw_tracks(g, retired).cpu().numpy()
             next_obs = envs.reassign_tracks(toe)
         self.retired.append([int(k) for k in retired])
         self._graphs = {}

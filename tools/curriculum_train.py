@@ -2,6 +2,7 @@
 
     python tools/curriculum_train.py --envs 4096 --steps 128 --updates 60 --tracks 512 --resample-every 4
     python tools/curriculum_train.py --envs 64 --steps 32 --updates 6 --tracks 8 --resample-every 2 --no-uniform
+    python tools/curriculum_train.py --replay value_l1 --envs 4096 --steps 128 --updates 60 --tracks 512
 
 ``CurriculumPPO`` on a pool of ``--tracks`` distinct tracks (env i starts on slot
 i % tracks): every finished episode is tallied against its slot on the device;
@@ -13,7 +14,10 @@ follows.  Both are evaluated every ``--eval-every`` updates and at the end with
 rx.evaluate's protocol (40 held-out tracks x 5 runs, fused backend); the success
 rates over env-steps, the first evaluation at or above 90 % and the curriculum's
 per-slot table go to ``--out`` as JSON, and the table's most failed slots are
-printed.
+printed.  With ``--replay value_l1`` (or ``value_pos``) the curriculum run is
+``rx.track_replay.ReplayCurriculumPPO``: the redraw follows the value-loss scores
+of the rollouts (rank prioritisation ``--replay-power``, staleness ``--stale-mix``)
+instead of the finish tallies; ``off`` (the default) runs ``CurriculumPPO``.
 """
 import argparse
 import json
@@ -40,6 +44,10 @@ def run(kind, args, evaluator):
                       curriculum_score=args.score, curriculum_refresh=args.refresh, curriculum_mastery=args.mastery,
                       curriculum_min_episodes=args.min_episodes)
     cfg["total_timesteps"] = args.updates * cfg["batch_size"]
+    replay = kind == "curriculum" and args.replay != "off"
+    if replay:
+        cfg.update(replay_kind=args.replay, replay_power=args.replay_power, replay_alpha=args.replay_alpha,
+                   replay_stale_mix=args.stale_mix)
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
@@ -48,6 +56,8 @@ def run(kind, args, evaluator):
     widths = [int(rng.randint(6, 10)) for _ in range(args.tracks)]
     n = args.tracks
     cls = CurriculumPPO if kind == "curriculum" else PPO
+    if replay:
+        from rx.track_replay import ReplayCurriculumPPO as cls
     t = cls(lambda i: RacingEnv(num_sensors=11, track_pool=pool, track_id=i % n, track_width=widths[i % n]), cfg,
             device="cuda")
     info, curve = {"steps": [], "rewards": []}, []
@@ -60,7 +70,7 @@ def run(kind, args, evaluator):
             print(f"[{kind}] update {update + 1}: eval success {s['success_rate']:.3f} crash {s['crash_rate']:.3f}",
                   flush=True)
     first90 = next((c["env_steps"] for c in curve if c["success_rate"] >= 0.9), None)
-    out = {"kind": kind, "eval": curve, "env_steps_to_90": first90, "track_generation": t.envs.track_generation}
+    out = {"kind": kind, "replay": args.replay if kind == "curriculum" else "off", "eval": curve, "env_steps_to_90": first90, "track_generation": t.envs.track_generation}
     if kind == "curriculum":
         from rx.curriculum import format_track_table
         tab = t.track_table()
@@ -87,6 +97,11 @@ def main():
     ap.add_argument("--refresh", type=float, default=0.25)
     ap.add_argument("--mastery", type=float, default=0.8)
     ap.add_argument("--min-episodes", type=int, default=4)
+    ap.add_argument("--replay", choices=("off", "value_l1", "value_pos"), default="off",
+                    help="draw by the rollouts' value-loss scores (rx.track_replay) instead of the finish tallies")
+    ap.add_argument("--replay-power", type=int, default=4, help="rank weight (1 / rank) ** power")
+    ap.add_argument("--replay-alpha", type=float, default=1.0)
+    ap.add_argument("--stale-mix", type=float, default=0.1)
     ap.add_argument("--prec", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--show", type=int, default=20, help="slots of the table to print, the most failed first")
