@@ -150,6 +150,8 @@ struct rx_env {
   DevBuf<double> snap_pose[RX_PAIR_RING];
   DevBuf<int32_t> snap_tasks[RX_PAIR_RING];
   DevBuf<float> obs_shadow;
+  DevBuf<int32_t> snap_rows[RX_CROSS_RING];  // the crossing step's row ids and visiting-order hint (pre-sort)
+  DevBuf<double> snap_hint[RX_CROSS_RING];
   // rx_profile: per recorded launch, [RX_PROF_SLOTS] wave start + [RX_PROF_SLOTS] wave end stamps
   bool prof = false;
   DevBuf<unsigned long long> prof_buf;
@@ -400,6 +402,10 @@ int rx_destroy(rx_env* h) {
     h->snap_tasks[b].release();
   }
   h->obs_shadow.release();
+  for (int b = 0; b < RX_CROSS_RING; ++b) {
+    h->snap_rows[b].release();
+    h->snap_hint[b].release();
+  }
   h->policy_frag.release();
   h->pos_slot.release();
   h->prof_buf.release();
@@ -702,6 +708,12 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
     std::vector<float> z((size_t)N * h->D, 0.0f);
     if ((rc = upload(h->obs_shadow, z.data(), z.size()))) return rc;
   }
+  for (int b = 0; b < RX_CROSS_RING && RX_STEPS_CARRY && RX_STEPS_PAIR && RX_STEPS_CROSS && A == 1 && h->sort_on; ++b) {
+    std::vector<int32_t> r0((size_t)N, 0);
+    std::vector<double> h0((size_t)N, 0.0);
+    if ((rc = upload(h->snap_rows[b], r0.data(), r0.size()))) return rc;
+    if ((rc = upload(h->snap_hint[b], h0.data(), h0.size()))) return rc;
+  }
   if ((rc = upload(h->dyn_waves, dyn.data(), dyn.size()))) return rc;
   if ((rc = upload(h->ray_waves, ray.data(), ray.size()))) return rc;
   h->ray_waves_h = ray;
@@ -847,6 +859,7 @@ static void make_kargs(rx_env* h, const rx_io* io, int mode, const uint8_t* mask
   a.ray_x = a.st.x;  // the ray inputs: the working state (rx_steps' carried schedule: a snapshot)
   a.ray_y = a.st.y;
   a.ray_angle = a.st.angle;
+  a.ray_hint = a.st.progress;  // (a crossing step of rx_steps' paired schedule: the hint snapshot)
   a.sort_base = h->sort_base.p;
   a.sort_shift = h->sort_shift;
   a.box_quadrants = h->cfg.box_quadrants >= 0;
@@ -1255,6 +1268,15 @@ static bool steps_paired(const rx_env* h) {
 // would write the same obs rows (stride 0): the older one writes the handle's shadow rows,
 // so the caller's rows end with the newest step's.  The task buffer of the handle and the
 // bookkeeping are kept as steps_carry keeps them.
+// RX_STEPS_CROSS (DESIGN.md §3 "The crossing step"): a re-sort step k + 1 that a step follows
+// in the call gives up its own launch.  REWARD k + 1 is the KIN-less second sub-step of D_k's
+// launch, and step k + 1 stays in the queue ACROSS the sort: the next window's first launch
+// casts it as the older ray step, from its ring slots (which the sort leaves alone) and from
+// the snapshots of perm and progress that REWARD k + 1 stored (which the sort rewrites):
+//   sort k_kin1(8) [D8 D9 | rays 7 8] [D10 D11 | rays 9 10] [D12 D13 | rays 11 12]
+//   [D14 R15 | rays 13 14] sort k_kin1(16) [D16 D17 | rays 15 16] ...
+// A re-sort step that is the call's last keeps the order above, so the queue is still empty
+// at the end of the call.
 static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32_t K, hipStream_t s) {
   const size_t N = (size_t)h->cfg.n_envs;
   rx_kargs a{};
@@ -1266,8 +1288,11 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
   struct ray_step {
     int32_t k;
     const int32_t* tasks;
+    const int32_t* rows;  // position -> env and the visiting-order hint: the handle's perm and
+    const double* hint;   // progress, or -- a step that crossed a sort -- their snapshots
   } pend[2];
   int n_pend = 0;
+  int cb = 0;  // the crossing snapshots' ring, by the call's crossings (as tb)
   struct kin_out {
     double* snap;
     int32_t* tasks_out;
@@ -1291,7 +1316,7 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
       }
       ++h->task_calls;
     }
-    pend[n_pend++] = ray_step{k, ray_tasks};
+    pend[n_pend++] = ray_step{k, ray_tasks, a.perm, a.st.progress};
     return o;
   };
   auto kin1 = [&](int32_t k) {
@@ -1310,6 +1335,8 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
       p.ray_pose[r] = h->snap_pose[pend[r].k % RX_PAIR_RING].p;
       p.ray_tasks[r] = pend[r].tasks;
       p.ray_obs[r] = io_at(io, st, pend[r].k).obs;
+      p.ray_rows[r] = pend[r].rows;
+      p.ray_hint[r] = pend[r].hint;
       reads_main = reads_main || (tasks_main && pend[r].tasks == tasks_main);
     }
     if (n_pend == 2 && p.ray_obs[0] == p.ray_obs[1]) p.ray_obs[0] = h->obs_shadow.p;
@@ -1321,6 +1348,23 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
   auto resort_at = [&](int32_t ahead) {
     return sorting_envs && ((h->dyn_calls + ahead) % h->cfg.sort_interval) == 0;
   };
+  // will the next KIN part sort its ray tasks (kin_args' turn)?
+  auto kin_sorts = [&] { return h->tasks_stale || (h->task_calls % (uint64_t)h->task_sort) == 0; };
+  // as launch(): the REWARD half of the re-sort step writes the keys and counts the bins
+  auto keys_args = [&]() -> int {
+    if (h->sort_hist_done) RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sort_bins * sizeof(uint32_t), s));
+    a.sort_keys = h->keys_in.p;
+    a.sort_hist = h->sort_hist.p;
+    a.sort_off = h->keys_off.p;
+    return RX_OK;
+  };
+  auto sort_now = [&] {
+    h->sort_hist_done = false;
+    h->tasks_stale = true;  // the re-sort moves envs between blocks
+    rx_state work = h->work, tmp = h->work_tmp;
+    return rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, 1, h->sort_hist.p, h->sort_cursor.p, h->sort_bins,
+                        h->perm[0].p, h->perm[1].p, &work, &tmp, s, 1);
+  };
   if ((rc = kin1(0)) != 0) return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
   for (int32_t k = 0; k < K;) {
     const bool resort = resort_at(0);
@@ -1330,30 +1374,45 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
     a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
     a.snap_x = a.snap_y = a.snap_angle = nullptr;
     a.tasks_out = nullptr, a.tasks_snap = nullptr;
+    a.rows_snap = nullptr, a.hint_snap = nullptr;
     if (!resort && k + 1 < K) {  // D_k, and D_k+1 unless step k + 1 has no KIN behind it
       const int32_t d = (k + 2 < K && !resort_at(1)) ? 2 : 1;
+      // Step k + 1 is due for the re-sort and a step follows it in the call: it CROSSES the
+      // sort.  Its REWARD runs here as the second sub-step, without a KIN (it writes the keys
+      // and the snapshots), and its rays stay pending across the sort.  Its task row must then
+      // be a row of the ring: the k_kin1 after the sort rewrites the handle's buffer.  Where it
+      // would be the handle's (a call that begins between two task sorts and has not sorted
+      // yet), the window does not cross and step k + 1 keeps its own launch.
+      const bool cross = RX_STEPS_CROSS && k + 2 < K && resort_at(1) && h->snap_rows[cb].p && h->snap_hint[cb].p &&
+                         (!tasks_main || ray_tasks != tasks_main || kin_sorts());
       const bool reads_main = take_rays(p);
-      p.n_sub = d;
+      p.n_sub = cross ? 2 : d;
       for (int32_t j = 0; j < d; ++j) {
         const kin_out o = kin_args(k + j + 1, reads_main);
         p.io[j + 1] = io_at(io, st, k + j + 1);
         p.kin[j] = 1;
         p.snap[j] = o.snap, p.tasks_out[j] = o.tasks_out, p.tasks_snap[j] = o.tasks_snap;
       }
+      if (cross) {
+        if ((rc = keys_args()) != 0) return rc;
+        a.rows_snap = h->snap_rows[cb].p;
+        a.hint_snap = h->snap_hint[cb].p;
+      }
       if ((rc = rx_launch_step2_pair(&a, &p, s)) != 0)
         return fail(RX_EHIP, "k_step2_pair launch failed: %s", hipGetErrorString((hipError_t)rc));
-      if (sorting_envs) h->dyn_calls += (uint64_t)d;
-      k += d;
+      if (sorting_envs) h->dyn_calls += (uint64_t)p.n_sub;
+      k += p.n_sub;
+      if (cross) {  // the queue holds step k - 1 alone: from here on it reads the snapshots
+        pend[0].rows = a.rows_snap, pend[0].hint = a.hint_snap;
+        cb = (cb + 1) % RX_CROSS_RING;
+        if ((rc = sort_now()) != 0) return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
+        if ((rc = kin1(k)) != 0) return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
+      }
       continue;
     }
     if (sorting_envs) ++h->dyn_calls;
-    if (resort) {  // as launch(): the REWARD half writes the keys and counts the bins
-      if (h->sort_hist_done) RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sort_bins * sizeof(uint32_t), s));
-      a.sort_keys = h->keys_in.p;
-      a.sort_hist = h->sort_hist.p;
-      a.sort_off = h->keys_off.p;
-    }
-    if (n_pend == 1) {  // only its own rays are pending: the plain k_step2
+    if (resort && (rc = keys_args()) != 0) return rc;
+    if (n_pend == 1 && pend[0].rows == a.perm) {  // only its own rays are pending: the plain k_step2
       a.ray_x = h->snap_pose[pend[0].k % RX_PAIR_RING].p;
       a.ray_y = a.ray_x + N;
       a.ray_angle = a.ray_x + 2 * N;
@@ -1367,14 +1426,8 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
       if ((rc = rx_launch_step2_pair(&a, &p, s)) != 0)
         return fail(RX_EHIP, "k_step2_pair launch failed: %s", hipGetErrorString((hipError_t)rc));
     }
-    if (resort) {
-      h->sort_hist_done = false;
-      h->tasks_stale = true;  // the re-sort moves envs between blocks
-      rx_state work = h->work, tmp = h->work_tmp;
-      if ((rc = rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, 1, h->sort_hist.p, h->sort_cursor.p,
-                             h->sort_bins, h->perm[0].p, h->perm[1].p, &work, &tmp, s, 1)) != 0)
-        return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
-    }
+    if (resort && (rc = sort_now()) != 0)
+      return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
     if (++k < K && (rc = kin1(k)) != 0)
       return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
   }

@@ -147,6 +147,11 @@ struct rx_kargs {
   uint32_t* sort_keys;        // [N] k_dyn writes the sort bin (sort_base[slot] + (waypoint >> sort_shift)) at its perm position, or nullptr
   uint32_t* sort_hist;        // with sort_keys: the REWARD half also counts the bins (the re-sort then skips k_sort_hist), or nullptr
   uint32_t* sort_off;         // with sort_hist: [N] the position's rank within its bin (the count atomic's return + lane rank)
+  // with sort_keys, k_step2_pair only (rx_steps' crossing step): the REWARD half also stores the
+  // position's env id and new progress -- the row ids and the visiting-order hint that the step's
+  // ray waves read AFTER the re-sort has rewritten perm and moved progress; nullptr = no snapshot
+  int32_t* rows_snap;         // [N]
+  double* hint_snap;          // [N]
   const int32_t* sort_base;   // [n_tracks] first sort bin of each slot (ascending with the slot id)
   int32_t sort_shift;         // waypoints per sort bin = 1 << sort_shift
   // ray_order 2: k_dyn writes the direction-sorted (agent, ray) task ids of
@@ -197,6 +202,9 @@ struct rx_kargs {
   const double* ray_x;
   const double* ray_y;
   const double* ray_angle;
+  // the culled raycast's visiting-order hint, [N * A] by position: st.progress in every launch
+  // but the paired one that casts a crossing step (below), where it is the hint snapshot
+  const double* ray_hint;
   // rx_steps' carried schedule: KIN also stores its stepped pose here (the snapshot its
   // step's ray waves read), and its sorted task row to tasks_snap; nullptr = no snapshot
   double* snap_x;
@@ -223,6 +231,16 @@ struct rx_kargs {
 #endif
 #define RX_PAIR_RING 4  // pose / task-row snapshots: a launch writes at most two and reads at most two others
 
+// The paired schedule's crossing step (DESIGN.md §3 "The crossing step"): the REWARD of a step
+// whose re-sort is due runs as the second sub-step of the launch before it, KIN-less, and its
+// rays are cast AFTER the sort, in the next window's first launch, from pre-sort snapshots of
+// the row ids and the visiting-order hint -- the re-sort step's own launch leaves the window.
+// 0 = the re-sort step keeps its own launch (REWARD and rays before the sort).
+#ifndef RX_STEPS_CROSS
+#define RX_STEPS_CROSS 1
+#endif
+#define RX_CROSS_RING 2  // row-id / hint snapshots: a launch stores one and may read the other
+
 // What one k_step2_pair launch runs beside rx_kargs (whose io, io_next, ray_*, snap_*, tasks,
 // tasks_out and tasks_snap it ignores).
 struct rx_pair {
@@ -238,14 +256,21 @@ struct rx_pair {
   const double* ray_pose[2];
   const int32_t* ray_tasks[2];
   float* ray_obs[2];
+  // ... and its row ids (position -> env: the obs row) and visiting-order hint: rx_kargs' perm
+  // and st.progress, or -- a crossing step, cast after the re-sort -- their pre-sort snapshots
+  const int32_t* ray_rows[2];
+  const double* ray_hint[2];
   int64_t n_envs;
 };
 
 extern "C" int rx_launch_step(const rx_kargs* a, int n_agents, int phases, hipStream_t s);
 // k_step2_pair (single-agent, one lane per env).  Refuses (hipErrorInvalidValue) a launch that
-// writes a snapshot or sorts into a row that one of its own ray steps reads, and two ray
-// steps that write the same obs rows.
+// writes a snapshot or sorts into a row that one of its own ray steps reads (the row-id and
+// hint snapshots of its key-writing REWARD included), and two ray steps that write the same
+// obs rows.
 extern "C" int rx_launch_step2_pair(const rx_kargs* a, const rx_pair* p, hipStream_t s);
+// sizes and field offsets of rx_kargs / rx_pair for a caller that fills them as bytes (see the definition)
+extern "C" int64_t rx_pair_layout(int what);
 // split step (STEP mode, next-step / no autoreset): k_kin1 / k_kin2, then k_step2<A>
 #define RX_SPLIT_KIN 0
 #define RX_SPLIT_REWARD 1

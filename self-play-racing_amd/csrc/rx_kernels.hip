@@ -878,6 +878,12 @@ __device__ __forceinline__ void dyn1_env(const rx_kargs& a, int wave, double* an
     o[3] = (float)last_steering;
   }
   if (!KIN) write_sort_key(a, p, k, c.progress, W);
+  if constexpr (REW) {  // a crossing step: what its ray waves read of this position after the re-sort
+    if (a.sort_keys && a.rows_snap) {
+      a.rows_snap[p] = e;
+      stc(a.hint_snap + p, c.progress);
+    }
+  }
   if (!REW) {
     ang_out[0] = c.angle;
     e_out = p;  // the ray tasks name the position (k_rays reads the state there, writes obs row perm[p])
@@ -1988,7 +1994,7 @@ __device__ __forceinline__ void rays_wave(const rx_kargs& a, const rx_wave we, c
     const float csf = (float)cs, snf = (float)sn;
     const rx_f2 id2 = {1.0f / csf, 1.0f / snf};
     // visit chunks outward from the wave's first car
-    int w0 = (int)(ldc(a.st.progress + i) * (double)W + 0.5);
+    int w0 = (int)(ldc(a.ray_hint + i) * (double)W + 0.5);  // (the order of the visits only, never the minimum)
     w0 = w0 < 0 ? 0 : (w0 >= W ? W - 1 : w0);
     const int c0 = uni<LV>(w0 / G);
     // direction quadrant (sign bits of the f32 direction, as id2's signs): a
@@ -2294,8 +2300,10 @@ __global__ __launch_bounds__(64, LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW) void k_s
 // dyn1_env / sort_block_tasks calls (one copy of the code), every part reading what the
 // part before stored for its own lane.  The ray workgroups cast n_rays earlier steps, the
 // older one first: ray workgroup r is record r % n_ray_waves of step r / n_ray_waves, on
-// that step's pose snapshot, task row and obs rows.  Their KIN parts ran in an EARLIER
-// launch, so no wave of this launch waits on another.
+// that step's pose snapshot, task row, obs rows, row ids and hint.  Their KIN parts ran in an
+// EARLIER launch, so no wave of this launch waits on another.  A step whose re-sort is due
+// can be the second sub-step without a KIN (it writes the keys, and the row-id and hint
+// snapshots its rays are cast from after the sort; DESIGN.md §3 "The crossing step").
 // Scheduling knobs, same-session A/B at 65,536 envs (profiles/steps_pair/): issue priority of
 // the REWARD workgroups 0 / 1 / 2 / 3 = 998 / 1,047 / 1,045 / 1,045 M env-steps/s (parent
 // 1,012 M); the two steps' ray records interleaved in octets 1,080 M against 1,085 M for the
@@ -2397,6 +2405,8 @@ __device__ __forceinline__ void step2_pair_body(const rx_pair_args& ka) {
     ar.ray_angle = ar.ray_x + 2 * pp.n_envs;
     ar.tasks = newer ? pp.ray_tasks[1] : pp.ray_tasks[0];
     ar.io.obs = newer ? pp.ray_obs[1] : pp.ray_obs[0];
+    ar.perm = newer ? pp.ray_rows[1] : pp.ray_rows[0];  // a crossing step: the pre-sort snapshots
+    ar.ray_hint = newer ? pp.ray_hint[1] : pp.ray_hint[0];
     rays_dispatch<1, LPR, LV, LPR == 4>(ar, rec);
   }
 }
@@ -2843,11 +2853,30 @@ extern "C" int rx_launch_step2_carry(const rx_kargs* a, hipStream_t s) {
 // The paired k_step2: n_rw REWARD workgroups, then n_rays copies of the ray table (n_ray_waves
 // is a multiple of 8, so both copies keep the group -> XCD placement); the sort's LDS as the
 // carrying launch sizes it.  Checked here, on the host: no KIN part of the launch stores a
-// pose snapshot or sorts a task row that one of the launch's ray steps reads, and two ray
-// steps never write the same obs rows.
+// pose snapshot or sorts a task row that one of the launch's ray steps reads, two ray
+// steps never write the same obs rows, and no ray step reads a row-id or hint snapshot that
+// the launch's key-writing REWARD stores (those are its OWN step's, cast by a later launch).
+// rx_pair_layout: sizes and offsets for a caller that fills the two structs as bytes (the
+// refusal test): 0 / 1-3 = sizeof rx_kargs / its sort_keys, rows_snap, hint_snap; 4 / 5-9 =
+// sizeof rx_pair / its n_sub, n_rays, ray_obs, ray_rows, ray_hint; else -1.
+extern "C" int64_t rx_pair_layout(int what) {
+  const size_t v[10] = {sizeof(rx_kargs),           offsetof(rx_kargs, sort_keys), offsetof(rx_kargs, rows_snap),
+                        offsetof(rx_kargs, hint_snap), sizeof(rx_pair),            offsetof(rx_pair, n_sub),
+                        offsetof(rx_pair, n_rays),  offsetof(rx_pair, ray_obs),    offsetof(rx_pair, ray_rows),
+                        offsetof(rx_pair, ray_hint)};
+  return what >= 0 && what < 10 ? (int64_t)v[what] : -1;
+}
+
 extern "C" int rx_launch_step2_pair(const rx_kargs* a, const rx_pair* p, hipStream_t s) {
   if (p->n_sub < 1 || p->n_sub > 2 || p->n_rays < 1 || p->n_rays > 2) return (int)hipErrorInvalidValue;
   if (p->n_rays == 2 && p->ray_obs[0] == p->ray_obs[1]) return (int)hipErrorInvalidValue;
+  for (int r = 0; r < p->n_rays; ++r) {
+    if (!p->ray_rows[r] || !p->ray_hint[r]) return (int)hipErrorInvalidValue;
+    // the key-writing REWARD stores the snapshots of ITS step, whose rays a later launch casts
+    if (a->sort_keys && a->rows_snap && (p->ray_rows[r] == a->rows_snap || p->ray_hint[r] == a->hint_snap))
+      return (int)hipErrorInvalidValue;
+  }
+  if (a->sort_keys && a->rows_snap && !a->hint_snap) return (int)hipErrorInvalidValue;
   bool sorting = false;
   for (int j = 0; j < p->n_sub; ++j) {
     if (!p->kin[j]) continue;
