@@ -530,7 +530,11 @@ int rx_adam_clip_step(const rx_adam_config* cfg, float* params, float* grads, fl
  * FP32 = v_mfma_f32_16x16x4_f32, exact float32 products (an fmaf chain);
  * BF16 = v_mfma_f32_16x16x32_bf16: weights / activations / gradients rounded to
  * bf16 as matrix operands, float32 accumulation, float32 everywhere else
- * (BASELINE.json configs[1], "PPO bf16"). */
+ * (BASELINE.json configs[1], "PPO bf16").  Biases are never rounded; a bias
+ * gradient is the sum of the ROUNDED operand of its layer's weight gradient
+ * (db = sum over rows of bf16(dZ), through a ones column of the same MFMA).
+ * DESIGN.md §4, "The bf16 contract", lists every rounded operand;
+ * tests/bf16_ref.py restates them in float64. */
 #define RX_PREC_FP32 0
 #define RX_PREC_BF16 1
 typedef struct rx_ppo_batch {
