@@ -1137,6 +1137,64 @@ int rx_track_learn_draw(const rx_track_learn_io* lt, int64_t n, uint32_t generat
 int rx_track_learn_draw_host(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix,
                              double stale_mix, void* stream);
 
+/* ABI v25, additive: TRACK EVOLUTION -- what fills the track slots the curriculum
+ * retires, written by a kernel into a device-resident control-point buffer
+ * (rx.track_evolve): a fresh track of the host generator's distribution, or a small
+ * edit of a track the replay scores still rank high (ACCEL, Parker-Holder et al.
+ * 2022).  Handle-free, as rx_build_tracks, which takes the new buffer as it is.  The
+ * arithmetic lives in csrc/rx_track_evolve.h, shared by the kernels
+ * (csrc/rx_track_evolve.hip) and the *_host twins; the rules are written out there
+ * and in DESIGN.md §4.  Floating point is float64, every operation separately
+ * rounded; the only transcendental is rx_sincos.
+ *
+ * The hash stream of spawned slot k at `generation` g is
+ *   h0 = splitmix64(seed ^ splitmix64(((uint64)g << 32) ^ k)),  h_{i+1} = splitmix64(h_i)
+ * and its first draw decides the kind: an EDIT (1) when u < edit_frac and
+ * cdf_score[n_tracks - 1] > 0, else FRESH (0).
+ *
+ * rx_track_evolve_plan(generation, edit_frac): for j < n_spawn,
+ *   plan[j] = (kind, parent or -1, P, 0)
+ * with parent drawn from cdf_score (rx_track_learn_tables' table as it stands) and P
+ * the parent's point count, or the 10..14 a fresh track draws.  Reads slots, cp_off,
+ * cdf_score; writes plan.  The caller downloads the plan (16 bytes per spawned slot)
+ * and forms the new offsets from its P column.
+ *
+ * rx_track_evolve(generation): slot k of the new pool, for every k < n_tracks: a slot
+ * not in `slots` is copied (points and width, bit for bit) from cp_off / cp / width to
+ * its place in cp_off_new / cp_new / width_new; a spawned slot is written there by its
+ * plan row, and plan[j][3] = the edits applied.  A slot whose span in cp_off_new is
+ * not the P its rule gives is not written, and its width_new becomes NaN (a bad track
+ * to rx_build_tracks): nothing is ever written outside [cp_off_new[k], cp_off_new[k+1]).
+ * Reads slots, cp_off, cp, width, plan, cp_off_new; writes cp_new, width_new, plan[.][3].
+ * cp_new and width_new must not overlap cp and width.
+ *
+ * All pointers are DEVICE pointers, the offsets included; the *_host twins take the
+ * same arguments as HOST pointers, ignore `stream`, make no HIP call and give the same
+ * bits.  No host wait and no allocation.  With n_spawn == 0 the plan call does nothing
+ * and the evolve call copies the pool (slots and plan may then be null).
+ *
+ * Checked before any HIP call (RX_EINVAL, the message names the field): a null io,
+ * n_tracks <= 0, n_spawn outside 0..n_tracks, null pointers among the ones the entry
+ * point reads, edit_frac outside [0, 1] or NaN. */
+typedef struct rx_track_evolve_io {
+  int32_t n_tracks;            /* slots of the pool, > 0 */
+  int32_t n_spawn;             /* slots to replace, 0..n_tracks */
+  const int32_t* slots;        /* [n_spawn] ascending, distinct */
+  const int32_t* cp_off;       /* [n_tracks + 1] the pool as it stands: offsets in points */
+  const double* cp;            /* [cp_off[n_tracks]][2] */
+  const double* width;         /* [n_tracks] */
+  const int64_t* cdf_score;    /* [n_tracks] rx_track_learn_tables' rank table (plan only) */
+  int32_t* plan;               /* [n_spawn][4] = (kind, parent or -1, P, edits applied) */
+  const int32_t* cp_off_new;   /* [n_tracks + 1] (evolve only) */
+  double* cp_new;              /* [cp_off_new[n_tracks]][2] out (evolve only) */
+  double* width_new;           /* [n_tracks] out (evolve only) */
+  uint64_t seed;
+} rx_track_evolve_io;
+int rx_track_evolve_plan(const rx_track_evolve_io* ev, uint32_t generation, double edit_frac, void* stream);
+int rx_track_evolve_plan_host(const rx_track_evolve_io* ev, uint32_t generation, double edit_frac, void* stream);
+int rx_track_evolve(const rx_track_evolve_io* ev, uint32_t generation, void* stream);
+int rx_track_evolve_host(const rx_track_evolve_io* ev, uint32_t generation, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2636,4 +2636,72 @@ int rx_track_learn_draw_host(const rx_track_learn_io* lt, int64_t n, uint32_t ge
   return RX_OK;
 }
 
+// ABI v25, additive: track evolution (csrc/rx_track_evolve.h).  The checks of the two entry points and
+// their host twins, before any HIP call.
+static int evolve_null(const char* fn, const char* name) { return fail(RX_EINVAL, "%s: null %s", fn, name); }
+
+static int evolve_io(const char* fn, const rx_track_evolve_io* ev) {
+  if (!ev) return fail(RX_EINVAL, "%s: null track evolve io", fn);
+  if (ev->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, ev->n_tracks);
+  if (ev->n_spawn < 0 || ev->n_spawn > ev->n_tracks)
+    return fail(RX_EINVAL, "%s: n_spawn=%d outside 0..n_tracks=%d", fn, ev->n_spawn, ev->n_tracks);
+  if (ev->n_spawn > 0) {
+    if (!ev->slots) return evolve_null(fn, "slots");
+    if (!ev->plan) return evolve_null(fn, "plan");
+  }
+  if (!ev->cp_off) return evolve_null(fn, "cp_off");
+  return RX_OK;
+}
+
+static int evolve_plan_args(const char* fn, const rx_track_evolve_io* ev, double edit_frac) {
+  const int rc = evolve_io(fn, ev);
+  if (rc) return rc;
+  if (!ev->cdf_score) return evolve_null(fn, "cdf_score");
+  if (!(edit_frac >= 0.0 && edit_frac <= 1.0))
+    return fail(RX_EINVAL, "%s: edit_frac=%g outside [0, 1]", fn, edit_frac);
+  return RX_OK;
+}
+
+static int evolve_args(const char* fn, const rx_track_evolve_io* ev) {
+  const int rc = evolve_io(fn, ev);
+  if (rc) return rc;
+  if (!ev->cp) return evolve_null(fn, "cp");
+  if (!ev->width) return evolve_null(fn, "width");
+  if (!ev->cp_off_new) return evolve_null(fn, "cp_off_new");
+  if (!ev->cp_new) return evolve_null(fn, "cp_new");
+  if (!ev->width_new) return evolve_null(fn, "width_new");
+  return RX_OK;
+}
+
+int rx_track_evolve_plan(const rx_track_evolve_io* ev, uint32_t generation, double edit_frac, void* stream) {
+  int rc = evolve_plan_args("rx_track_evolve_plan", ev, edit_frac);
+  if (rc) return rc;
+  if (ev->n_spawn == 0) return RX_OK;
+  if ((rc = rx_launch_track_evolve_plan(ev, generation, edit_frac, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_evolve_plan: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_evolve_plan_host(const rx_track_evolve_io* ev, uint32_t generation, double edit_frac, void* /*stream*/) {
+  const int rc = evolve_plan_args("rx_track_evolve_plan_host", ev, edit_frac);
+  if (rc) return rc;
+  rx_host_track_evolve_plan(ev, generation, edit_frac);
+  return RX_OK;
+}
+
+int rx_track_evolve(const rx_track_evolve_io* ev, uint32_t generation, void* stream) {
+  int rc = evolve_args("rx_track_evolve", ev);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_evolve(ev, generation, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_evolve: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_evolve_host(const rx_track_evolve_io* ev, uint32_t generation, void* /*stream*/) {
+  const int rc = evolve_args("rx_track_evolve_host", ev);
+  if (rc) return rc;
+  rx_host_track_evolve(ev, generation);
+  return RX_OK;
+}
+
 }  // extern "C"

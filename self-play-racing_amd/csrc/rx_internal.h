@@ -417,6 +417,13 @@ extern "C" void rx_host_track_learn_fold(const rx_track_learn_io* lt, int32_t up
 extern "C" void rx_host_track_learn_tables(const rx_track_learn_io* lt, int32_t power, int32_t now);
 extern "C" void rx_host_track_learn_draw(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix,
                                          double stale_mix);
+// rx_track_evolve.hip: the plan of the spawned slots; the new control-point buffer (arguments checked by rx_api.cpp)
+extern "C" int rx_launch_track_evolve_plan(const rx_track_evolve_io* ev, uint32_t generation, double edit_frac,
+                                           hipStream_t s);
+extern "C" int rx_launch_track_evolve(const rx_track_evolve_io* ev, uint32_t generation, hipStream_t s);
+// rx_track_evolve_host.cpp: the same two as host loops (plain C++, no HIP call)
+extern "C" void rx_host_track_evolve_plan(const rx_track_evolve_io* ev, uint32_t generation, double edit_frac);
+extern "C" void rx_host_track_evolve(const rx_track_evolve_io* ev, uint32_t generation);
 extern "C" int rx_launch_adv_stats(const rx_ppo_batch* b, int n_mb, float* stats, double* moments, hipStream_t s);
 extern "C" int rx_adv_chunks(int mb);
 extern "C" int rx_launch_adv_stats_ws(const rx_ppo_batch* b, int n_mb, double* ws, float* stats, double* moments,

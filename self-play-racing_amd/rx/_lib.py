@@ -40,7 +40,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_upload_tracks_device", "rx_track_tally", "rx_track_tally_host", "rx_track_scores", "rx_track_scores_host",
            "rx_track_draw", "rx_track_draw_host", "rx_track_rollout_steps", "rx_track_learn_tally",
            "rx_track_learn_tally_host", "rx_track_learn_fold", "rx_track_learn_fold_host", "rx_track_learn_tables",
-           "rx_track_learn_tables_host", "rx_track_learn_draw", "rx_track_learn_draw_host")
+           "rx_track_learn_tables_host", "rx_track_learn_draw", "rx_track_learn_draw_host", "rx_track_evolve_plan",
+           "rx_track_evolve_plan_host", "rx_track_evolve", "rx_track_evolve_host")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -178,6 +179,16 @@ class RxTrackLearnIO(ctypes.Structure):
                [("seed", ctypes.c_uint64)]
 
 
+# track evolution (ABI v25, additive): fresh tracks and edited children written on the device (include/rx.h)
+RX_TRACK_EVOLVE_W, RX_TRACK_EVOLVE_FRESH, RX_TRACK_EVOLVE_EDIT = 4, 0, 1
+TRACK_EVOLVE_FIELDS = ("slots", "cp_off", "cp", "width", "cdf_score", "plan", "cp_off_new", "cp_new", "width_new")
+
+
+class RxTrackEvolveIO(ctypes.Structure):
+    _fields_ = [("n_tracks", ctypes.c_int32), ("n_spawn", ctypes.c_int32)] + [(k, _P) for k in TRACK_EVOLVE_FIELDS] + \
+               [("seed", ctypes.c_uint64)]
+
+
 # rendering (ABI v25, additive): pixel classes / trail bits, size limits, edge record width (include/rx.h)
 RX_PX_BACKGROUND, RX_PX_TRACK, RX_PX_BORDER, RX_PX_START, RX_PX_TRAIL0, RX_PX_TRAIL1 = 0, 1, 2, 3, 0x10, 0x20
 RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX, RX_RASTER_EDGE_W = 16, 2048, 6
@@ -301,6 +312,9 @@ def load(build_if_missing=True):
         getattr(L, "rx_track_learn_tables" + sfx).argtypes = [lt, ctypes.c_int32, ctypes.c_int32, _P]
         getattr(L, "rx_track_learn_draw" + sfx).argtypes = [lt, ctypes.c_int64, ctypes.c_uint32, ctypes.c_double,
                                                             ctypes.c_double, _P]
+        ev = ctypes.POINTER(RxTrackEvolveIO)
+        getattr(L, "rx_track_evolve_plan" + sfx).argtypes = [ev, ctypes.c_uint32, ctypes.c_double, _P]
+        getattr(L, "rx_track_evolve" + sfx).argtypes = [ev, ctypes.c_uint32, _P]
         getattr(L, "rx_league_weights" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int32, ctypes.c_int32,
                                                          ctypes.c_double, ctypes.c_double, _P]
         getattr(L, "rx_league_draw" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int64, _P, _P, _P]

@@ -275,40 +275,53 @@ class CurriculumPPO(PPO):
         whose tracks were just replaced.  The one place a subclass changes the draw."""
         return self.curriculum.draw(generation)
 
+    def _replace_tracks(self, generation, slots, control_points, widths):
+        """Put the given host tracks into ``slots`` and build the pool's table (one
+        ``DeviceTrackTable.build`` of every slot's control points)."""
+        from .track_device import DeviceTrackTable
+        for k, cp, w in zip(slots, control_points, widths):
+            self._cps[k], self._widths[k] = cp, w
+        return DeviceTrackTable.build(self._cps, self._widths, device=self.device)
+
+    def _spawn_tracks(self, generation, retired):
+        """New tracks for the ``retired`` slots -> the ``DeviceTrackTable`` of the whole
+        pool.  The one place a subclass changes where new tracks come from; here the
+        host draw: ``gen_tracks(seed=None)`` and one ``randint(6, 10)`` width each
+        from ``RandomState(seed + 7919 * generation)``."""
+        from .track import gen_tracks
+        rng = np.random.RandomState((self.config["seed"] + 7919 * generation) % 2 ** 32)
+        new_cps = gen_tracks(len(retired), seed=None, rng=rng)
+        new_widths = [int(rng.randint(6, 10)) for _ in range(len(retired))]
+        return self._replace_tracks(generation, retired, new_cps, new_widths)
+
     def resample_tracks(self, control_points=None, widths=None):
         """Redraw the envs over the track slots from the tallies.  With no arguments:
         the scores; up to floor(curriculum_refresh * n_tracks) mastered slots are
         retired for fresh tracks (``gen_tracks(seed=None)`` and one ``randint(6, 10)``
         width each from ``RandomState(seed + 7919 * g)``, as ``PPO.resample_tracks``
-        draws them: np.random does not move), their tallies start again and the table
-        is rebuilt on the device; then every env draws its slot (generation g) and is
-        reset.  With nothing retired the table stays and only the assignment moves
-        (``reassign_tracks``).  ``control_points`` and ``widths`` (one per slot)
-        replace the whole pool instead.  The captured rollout graphs are dropped.
-        Returns the new (next_obs, next_done)."""
-        from .track import gen_tracks
-        from .track_device import DeviceTrackTable
+        draws them: np.random does not move; ``_spawn_tracks``), their tallies start
+        again and the table is rebuilt on the device; then every env draws its slot
+        (generation g) and is reset.  With nothing retired the table stays and only
+        the assignment moves (``reassign_tracks``).  ``control_points`` and ``widths``
+        (one per slot) replace the whole pool instead.  The captured rollout graphs
+        are dropped.  Returns the new (next_obs, next_done)."""
         cur, envs = self.curriculum, self.envs
         g = envs.track_generation + 1
         cur.scores()
+        table = None
         if control_points is not None or widths is not None:
             if control_points is None or widths is None or len(control_points) != cur.n_tracks \
                     or len(widths) != cur.n_tracks:
                 raise ValueError(f"resample_tracks: pass control_points and widths for all {cur.n_tracks} slots")
             retired = np.arange(cur.n_tracks, dtype=np.int64)
-            new_cps, new_widths = list(control_points), list(widths)
+            table = self._replace_tracks(g, retired, list(control_points), list(widths))
         else:
             retired = self._mastered()
             if len(retired):
-                rng = np.random.RandomState((self.config["seed"] + 7919 * g) % 2 ** 32)
-                new_cps = gen_tracks(len(retired), seed=None, rng=rng)
-                new_widths = [int(rng.randint(6, 10)) for _ in range(len(retired))]
+                table = self._spawn_tracks(g, retired)
         if len(retired):
-            for k, cp, w in zip(retired, new_cps, new_widths):
-                self._cps[k], self._widths[k] = cp, w
             cur.reset_slots(retired)
             cur.scores()  # a fresh slot weighs what an unseen one does
-            table = DeviceTrackTable.build(self._cps, self._widths, device=self.device)
             toe = self._draw_tracks(g, retired).cpu().numpy()
             next_obs = envs.set_tracks(table, toe)
         else:

@@ -36,8 +36,36 @@ class DeviceTrackTable:
         self.wp_off = np.ascontiguousarray(wp_off, dtype=np.int32)
         self.wp, self.nrm, self.seg, self.meta = wp, nrm, seg, meta
         self.device = meta.device
-        self.control_points, self.widths, self.factor = control_points, widths, factor
+        self._control_points, self._widths, self.factor = control_points, widths, factor
+        self._cp_dev = None  # build_from_device: (cp_off, cp, width), downloaded when someone asks
         self._track_set = None
+
+    def _download_control_points(self):
+        cp_off, cp_d, w_d = self._cp_dev
+        cp = cp_d.cpu().numpy().reshape(-1, 2)
+        self._control_points = [cp[cp_off[k]:cp_off[k + 1]].copy() for k in range(len(cp_off) - 1)]
+        self._widths = [float(w) for w in w_d.cpu().numpy()]
+        self._cp_dev = None
+
+    @property
+    def control_points(self):
+        if self._cp_dev is not None:
+            self._download_control_points()
+        return self._control_points
+
+    @control_points.setter
+    def control_points(self, value):
+        self._control_points = value
+
+    @property
+    def widths(self):
+        if self._cp_dev is not None:
+            self._download_control_points()
+        return self._widths
+
+    @widths.setter
+    def widths(self, value):
+        self._widths = value
 
     def __len__(self):
         return len(self.wp_off) - 1
@@ -77,6 +105,39 @@ class DeviceTrackTable:
                                          *[_lib.ptr(x) for x in parts], _lib.stream_ptr()), "rx_build_tracks")
         return cls(wp_off, parts[0].view(wt, 2), parts[1].view(wt, 2), parts[2].view(2 * wt, 4), parts[3].view(n, 8),
                    control_points=cps, widths=ws, factor=factor)
+
+    @classmethod
+    def build_from_device(cls, cp_off, cp_d, width_d, factor=30):
+        """``build`` on control points that already live in device memory: ``cp_off``
+        (host int32 [n + 1], in points), ``cp_d`` (float64 [cp_off[n], 2]) and
+        ``width_d`` (float64 [n]) on one device.  The same ONE rx_build_tracks launch
+        on torch's current stream, without the host concatenation and the upload; no
+        download and no wait.  ``control_points`` and ``widths`` come down only when
+        ``track_set()`` or a caller asks for them (the tensors are kept until then)."""
+        L = _lib.load()
+        cp_off = np.ascontiguousarray(cp_off, dtype=np.int32)
+        n, dev = len(cp_off) - 1, width_d.device
+        if n <= 0:
+            raise ValueError("need at least one track and one width per track")
+        if cp_d.device != dev or dev.type != "cuda" or cp_d.dtype != torch.float64 or width_d.dtype != torch.float64 \
+                or tuple(cp_d.shape) != (int(cp_off[-1]), 2) or tuple(width_d.shape) != (n,) \
+                or not cp_d.is_contiguous() or not width_d.is_contiguous():
+            raise ValueError(f"build_from_device: need contiguous float64 control points [{int(cp_off[-1])}, 2] and "
+                             f"widths [{n}] on one cuda device, got {tuple(cp_d.shape)} {cp_d.dtype} on {cp_d.device} "
+                             f"and {tuple(width_d.shape)} {width_d.dtype} on {dev}")
+        wt = max(int(cp_off[-1]) * max(int(factor), 0), 0)
+        cuts = np.concatenate([[0], np.cumsum((2 * wt, 2 * wt, 8 * wt, 8 * n))])
+        wp_off = np.zeros(n + 1, dtype=np.int32)
+        with torch.cuda.device(dev):
+            flat_d = torch.empty(int(cuts[-1]), dtype=torch.float64, device=dev)
+            parts = [flat_d[cuts[i]:cuts[i + 1]] for i in range(4)]
+            _lib.check(L.rx_build_tracks(n, factor, _lib.ptr(cp_off), _lib.ptr(cp_d), _lib.ptr(width_d),
+                                         _lib.ptr(wp_off), *[_lib.ptr(x) for x in parts], _lib.stream_ptr()),
+                       "rx_build_tracks")
+        table = cls(wp_off, parts[0].view(wt, 2), parts[1].view(wt, 2), parts[2].view(2 * wt, 4), parts[3].view(n, 8),
+                    factor=factor)
+        table._cp_dev = (cp_off, cp_d, width_d)
+        return table
 
     @classmethod
     def from_arrays(cls, arrays, device):

@@ -3,6 +3,7 @@
     python tools/curriculum_train.py --envs 4096 --steps 128 --updates 60 --tracks 512 --resample-every 4
     python tools/curriculum_train.py --envs 64 --steps 32 --updates 6 --tracks 8 --resample-every 2 --no-uniform
     python tools/curriculum_train.py --replay value_l1 --envs 4096 --steps 128 --updates 60 --tracks 512
+    python tools/curriculum_train.py --evolve --envs 4096 --steps 128 --updates 60 --tracks 512
 
 ``CurriculumPPO`` on a pool of ``--tracks`` distinct tracks (env i starts on slot
 i % tracks): every finished episode is tallied against its slot on the device;
@@ -18,6 +19,9 @@ printed.  With ``--replay value_l1`` (or ``value_pos``) the curriculum run is
 ``rx.track_replay.ReplayCurriculumPPO``: the redraw follows the value-loss scores
 of the rollouts (rank prioritisation ``--replay-power``, staleness ``--stale-mix``)
 instead of the finish tallies; ``off`` (the default) runs ``CurriculumPPO``.
+With ``--evolve`` it is ``rx.track_evolve.EvolvingCurriculumPPO``: the replay draw
+(``--replay``, value_l1 when left off) and the retired slots filled on the device,
+a fraction ``--evolve-edit`` of them by edited children of high-ranked tracks.
 """
 import argparse
 import json
@@ -44,9 +48,11 @@ def run(kind, args, evaluator):
                       curriculum_score=args.score, curriculum_refresh=args.refresh, curriculum_mastery=args.mastery,
                       curriculum_min_episodes=args.min_episodes)
     cfg["total_timesteps"] = args.updates * cfg["batch_size"]
-    replay = kind == "curriculum" and args.replay != "off"
+    evolve = kind == "curriculum" and args.evolve
+    replay_kind = "value_l1" if evolve and args.replay == "off" else args.replay
+    replay = kind == "curriculum" and replay_kind != "off"
     if replay:
-        cfg.update(replay_kind=args.replay, replay_power=args.replay_power, replay_alpha=args.replay_alpha,
+        cfg.update(replay_kind=replay_kind, replay_power=args.replay_power, replay_alpha=args.replay_alpha,
                    replay_stale_mix=args.stale_mix)
     random.seed(args.seed)
     np.random.seed(args.seed)
@@ -58,6 +64,9 @@ def run(kind, args, evaluator):
     cls = CurriculumPPO if kind == "curriculum" else PPO
     if replay:
         from rx.track_replay import ReplayCurriculumPPO as cls
+    if evolve:
+        from rx.track_evolve import EvolvingCurriculumPPO as cls
+        cfg["evolve_edit"] = args.evolve_edit
     t = cls(lambda i: RacingEnv(num_sensors=11, track_pool=pool, track_id=i % n, track_width=widths[i % n]), cfg,
             device="cuda")
     info, curve = {"steps": [], "rewards": []}, []
@@ -70,7 +79,8 @@ def run(kind, args, evaluator):
             print(f"[{kind}] update {update + 1}: eval success {s['success_rate']:.3f} crash {s['crash_rate']:.3f}",
                   flush=True)
     first90 = next((c["env_steps"] for c in curve if c["success_rate"] >= 0.9), None)
-    out = {"kind": kind, "replay": args.replay if kind == "curriculum" else "off", "eval": curve, "env_steps_to_90": first90, "track_generation": t.envs.track_generation}
+    out = {"kind": kind, "replay": replay_kind if kind == "curriculum" else "off", "evolve": bool(evolve),
+           "evolve_edit": args.evolve_edit if evolve else None, "eval": curve, "env_steps_to_90": first90, "track_generation": t.envs.track_generation}
     if kind == "curriculum":
         from rx.curriculum import format_track_table
         tab = t.track_table()
@@ -102,6 +112,9 @@ def main():
     ap.add_argument("--replay-power", type=int, default=4, help="rank weight (1 / rank) ** power")
     ap.add_argument("--replay-alpha", type=float, default=1.0)
     ap.add_argument("--stale-mix", type=float, default=0.1)
+    ap.add_argument("--evolve", action="store_true",
+                    help="fill the retired slots on the device (rx.track_evolve): fresh tracks and edited children")
+    ap.add_argument("--evolve-edit", type=float, default=0.5, help="the fraction of retired slots filled by an edit")
     ap.add_argument("--prec", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--show", type=int, default=20, help="slots of the table to print, the most failed first")
