@@ -143,10 +143,10 @@ struct rx_env {
   // split step (k_kin1 + k_step2): cos / sin of the stepped angles; RX_SPLIT=0 disables
   DevBuf<double> cs_scratch;
   bool split = true;
-  // rx_steps' carried schedule: two snapshots of what the ray waves read -- the stepped
-  // pose ([3][N] x, y, angle) and the sorted task ids -- written by a step's KIN part
-  // (the paired schedule: rings of RX_PAIR_RING, and a shadow of the obs rows for the older
-  // of two ray steps that would write the same rows -- stride-0 outputs)
+  // rx_steps' carrying schedule: rings of snapshots of what the ray waves read -- the stepped
+  // pose ([3][N] x, y, angle) and the sorted task ids -- written by a step's KIN part, and a
+  // shadow of the obs rows for the older of two ray steps that would write the same rows
+  // (stride-0 outputs)
   DevBuf<double> snap_pose[RX_PAIR_RING];
   DevBuf<int32_t> snap_tasks[RX_PAIR_RING];
   DevBuf<float> obs_shadow;
@@ -695,24 +695,20 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
     std::vector<double> z(2 * (size_t)N * A, 0.0);
     if ((rc = upload(h->cs_scratch, z.data(), z.size()))) return rc;
   }
-  // the carried schedule's snapshots (single-agent; here, not in rx_steps: it may run under capture)
-  for (int b = 0; b < (RX_STEPS_PAIR ? RX_PAIR_RING : 2) && RX_STEPS_CARRY && A == 1; ++b) {
-    std::vector<double> z(3 * (size_t)N, 0.0);
-    if ((rc = upload(h->snap_pose[b], z.data(), z.size()))) return rc;
-    if (h->cfg.ray_order == 2) {
-      std::vector<int32_t> t0((size_t)N * R, 0);
-      if ((rc = upload(h->snap_tasks[b], t0.data(), t0.size()))) return rc;
+  // the carrying schedule's snapshots (single-agent; here, not in rx_steps: it may run under capture)
+  if (RX_STEPS_CARRY && A == 1) {
+    const std::vector<double> zd(3 * (size_t)N, 0.0);
+    const std::vector<int32_t> zi((size_t)N * R, 0);
+    const std::vector<float> zf((size_t)N * h->D, 0.0f);
+    for (int b = 0; b < RX_PAIR_RING; ++b) {
+      if ((rc = upload(h->snap_pose[b], zd.data(), zd.size()))) return rc;
+      if (h->cfg.ray_order == 2 && (rc = upload(h->snap_tasks[b], zi.data(), zi.size()))) return rc;
     }
-  }
-  if (RX_STEPS_CARRY && RX_STEPS_PAIR && A == 1) {
-    std::vector<float> z((size_t)N * h->D, 0.0f);
-    if ((rc = upload(h->obs_shadow, z.data(), z.size()))) return rc;
-  }
-  for (int b = 0; b < RX_CROSS_RING && RX_STEPS_CARRY && RX_STEPS_PAIR && RX_STEPS_CROSS && A == 1 && h->sort_on; ++b) {
-    std::vector<int32_t> r0((size_t)N, 0);
-    std::vector<double> h0((size_t)N, 0.0);
-    if ((rc = upload(h->snap_rows[b], r0.data(), r0.size()))) return rc;
-    if ((rc = upload(h->snap_hint[b], h0.data(), h0.size()))) return rc;
+    if ((rc = upload(h->obs_shadow, zf.data(), zf.size()))) return rc;
+    for (int b = 0; b < RX_CROSS_RING && RX_STEPS_CROSS && h->sort_on; ++b) {  // the crossing step's
+      if ((rc = upload(h->snap_rows[b], zi.data(), (size_t)N))) return rc;
+      if ((rc = upload(h->snap_hint[b], zd.data(), (size_t)N))) return rc;
+    }
   }
   if ((rc = upload(h->dyn_waves, dyn.data(), dyn.size()))) return rc;
   if ((rc = upload(h->ray_waves, ray.data(), ray.size()))) return rc;
@@ -856,10 +852,10 @@ static void make_kargs(rx_env* h, const rx_io* io, int mode, const uint8_t* mask
   a.lane_tracks = h->lane_tracks;
   a.pos_slot = h->lane_tracks ? h->pos_slot.p : nullptr;
   a.cs_scratch = h->cs_scratch.p;
-  a.ray_x = a.st.x;  // the ray inputs: the working state (rx_steps' carried schedule: a snapshot)
+  a.ray_x = a.st.x;  // the ray inputs: the working state (rx_steps' carrying launches: a snapshot)
   a.ray_y = a.st.y;
   a.ray_angle = a.st.angle;
-  a.ray_hint = a.st.progress;  // (a crossing step of rx_steps' paired schedule: the hint snapshot)
+  a.ray_hint = a.st.progress;  // (a crossing step of rx_steps: the hint snapshot)
   a.sort_base = h->sort_base.p;
   a.sort_shift = h->sort_shift;
   a.box_quadrants = h->cfg.box_quadrants >= 0;
@@ -867,6 +863,59 @@ static void make_kargs(rx_env* h, const rx_io* io, int mode, const uint8_t* mask
 #ifdef RX_AB_NO_EPSTATS  // A/B build only (tools/build_rev.py): drop the episode-statistics atomics
   a.io.ep_stats = nullptr;
 #endif
+}
+
+// The bookkeeping of a dynamics launch, shared by launch() and rx_steps' carrying schedule
+// (steps_pair), which advances it as K x rx_step would.
+// The ray-task order only steers which rays share a wave (results never depend on it): a KIN
+// part may reuse the previous one's while the blocks hold the same envs.  Does the next KIN
+// part sort its ray tasks?  (Asked only where tasks_out is non-null.)
+static bool task_sort_due(const rx_env* h) {
+  return h->tasks_stale || (h->task_calls % (uint64_t)h->task_sort) == 0;
+}
+// ... and the same for the KIN part being armed now, which takes its turn
+static bool take_task_sort_turn(rx_env* h) {
+  const bool due = task_sort_due(h);
+  if (due) h->tasks_stale = false;
+  ++h->task_calls;
+  return due;
+}
+// Spatial re-sort, every sort_interval dynamics launches (dyn_calls counts them only while
+// the re-sort is on): is it due `ahead` dynamics launches from now?
+static bool resort_on(const rx_env* h) { return h->cfg.sort_interval > 0 && h->sort_on; }
+static bool resort_due(const rx_env* h, int32_t ahead) {
+  return resort_on(h) && ((h->dyn_calls + ahead) % h->cfg.sort_interval) == 0;
+}
+// The REWARD half (or k_dyn) of the re-sort step writes the sort keys; with `hist` (single
+// agent, split step) it also builds the re-sort's histogram and each env's rank in its bin,
+// one launch fewer per re-sort: rx_sort_envs skips k_sort_hist.  The histogram is zero
+// unless sort_hist_done, when it holds the counts of the keys this launch is about to
+// overwrite (keys requested again before their sort ran: rx_step_phases(1) twice, or a reset
+// in between): clear it, so the fused count, or k_sort_hist, starts from zero.
+static int arm_sort_keys(rx_env* h, rx_kargs& a, bool hist, hipStream_t s) {
+  if (h->sort_hist_done) {
+    RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sort_bins * sizeof(uint32_t), s));
+    h->sort_hist_done = false;
+  }
+  a.sort_keys = h->keys_in.p;
+  if (hist) {
+    a.sort_hist = h->sort_hist.p;
+    a.sort_off = h->keys_off.p;
+    h->sort_hist_done = true;
+  }
+  return RX_OK;
+}
+// The sort itself, which moves the working-state rows: after the raycast of the step whose
+// keys it reads (the ray tasks name positions), so the new order applies from the next step.
+static int sort_envs_now(rx_env* h, hipStream_t s) {
+  const int hist_done = h->sort_hist_done ? 1 : 0;
+  h->sort_hist_done = false;
+  h->tasks_stale = true;  // the re-sort moves envs between blocks
+  rx_state work = h->work, tmp = h->work_tmp;
+  const int rc = rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, h->cfg.n_agents, h->sort_hist.p,
+                              h->sort_cursor.p, h->sort_bins, h->perm[0].p, h->perm[1].p, &work, &tmp, s, hist_done);
+  if (rc != 0) return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
 }
 
 static int launch(rx_env* h, const rx_io* io, int mode, const uint8_t* mask, void* stream, int phases = 3) {
@@ -901,48 +950,21 @@ static int launch(rx_env* h, const rx_io* io, int mode, const uint8_t* mask, voi
     a.reset_rank = h->draw_rank.p;
   }
   const bool split = split_step(h, mode);
-  // Spatial re-sort, every sort_interval dynamics launches: that launch's
-  // REWARD half (or k_dyn) writes the sort keys; the sort -- which moves the
-  // working-state rows -- runs after the step's raycast (the ray tasks name
-  // positions), so the new order applies from the next step.
   const bool dyn = (phases & RX_PHASE_DYNAMICS) != 0;
-  // the ray-task order only steers which rays share a wave (results never depend
-  // on it): a launch may reuse the previous one's while the blocks hold the same envs
-  if (dyn && a.tasks_out) {
-    if (h->tasks_stale || (h->task_calls % (uint64_t)h->task_sort) == 0)
-      h->tasks_stale = false;
-    else
-      a.tasks_out = nullptr;
-    ++h->task_calls;
-  }
-  if (dyn && h->cfg.sort_interval > 0 && h->sort_on && (h->dyn_calls++ % h->cfg.sort_interval) == 0) {
-    a.sort_keys = h->keys_in.p;
-    // The histogram is zero unless sort_hist_done, when it holds the counts of
-    // the keys this launch is about to overwrite (keys requested again before
-    // their sort ran: rx_step_phases(1) twice, or a reset in between): clear it,
-    // so the fused count below, or k_sort_hist, starts from zero.
-    if (h->sort_hist_done) {
-      RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sort_bins * sizeof(uint32_t), s));
-      h->sort_hist_done = false;
-    }
-    h->sort_pending = true;
-  }
+  if (dyn && a.tasks_out && !take_task_sort_turn(h)) a.tasks_out = nullptr;
+  // the re-sort step: its keys are armed below, for the launch that writes them (the two-car
+  // REWARD half and k_dyn count no bins); the sort runs after the step's raycast, which
+  // rx_step_phases may ask for in a later call (sort_pending)
+  const bool resort = dyn && resort_due(h, 0);
+  if (dyn && resort_on(h)) ++h->dyn_calls;
+  if (resort) h->sort_pending = true;
   if (split) {
-    uint32_t* keys = a.sort_keys;
     if (dyn) {
-      a.sort_keys = nullptr;
       prof_arm(h, a, RX_KERNEL_KIN);
       if ((rc = rx_launch_split(&a, A, RX_SPLIT_KIN, s)) != 0)
         return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
       a.tasks_out = nullptr;
-      a.sort_keys = keys;
-      // single-agent: the REWARD half also builds the re-sort's histogram (one
-      // launch fewer per re-sort: rx_sort_envs skips k_sort_hist)
-      if (keys && A == 1) {
-        a.sort_hist = h->sort_hist.p;
-        a.sort_off = h->keys_off.p;
-        h->sort_hist_done = true;
-      }
+      if (resort && (rc = arm_sort_keys(h, a, A == 1, s)) != 0) return rc;
       prof_arm(h, a, phases == 3 ? RX_KERNEL_STEP2 : RX_KERNEL_REWARD);
       if ((rc = rx_launch_split(&a, A, phases == 3 ? RX_SPLIT_REWARD_RAYS : RX_SPLIT_REWARD, s)) != 0)
         return fail(RX_EHIP, "k_step2 launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -954,6 +976,7 @@ static int launch(rx_env* h, const rx_io* io, int mode, const uint8_t* mask, voi
     }
   } else {
     if (dyn) {
+      if (resort && (rc = arm_sort_keys(h, a, false, s)) != 0) return rc;
       prof_arm(h, a, RX_KERNEL_DYN);
       if ((rc = rx_launch_step(&a, h->cfg.n_agents, RX_PHASE_DYNAMICS, s)) != 0)
         return fail(RX_EHIP, "k_dyn launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -968,13 +991,7 @@ static int launch(rx_env* h, const rx_io* io, int mode, const uint8_t* mask, voi
   }
   if (h->sort_pending && (phases & RX_PHASE_RAYS)) {
     h->sort_pending = false;
-    h->tasks_stale = true;  // the re-sort moves envs between blocks
-    rx_state work = h->work, tmp = h->work_tmp;
-    const int hist_done = h->sort_hist_done ? 1 : 0;
-    h->sort_hist_done = false;
-    if ((rc = rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, A, h->sort_hist.p, h->sort_cursor.p, h->sort_bins,
-                           h->perm[0].p, h->perm[1].p, &work, &tmp, s, hist_done)) != 0)
-      return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
+    if ((rc = sort_envs_now(h, s)) != 0) return rc;
   }
   return RX_OK;
 }
@@ -1137,126 +1154,29 @@ static rx_io io_at(const rx_io* io, const rx_io_strides& st, int64_t s) {
   return o;
 }
 
-// rx_steps' carried schedule (DESIGN.md §3 "The carried step") applies to the split step of
-// single-agent envs at one lane per env while nothing records (rx_profile, the counters)
+// rx_steps' carrying schedule (steps_pair) applies to the split step of single-agent envs at
+// one lane per env -- what k_step2_pair is built for -- while nothing records (rx_profile's
+// stamps and the counters are per launch of rx_step's kernels), with no re-sort left pending
+// by rx_step_phases (its keys belong to a step whose rays are not cast yet), and needs
+// rx_assign's snapshot rings and shadow obs rows.  Otherwise rx_steps is K x rx_step.
 static bool steps_carried(const rx_env* h, const rx_io* io) {
-  return RX_STEPS_CARRY && split_step(h, RX_MODE_STEP) && h->cfg.n_agents == 1 && h->reward_lpe == 1 && !h->prof &&
-         !io->counters && !h->sort_pending && h->snap_pose[0].p && h->snap_pose[1].p &&
-         (h->cfg.ray_order != 2 || h->lane_tracks || (h->snap_tasks[0].p && h->snap_tasks[1].p));
-}
-
-// K steps with the actions of all of them in device memory: block b's KIN part of step
-// k + 1 needs only block b's REWARD results of step k, so REWARD wave b of step k's
-// k_step2 runs it (k_step2_carry) and k_kin1 leaves the step:
-//   k_kin1(0); per step k: k_step2_carry(REWARD k | rays k | KIN k + 1); plain k_step2(K - 1)
-// A step whose re-sort is due runs the plain k_step2, the sort, then a k_kin1 for the next
-// step (the sort moves rows, and the tasks name positions).  KIN k + 1 overwrites what the
-// ray waves of step k read, so every KIN part also stores its pose and its task row to a
-// snapshot and the ray waves read that: poses alternate by the step's parity within the call
-// (the launch boundary frees the other one), task rows by the sorts of the call (task_sort
-// > 1: the rays read the row last written, which the next sort must not overwrite under
-// them) -- a captured call replays with the same buffers.  Until the call's first sort the
-// rays read the handle's task buffer, which every sort otherwise also writes (it stays the
-// current order for the launches after the call): a CARRIED sort while the rays still read
-// it writes the snapshot alone, and if no later sort of the call brings the handle's buffer
-// up to date the call leaves it marked stale (it is a valid, older order; the next dynamics
-// launch sorts).  No carrying launch reads the buffer it sorts into (rx_launch_step2_carry
-// refuses one).  The working state stays single-buffered and is current after every launch;
-// the bookkeeping (dyn_calls, task_calls, the re-sort) advances as K x rx_step.
-static int steps_carry(rx_env* h, const rx_io* io, const rx_io_strides& st, int32_t K, hipStream_t s) {
-  const size_t N = (size_t)h->cfg.n_envs;
-  rx_kargs a{};
-  make_kargs(h, io, RX_MODE_STEP, nullptr, a);
-  int32_t* const tasks_main = a.tasks_out;  // nullptr: this schedule sorts no ray tasks
-  const int32_t* ray_tasks = h->tasks.p;    // the row the last sort wrote: the handle's before the call's first
-  int tb = 0, rc;
-  bool main_behind = false;  // the last sort left the handle's task buffer out
-  // the KIN part of step k (the ray-task sort's turn as in launch()); carried: in the launch
-  // whose ray waves read ray_tasks
-  auto kin_args = [&](int32_t k, bool carried) {
-    a.snap_x = h->snap_pose[k & 1].p;
-    a.snap_y = a.snap_x + N;
-    a.snap_angle = a.snap_x + 2 * N;
-    a.tasks_out = tasks_main;
-    a.tasks_snap = nullptr;
-    if (tasks_main) {
-      if (h->tasks_stale || (h->task_calls % (uint64_t)h->task_sort) == 0) {
-        h->tasks_stale = false;
-        main_behind = carried && ray_tasks == tasks_main;  // this launch's ray waves read the handle's buffer
-        if (main_behind)
-          a.tasks_out = h->snap_tasks[tb].p;
-        else
-          a.tasks_snap = h->snap_tasks[tb].p;
-        ray_tasks = h->snap_tasks[tb].p;
-        tb ^= 1;
-      } else {
-        a.tasks_out = nullptr;
-      }
-      ++h->task_calls;
-    }
-  };
-  a.io = io_at(io, st, 0);
-  kin_args(0, false);
-  if ((rc = rx_launch_split(&a, 1, RX_SPLIT_KIN, s)) != 0)
-    return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
-  for (int32_t k = 0; k < K; ++k) {
-    a.io = io_at(io, st, k);
-    a.ray_x = h->snap_pose[k & 1].p;  // what KIN k stored
-    a.ray_y = a.ray_x + N;
-    a.ray_angle = a.ray_x + 2 * N;
-    a.tasks = ray_tasks;
-    const bool resort = h->cfg.sort_interval > 0 && h->sort_on && (h->dyn_calls++ % h->cfg.sort_interval) == 0;
-    a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
-    if (!resort && k + 1 < K) {
-      a.io_next = io_at(io, st, k + 1);
-      kin_args(k + 1, true);
-      if ((rc = rx_launch_step2_carry(&a, s)) != 0)
-        return fail(RX_EHIP, "k_step2_carry launch failed: %s", hipGetErrorString((hipError_t)rc));
-      continue;
-    }
-    if (resort) {  // as launch(): the REWARD half writes the keys and counts the bins
-      if (h->sort_hist_done) RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sort_bins * sizeof(uint32_t), s));
-      a.sort_keys = h->keys_in.p;
-      a.sort_hist = h->sort_hist.p;
-      a.sort_off = h->keys_off.p;
-    }
-    a.tasks_out = nullptr;
-    if ((rc = rx_launch_split(&a, 1, RX_SPLIT_REWARD_RAYS, s)) != 0)
-      return fail(RX_EHIP, "k_step2 launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (resort) {
-      h->sort_hist_done = false;
-      h->tasks_stale = true;  // the re-sort moves envs between blocks
-      rx_state work = h->work, tmp = h->work_tmp;
-      if ((rc = rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, 1, h->sort_hist.p, h->sort_cursor.p,
-                             h->sort_bins, h->perm[0].p, h->perm[1].p, &work, &tmp, s, 1)) != 0)
-        return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    if (k + 1 < K) {
-      a.io = io_at(io, st, k + 1);
-      a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
-      kin_args(k + 1, false);
-      if ((rc = rx_launch_split(&a, 1, RX_SPLIT_KIN, s)) != 0)
-        return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-  }
-  if (main_behind) h->tasks_stale = true;
-  return RX_OK;
-}
-
-// the paired schedule needs the snapshot rings and the shadow obs rows of rx_assign
-static bool steps_paired(const rx_env* h) {
-  if (!RX_STEPS_PAIR || !h->obs_shadow.p) return false;
+  if (!RX_STEPS_CARRY || !split_step(h, RX_MODE_STEP) || h->cfg.n_agents != 1 || h->reward_lpe != 1) return false;
+  if (h->prof || io->counters || h->sort_pending || !h->obs_shadow.p) return false;
   for (int b = 0; b < RX_PAIR_RING; ++b)
     if (!h->snap_pose[b].p || (h->cfg.ray_order == 2 && !h->lane_tracks && !h->snap_tasks[b].p)) return false;
   return true;
 }
 
-// The carried schedule with two steps per launch (DESIGN.md §3 "The paired launch").  The ray
-// waves of step k read only what KIN k stored (the pose snapshot, the task row) and nothing
-// of a later step reads what they write, so once KIN k's launch has completed they can be
-// cast in ANY later launch of the window.  `pend` is the queue of such steps: KIN done, rays
-// not yet cast (never more than two).  Every launch casts all of them and its REWARD
-// workgroups advance up to two steps D_k = (REWARD k, KIN k + 1), which refills the queue:
+// K steps with the actions of all of them in device memory (DESIGN.md §3 "The carried step",
+// "The paired launch").  Block b's KIN part of step k + 1 needs only block b's REWARD results
+// of step k, so REWARD workgroup b of a k_step2_pair launch runs it and k_kin1 leaves the
+// step.  KIN k + 1 overwrites what the ray waves of step k read, so every KIN part also
+// stores its pose and its task row to a snapshot and the ray waves read that.  They read
+// nothing else that a later step writes and nothing of a later step reads what they write,
+// so once KIN k's launch has completed they can be cast in ANY later launch of the window.
+// `pend` is the queue of such steps: KIN done, rays not yet cast (never more than two).
+// Every launch casts all of them and its REWARD workgroups advance up to two steps D_k =
+// (REWARD k, KIN k + 1), which refills the queue:
 //   k_kin1(0) [D0 D1 | rays 0] [D2 D3 | rays 1 2] [D4 D5 | rays 3 4] [D6 | rays 5 6]
 //   k_step2(7, keys) sort k_kin1(8) ...
 // A step whose re-sort is due, and the call's last step, has no KIN behind its REWARD: the
@@ -1264,10 +1184,18 @@ static bool steps_paired(const rx_env* h) {
 // KIN-less sub-step (which writes the keys).  So the queue is empty before every sort (the
 // sort moves rows, and the rays name positions) and at the end of the call.  Pose snapshots
 // are a ring of RX_PAIR_RING by the step's index in the call, task rows a ring by the
-// call's sorts: a launch stores steps k + 1, k + 2 and reads k - 1, k.  Two ray steps that
-// would write the same obs rows (stride 0): the older one writes the handle's shadow rows,
-// so the caller's rows end with the newest step's.  The task buffer of the handle and the
-// bookkeeping are kept as steps_carry keeps them.
+// call's sorts (task_sort > 1: the rays read the row last written, which the next sort must
+// not overwrite under them): a launch stores steps k + 1, k + 2 and reads k - 1, k, and a
+// captured call replays with the same buffers.  Two ray steps that would write the same obs
+// rows (stride 0): the older one writes the handle's shadow rows, so the caller's rows end
+// with the newest step's.  Until the call's first sort the rays read the handle's task
+// buffer, which every sort otherwise also writes (it stays the current order for the launches
+// after the call): a sort in a launch whose rays still read it writes the ring row alone, and
+// if no later sort of the call brings the handle's buffer up to date the call leaves it
+// marked stale (it is a valid, older order; the next dynamics launch sorts).  No launch reads
+// the buffer it sorts into (rx_launch_step2_pair refuses one).  The working state stays
+// single-buffered and is current after every launch; the bookkeeping (dyn_calls, task_calls,
+// the re-sort) advances as K x rx_step.
 // RX_STEPS_CROSS (DESIGN.md §3 "The crossing step"): a re-sort step k + 1 that a step follows
 // in the call gives up its own launch.  REWARD k + 1 is the KIN-less second sub-step of D_k's
 // launch, and step k + 1 stays in the queue ACROSS the sort: the next window's first launch
@@ -1298,34 +1226,31 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
     int32_t* tasks_out;
     int32_t* tasks_snap;
   };
-  // the KIN part of step k (the ray-task sort's turn as in launch()); reads_main: in a launch
-  // one of whose ray steps reads the handle's task buffer.  Step k joins the queue.
+  // the KIN part of step k; reads_main: in a launch one of whose ray steps reads the handle's
+  // task buffer.  Step k joins the queue.
   auto kin_args = [&](int32_t k, bool reads_main) {
     kin_out o{h->snap_pose[k % RX_PAIR_RING].p, nullptr, nullptr};
-    if (tasks_main) {
-      if (h->tasks_stale || (h->task_calls % (uint64_t)h->task_sort) == 0) {
-        h->tasks_stale = false;
-        main_behind = reads_main;
-        int32_t* const row = h->snap_tasks[tb].p;
-        if (main_behind)
-          o.tasks_out = row;
-        else
-          o.tasks_out = tasks_main, o.tasks_snap = row;
-        ray_tasks = row;
-        tb = (tb + 1) % RX_PAIR_RING;
-      }
-      ++h->task_calls;
+    if (tasks_main && take_task_sort_turn(h)) {
+      main_behind = reads_main;
+      int32_t* const row = h->snap_tasks[tb].p;
+      if (main_behind)
+        o.tasks_out = row;
+      else
+        o.tasks_out = tasks_main, o.tasks_snap = row;
+      ray_tasks = row;
+      tb = (tb + 1) % RX_PAIR_RING;
     }
     pend[n_pend++] = ray_step{k, ray_tasks, a.perm, a.st.progress};
     return o;
   };
-  auto kin1 = [&](int32_t k) {
+  auto kin1 = [&](int32_t k) -> int {
     const kin_out o = kin_args(k, false);
     a.io = io_at(io, st, k);
     a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
     a.snap_x = o.snap, a.snap_y = o.snap + N, a.snap_angle = o.snap + 2 * N;
     a.tasks_out = o.tasks_out, a.tasks_snap = o.tasks_snap;
-    return rx_launch_split(&a, 1, RX_SPLIT_KIN, s);
+    const int e = rx_launch_split(&a, 1, RX_SPLIT_KIN, s);
+    return e ? fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)e)) : RX_OK;
   };
   // the pending ray steps into p (emptying the queue); do they read the handle's task buffer?
   auto take_rays = [&](rx_pair& p) {
@@ -1343,31 +1268,13 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
     n_pend = 0;
     return reads_main;
   };
-  // (dyn_calls counts only while the re-sort is on, as launch() counts it)
-  const bool sorting_envs = h->cfg.sort_interval > 0 && h->sort_on;
-  auto resort_at = [&](int32_t ahead) {
-    return sorting_envs && ((h->dyn_calls + ahead) % h->cfg.sort_interval) == 0;
+  auto pair = [&](const rx_pair& p) -> int {
+    const int e = rx_launch_step2_pair(&a, &p, s);
+    return e ? fail(RX_EHIP, "k_step2_pair launch failed: %s", hipGetErrorString((hipError_t)e)) : RX_OK;
   };
-  // will the next KIN part sort its ray tasks (kin_args' turn)?
-  auto kin_sorts = [&] { return h->tasks_stale || (h->task_calls % (uint64_t)h->task_sort) == 0; };
-  // as launch(): the REWARD half of the re-sort step writes the keys and counts the bins
-  auto keys_args = [&]() -> int {
-    if (h->sort_hist_done) RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sort_bins * sizeof(uint32_t), s));
-    a.sort_keys = h->keys_in.p;
-    a.sort_hist = h->sort_hist.p;
-    a.sort_off = h->keys_off.p;
-    return RX_OK;
-  };
-  auto sort_now = [&] {
-    h->sort_hist_done = false;
-    h->tasks_stale = true;  // the re-sort moves envs between blocks
-    rx_state work = h->work, tmp = h->work_tmp;
-    return rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, 1, h->sort_hist.p, h->sort_cursor.p, h->sort_bins,
-                        h->perm[0].p, h->perm[1].p, &work, &tmp, s, 1);
-  };
-  if ((rc = kin1(0)) != 0) return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
+  if ((rc = kin1(0)) != 0) return rc;
   for (int32_t k = 0; k < K;) {
-    const bool resort = resort_at(0);
+    const bool resort = resort_due(h, 0);
     rx_pair p{};
     p.n_envs = (int64_t)N;
     a.io = p.io[0] = io_at(io, st, k);
@@ -1376,15 +1283,15 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
     a.tasks_out = nullptr, a.tasks_snap = nullptr;
     a.rows_snap = nullptr, a.hint_snap = nullptr;
     if (!resort && k + 1 < K) {  // D_k, and D_k+1 unless step k + 1 has no KIN behind it
-      const int32_t d = (k + 2 < K && !resort_at(1)) ? 2 : 1;
+      const int32_t d = (k + 2 < K && !resort_due(h, 1)) ? 2 : 1;
       // Step k + 1 is due for the re-sort and a step follows it in the call: it CROSSES the
       // sort.  Its REWARD runs here as the second sub-step, without a KIN (it writes the keys
       // and the snapshots), and its rays stay pending across the sort.  Its task row must then
       // be a row of the ring: the k_kin1 after the sort rewrites the handle's buffer.  Where it
       // would be the handle's (a call that begins between two task sorts and has not sorted
       // yet), the window does not cross and step k + 1 keeps its own launch.
-      const bool cross = RX_STEPS_CROSS && k + 2 < K && resort_at(1) && h->snap_rows[cb].p && h->snap_hint[cb].p &&
-                         (!tasks_main || ray_tasks != tasks_main || kin_sorts());
+      const bool cross = RX_STEPS_CROSS && k + 2 < K && resort_due(h, 1) && h->snap_rows[cb].p &&
+                         h->snap_hint[cb].p && (!tasks_main || ray_tasks != tasks_main || task_sort_due(h));
       const bool reads_main = take_rays(p);
       p.n_sub = cross ? 2 : d;
       for (int32_t j = 0; j < d; ++j) {
@@ -1394,24 +1301,22 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
         p.snap[j] = o.snap, p.tasks_out[j] = o.tasks_out, p.tasks_snap[j] = o.tasks_snap;
       }
       if (cross) {
-        if ((rc = keys_args()) != 0) return rc;
+        if ((rc = arm_sort_keys(h, a, true, s)) != 0) return rc;
         a.rows_snap = h->snap_rows[cb].p;
         a.hint_snap = h->snap_hint[cb].p;
       }
-      if ((rc = rx_launch_step2_pair(&a, &p, s)) != 0)
-        return fail(RX_EHIP, "k_step2_pair launch failed: %s", hipGetErrorString((hipError_t)rc));
-      if (sorting_envs) h->dyn_calls += (uint64_t)p.n_sub;
+      if ((rc = pair(p)) != 0) return rc;
+      if (resort_on(h)) h->dyn_calls += (uint64_t)p.n_sub;
       k += p.n_sub;
       if (cross) {  // the queue holds step k - 1 alone: from here on it reads the snapshots
         pend[0].rows = a.rows_snap, pend[0].hint = a.hint_snap;
         cb = (cb + 1) % RX_CROSS_RING;
-        if ((rc = sort_now()) != 0) return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
-        if ((rc = kin1(k)) != 0) return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if ((rc = sort_envs_now(h, s)) != 0 || (rc = kin1(k)) != 0) return rc;
       }
       continue;
     }
-    if (sorting_envs) ++h->dyn_calls;
-    if (resort && (rc = keys_args()) != 0) return rc;
+    if (resort_on(h)) ++h->dyn_calls;
+    if (resort && (rc = arm_sort_keys(h, a, true, s)) != 0) return rc;
     if (n_pend == 1 && pend[0].rows == a.perm) {  // only its own rays are pending: the plain k_step2
       a.ray_x = h->snap_pose[pend[0].k % RX_PAIR_RING].p;
       a.ray_y = a.ray_x + N;
@@ -1423,13 +1328,10 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
     } else {
       take_rays(p);
       p.n_sub = 1;
-      if ((rc = rx_launch_step2_pair(&a, &p, s)) != 0)
-        return fail(RX_EHIP, "k_step2_pair launch failed: %s", hipGetErrorString((hipError_t)rc));
+      if ((rc = pair(p)) != 0) return rc;
     }
-    if (resort && (rc = sort_now()) != 0)
-      return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
-    if (++k < K && (rc = kin1(k)) != 0)
-      return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (resort && (rc = sort_envs_now(h, s)) != 0) return rc;
+    if (++k < K && (rc = kin1(k)) != 0) return rc;
   }
   if (main_behind) h->tasks_stale = true;
   return RX_OK;
@@ -1444,9 +1346,7 @@ int rx_steps(rx_env* h, const rx_io* io, int32_t n_steps, const rx_io_strides* s
     return fail(RX_ESTATE, "rx_steps needs rx_upload_tracks, rx_assign and rx_bind_state");
   const rx_io_strides st = strides ? *strides : rx_io_strides{};
   int rc;
-  if (steps_carried(h, io) && n_steps > 0)
-    return steps_paired(h) ? steps_pair(h, io, st, n_steps, (hipStream_t)stream)
-                           : steps_carry(h, io, st, n_steps, (hipStream_t)stream);
+  if (steps_carried(h, io) && n_steps > 0) return steps_pair(h, io, st, n_steps, (hipStream_t)stream);
   for (int32_t k = 0; k < n_steps; ++k) {
     const rx_io o = io_at(io, st, k);
     if ((rc = launch(h, &o, RX_MODE_STEP, nullptr, stream)) != 0) return rc;

@@ -196,38 +196,36 @@ struct rx_kargs {
   const int64_t* draw_base;
   const int32_t* reset_rank;
   // Ray inputs: what a ray wave reads of the stepped state (position order) -- st.x, st.y,
-  // st.angle (and `tasks` above) in every launch but rx_steps' carried ones, where they are
-  // the step's pose snapshot: the REWARD waves of a carrying k_step2 run the next step's KIN
-  // part, which overwrites the working state under this step's ray waves.
+  // st.angle (and `tasks` above) in every launch but those of rx_steps' carrying schedule,
+  // where they are the step's pose snapshot: the REWARD workgroups of a k_step2_pair launch run
+  // later steps' KIN parts, which overwrite the working state under the launch's ray waves.
   const double* ray_x;
   const double* ray_y;
   const double* ray_angle;
   // the culled raycast's visiting-order hint, [N * A] by position: st.progress in every launch
   // but the paired one that casts a crossing step (below), where it is the hint snapshot
   const double* ray_hint;
-  // rx_steps' carried schedule: KIN also stores its stepped pose here (the snapshot its
-  // step's ray waves read), and its sorted task row to tasks_snap; nullptr = no snapshot
+  // rx_steps' carrying launches: a KIN part (k_kin1 at the head of a window, k_step2_pair's
+  // REWARD workgroups after it) also stores its stepped pose here -- the snapshot its step's
+  // ray waves read in a later launch -- and its sorted task row to tasks_snap; nullptr = no
+  // snapshot
   double* snap_x;
   double* snap_y;
   double* snap_angle;
   int32_t* tasks_snap;
-  // carrying k_step2: the io rows of the NEXT step (its KIN part writes them; by env id)
-  rx_io io_next;
 };
 
-// rx_steps' carried schedule (DESIGN.md §3 "The carried step"): the REWARD waves of step
-// t's k_step2 also run step t + 1's KIN part, so k_kin1 leaves the step.  0 = a k_kin1 and a
-// k_step2 launch per step.
+// rx_steps' carrying schedule (DESIGN.md §3 "The carried step", "The paired launch"): the
+// REWARD workgroups of a k_step2_pair launch also run the next step's KIN part, so k_kin1
+// leaves the step; a launch advances up to two steps that way (REWARD k, KIN k + 1, REWARD
+// k + 1, KIN k + 2) and its ray workgroups cast the rays of up to two EARLIER-stepped steps,
+// whose KIN parts completed in a previous launch -- half the launch boundaries, half the
+// drains.  0 = a k_kin1 and a k_step2 launch per step.
 #ifndef RX_STEPS_CARRY
 #define RX_STEPS_CARRY 1
 #endif
-
-// rx_steps' paired schedule (DESIGN.md §3 "The paired launch"): a launch's REWARD workgroups
-// advance up to two steps (REWARD k, KIN k + 1, REWARD k + 1, KIN k + 2) and its ray
-// workgroups cast the rays of up to two EARLIER-stepped steps, whose KIN parts completed in
-// a previous launch -- half the launch boundaries, half the drains.  0 = the carried schedule.
-#ifndef RX_STEPS_PAIR
-#define RX_STEPS_PAIR 1
+#ifdef RX_STEPS_PAIR
+#error "RX_STEPS_PAIR is retired: the paired launches are the one carrying schedule; RX_STEPS_CARRY=0 selects a k_kin1 and a k_step2 launch per step"
 #endif
 #define RX_PAIR_RING 4  // pose / task-row snapshots: a launch writes at most two and reads at most two others
 
@@ -241,7 +239,7 @@ struct rx_kargs {
 #endif
 #define RX_CROSS_RING 2  // row-id / hint snapshots: a launch stores one and may read the other
 
-// What one k_step2_pair launch runs beside rx_kargs (whose io, io_next, ray_*, snap_*, tasks,
+// What one k_step2_pair launch runs beside rx_kargs (whose io, ray_*, snap_*, tasks,
 // tasks_out and tasks_snap it ignores).
 struct rx_pair {
   int32_t n_sub;   // REWARD sub-steps of the launch (1 or 2); the sort keys go with the last one
@@ -276,10 +274,6 @@ extern "C" int64_t rx_pair_layout(int what);
 #define RX_SPLIT_REWARD 1
 #define RX_SPLIT_REWARD_RAYS 2
 extern "C" int rx_launch_split(const rx_kargs* a, int n_agents, int part, hipStream_t s);
-// the carrying k_step2 (single-agent, one lane per env): REWARD of a->io's step beside its
-// raycast, then KIN (and the ray-task sort, with a->tasks_out) of a->io_next's step in the
-// REWARD waves
-extern "C" int rx_launch_step2_carry(const rx_kargs* a, hipStream_t s);
 // persistent small-N rollout (k_rollout): a->n_dyn_waves workgroups, one env
 // each, its slot staged in max_w * 96 bytes of dynamic LDS
 #define RX_ROLLOUT_MAX_W 1024

@@ -526,7 +526,7 @@ __device__ __forceinline__ void sort_block_tasks(const rx_kargs& a, int perm_sta
   const int lane = threadIdx.x & 63;
   int32_t* out = a.tasks_out + (size_t)perm_start * (A * a.n_sensors);
   for (int i = lane; i < total; i += 64) stc(out + i, stage[i]);
-  if (a.tasks_snap) {  // rx_steps' carried schedule: the row this step's ray waves read
+  if (a.tasks_snap) {  // rx_steps' carrying launches: the row this step's ray waves read
     int32_t* snap = a.tasks_snap + (size_t)perm_start * (A * a.n_sensors);
     for (int i = lane; i < total; i += 64) stc(snap + i, stage[i]);
   }
@@ -824,7 +824,7 @@ __device__ __forceinline__ void dyn1_env(const rx_kargs& a, int wave, double* an
     stc(S.vy + p, c.vy);
     stc(S.last_steering + p, last_steering);
     stc(S.steps + p, steps);
-    if (a.snap_x) {  // rx_steps' carried schedule: the pose this step's ray waves read
+    if (a.snap_x) {  // rx_steps' carrying launches: the pose this step's ray waves read
       stc(a.snap_x + p, c.x);
       stc(a.snap_y + p, c.y);
       stc(a.snap_angle + p, c.angle);
@@ -1961,7 +1961,7 @@ __device__ __forceinline__ void rays_wave(const rx_kargs& a, const rx_wave we, c
   const int S_ = 2 * W;
   const double4* __restrict__ seg = reinterpret_cast<const double4*>(a.tr.seg) + 2 * wp0;
   const int i = A * pos + q;  // working state (position order); the obs row is A * perm[pos] + q
-  // the ray inputs: the working state, or the step's pose snapshot (rx_steps' carried schedule)
+  // the ray inputs: the working state, or the step's pose snapshot (rx_steps' carrying launches)
   const double ox = ldc(a.ray_x + i), oy = ldc(a.ray_y + i);
   const double theta = ldc(a.ray_angle + i) + a.rel_angles[ray];  // racing_env.py:50
   RAY_STAMP(1);
@@ -2226,16 +2226,7 @@ __global__ __launch_bounds__(256) void k_rays_wide(rx_kargs a) {
 // the raycast's 64-VGPR cap (k_step2<1>: 36 B/lane of scratch) whichever
 // schedule ran.  For A = 2, RLPE 2 gives each car of an env its own lane in the
 // REWARD half (dyn2_env<REWARD, 2>).
-//
-// CARRY (k_step2_carry, rx_steps' carried schedule; DESIGN.md §3 "The carried step"):
-// REWARD workgroup b goes on, in the same 64 lanes over the same 64 envs, with the KIN
-// part of the NEXT step and the block's ray-task sort -- k_kin1's work, by k_kin1's
-// functions -- under this step's raycast.  KIN reads what REWARD has just stored for its
-// own lane (flags, progress, episode counters: plain per-lane loads after per-lane
-// stores) and writes the next step's rows (a.io_next); it overwrites the working pose
-// and the task buffer, so the launch's ray waves read a snapshot (a.ray_x / ray_y /
-// ray_angle, a.tasks) that the KIN part of THEIR step stored.
-template <int A, int RLPE, int LPR, bool LV, bool CARRY>
+template <int A, int RLPE, int LPR, bool LV>
 __device__ __forceinline__ void step2_body(const rx_kargs& a, int n_rw) {
   const int b = uniform((int)blockIdx.x);
   const unsigned long long prof_t0 = prof_start(a);
@@ -2260,23 +2251,6 @@ __device__ __forceinline__ void step2_body(const rx_kargs& a, int n_rw) {
       dyn2_env<RX_PART_REWARD>(a, b, ang, e, ep);
     }
     add_episode_stats(a, ep);
-    if constexpr (CARRY) {
-      static_assert(A == 1 && RLPE == 1, "the carried step: single-agent envs, one lane per env");
-      if (b < a.n_dyn_waves) {  // (n_rw pads the REWARD workgroups to a multiple of 8)
-        // as k_kin1: 64 sector counters and the staging row (dynamic LDS, only when sorting)
-        extern __shared__ int32_t task_lds[];
-        int32_t* cnt = task_lds;
-        int32_t* stage = cnt + kTaskSectors;
-        const bool sorting = a.tasks_out != nullptr;
-        if (sorting) cnt[threadIdx.x & 63] = 0;
-        rx_kargs an = a;
-        an.io = a.io_next;
-        double ang1[1], ep1[3];
-        int p1 = -1;
-        dyn1_env<1, RX_PART_KIN, LV>(an, b, ang1, p1, ep1);
-        if (sorting) sort_block_tasks<1>(an, uniform(a.dyn_waves[b].perm_start), p1, ang1, cnt, stage);
-      }
-    }
   } else {
     rays_dispatch<A, LPR, LV, LPR == 4>(a, b - n_rw);  // PF: prefetched leaf scans at 4 lanes per ray
   }
@@ -2286,24 +2260,25 @@ __device__ __forceinline__ void step2_body(const rx_kargs& a, int n_rw) {
 template <int A, int RLPE, int LPR, bool LV = false>
 __global__ __launch_bounds__(64, A == 1 ? (LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW) : RX_STEP2_MINW_2) void k_step2(
     rx_kargs a, int n_rw) {
-  step2_body<A, RLPE, LPR, LV, false>(a, n_rw);
+  step2_body<A, RLPE, LPR, LV>(a, n_rw);
 }
 
-template <int LPR, bool LV = false>
-__global__ __launch_bounds__(64, LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW) void k_step2_carry(rx_kargs a, int n_rw) {
-  step2_body<1, 1, LPR, LV, true>(a, n_rw);
-}
-
-// PAIR (k_step2_pair, rx_steps' paired schedule; DESIGN.md §3 "The paired launch"): the
-// carrying launch over two steps.  REWARD workgroup b runs a program of one or two
-// sub-steps -- REWARD k, KIN k + 1, REWARD k + 1, KIN k + 2 -- as a LOOP over the same
-// dyn1_env / sort_block_tasks calls (one copy of the code), every part reading what the
-// part before stored for its own lane.  The ray workgroups cast n_rays earlier steps, the
-// older one first: ray workgroup r is record r % n_ray_waves of step r / n_ray_waves, on
-// that step's pose snapshot, task row, obs rows, row ids and hint.  Their KIN parts ran in an
-// EARLIER launch, so no wave of this launch waits on another.  A step whose re-sort is due
-// can be the second sub-step without a KIN (it writes the keys, and the row-id and hint
-// snapshots its rays are cast from after the sort; DESIGN.md §3 "The crossing step").
+// PAIR (k_step2_pair, rx_steps' carrying launch; DESIGN.md §3 "The carried step" and "The
+// paired launch"; single-agent envs, one lane per env).  REWARD workgroup b goes on, in the
+// same 64 lanes over the same 64 envs, with the KIN part of the NEXT step and the block's
+// ray-task sort -- k_kin1's work, by k_kin1's functions -- under the launch's raycast.  KIN
+// reads what REWARD has just stored for its own lane (flags, progress, episode counters: plain
+// per-lane loads after per-lane stores) and writes the next step's rows; it overwrites the
+// working pose and the task buffer, so it also stores a pose snapshot and a second copy of its
+// sorted task row, which the ray waves of ITS step read in a later launch.  A REWARD workgroup
+// runs a program of one or two such sub-steps -- REWARD k, KIN k + 1, REWARD k + 1, KIN k + 2
+// -- as a LOOP over the same dyn1_env / sort_block_tasks calls (one copy of the code), every
+// part reading what the part before stored for its own lane.  The ray workgroups cast n_rays
+// earlier steps, the older one first: ray workgroup r is record r % n_ray_waves of step r /
+// n_ray_waves, on that step's pose snapshot, task row, obs rows, row ids and hint.  Their KIN
+// parts ran in an EARLIER launch, so no wave of this launch waits on another.  A step whose
+// re-sort is due can be the second sub-step without a KIN (it writes the keys, and the row-id
+// and hint snapshots its rays are cast from after the sort; DESIGN.md §3 "The crossing step").
 // Scheduling knobs, same-session A/B at 65,536 envs (profiles/steps_pair/): issue priority of
 // the REWARD workgroups 0 / 1 / 2 / 3 = 998 / 1,047 / 1,045 / 1,045 M env-steps/s (parent
 // 1,012 M); the two steps' ray records interleaved in octets 1,080 M against 1,085 M for the
@@ -2330,9 +2305,9 @@ __device__ __forceinline__ rx_io pair_io(const rx_io& x, const rx_io& y, bool se
 
 // The launch's one kernel argument.  The REWARD workgroups re-read it through a pointer to
 // the kernarg segment that passes through an empty asm in every iteration of the sub-step
-// loop: the loads of the ~100 argument words are then the iteration's own (as in
-// k_step2_carry) instead of being hoisted out of the loop and held -- or spilled -- across
-// it (64-VGPR cap: 317 SGPRs and 63 VGPRs spilled, 168 B/lane of scratch, without this).
+// loop: the loads of the ~100 argument words are then the iteration's own (as in a kernel
+// that runs one sub-step) instead of being hoisted out of the loop and held -- or spilled --
+// across it (64-VGPR cap: 317 SGPRs and 63 VGPRs spilled, 168 B/lane of scratch, without this).
 struct rx_pair_args {
   rx_kargs a;
   rx_pair p;
@@ -2829,33 +2804,15 @@ extern "C" int rx_launch_split(const rx_kargs* a, int n_agents, int part, hipStr
   return (int)hipGetLastError();
 }
 
-// The carrying k_step2: every workgroup of the launch gets the KIN part's sort LDS (the
-// ray workgroups leave it unused), so the staging row is sized for the handle's sensors,
-// not for the 16 the sort allows: 64 + 64 R words (3 KiB at 11 sensors; 32 workgroups a
-// CU keep k_step2's 8 waves per SIMD within the CU's LDS up to 16 sensors, 4.25 KiB).
-// The launch's ray waves read a->tasks while its KIN part sorts: never into the same buffer.
-extern "C" int rx_launch_step2_carry(const rx_kargs* a, hipStream_t s) {
-  if (a->tasks_out && (a->tasks_out == a->tasks || a->tasks_snap == a->tasks)) return (int)hipErrorInvalidValue;
-  const int n_rw = (a->n_dyn_waves + 7) / 8 * 8;
-  const dim3 grid(n_rw + a->n_ray_waves);
-  const size_t lds = a->tasks_out ? (size_t)(kTaskSectors + 64 * a->n_sensors) * sizeof(int32_t) : 0;
-  if (a->lane_tracks)
-    hipLaunchKernelGGL((k_step2_carry<1, true>), grid, dim3(64), lds, s, *a, n_rw);
-  else if (a->ray_lpr == 4)
-    hipLaunchKernelGGL((k_step2_carry<4>), grid, dim3(64), lds, s, *a, n_rw);
-  else if (a->ray_lpr == 2)
-    hipLaunchKernelGGL((k_step2_carry<2>), grid, dim3(64), lds, s, *a, n_rw);
-  else
-    hipLaunchKernelGGL((k_step2_carry<1>), grid, dim3(64), lds, s, *a, n_rw);
-  return (int)hipGetLastError();
-}
-
 // The paired k_step2: n_rw REWARD workgroups, then n_rays copies of the ray table (n_ray_waves
-// is a multiple of 8, so both copies keep the group -> XCD placement); the sort's LDS as the
-// carrying launch sizes it.  Checked here, on the host: no KIN part of the launch stores a
-// pose snapshot or sorts a task row that one of the launch's ray steps reads, two ray
-// steps never write the same obs rows, and no ray step reads a row-id or hint snapshot that
-// the launch's key-writing REWARD stores (those are its OWN step's, cast by a later launch).
+// is a multiple of 8, so both copies keep the group -> XCD placement).  Every workgroup of the
+// launch gets the KIN part's sort LDS (the ray workgroups leave it unused), so the staging row
+// is sized for the handle's sensors, not for the 16 the sort allows: 64 + 64 R words (3 KiB at
+// 11 sensors; 32 workgroups a CU keep k_step2's 8 waves per SIMD within the CU's LDS up to 16
+// sensors, 4.25 KiB).  Checked here, on the host: no KIN part of the launch stores a pose
+// snapshot or sorts a task row that one of the launch's ray steps reads, two ray steps never
+// write the same obs rows, and no ray step reads a row-id or hint snapshot that the launch's
+// key-writing REWARD stores (those are its OWN step's, cast by a later launch).
 // rx_pair_layout: sizes and offsets for a caller that fills the two structs as bytes (the
 // refusal test): 0 / 1-3 = sizeof rx_kargs / its sort_keys, rows_snap, hint_snap; 4 / 5-9 =
 // sizeof rx_pair / its n_sub, n_rays, ray_obs, ray_rows, ray_hint; else -1.

@@ -133,6 +133,18 @@ def test_schedule_config_is_validated_and_the_library_reads_no_environment():
         assert knob not in strings, knob
 
 
+def test_one_carrying_launcher_is_exported():
+    """rx_steps has one carrying schedule: the library exports the paired launcher and its
+    layout query, and the launcher of the retired carried kernel is gone."""
+    import subprocess
+    from rx import _build
+    _build.build(verbose=False)
+    out = subprocess.run(["nm", "-D", "--defined-only", _build.LIB], capture_output=True, text=True, check=True)
+    syms = {ln.split()[-1].split("@")[0] for ln in out.stdout.splitlines() if ln.strip()}
+    assert "rx_launch_step2_pair" in syms and "rx_pair_layout" in syms
+    assert "rx_launch_step2_carry" not in syms
+
+
 def test_default_sort_interval():
     """rx.vector_env.default_sort_interval: re-sort every 8 dynamics launches for
     single-agent envs above 32,768, every 16 elsewhere (profiles/r04/probe_sort_interval.txt)."""

@@ -2,8 +2,8 @@
 
 With the actions of all K steps on the device, rx_steps runs the KIN part of step
 k + 1 (autoreset, kinematics, non-ray obs columns, the block's ray-task sort) in the
-REWARD waves of step k's k_step2 (k_step2_carry) and the ray waves read a two-deep
-snapshot of the stepped pose and the task rows.  Only the place the work runs
+REWARD waves of step k's launch (k_step2_pair) and the ray waves read a ring of
+snapshots of the stepped pose and the task rows.  Only the place the work runs
 changes, so ``steps_device(actions[K])`` must equal K x ``step_device`` on a twin env
 BIT FOR BIT: every step's obs / reward / done rows, the info and mask rows, the
 episode statistics and the whole state -- on carried steps, on re-sort steps (which
@@ -207,8 +207,9 @@ def test_task_sort2_first_sort_of_a_call_is_carried(golden):
     still start after the REWARD+KIN waves have sorted.  After a reset the first call
     begins between two sorts: its ray waves read the handle's task buffer and the
     call's first sort runs carried -- it must not land on the rows those waves read
-    (it writes the snapshot alone; rx_launch_step2_carry refuses a launch that reads
-    the buffer it sorts into, so a regression fails here whatever the timing).  The
+    (it writes the snapshot alone; rx_launch_step2_pair refuses a launch that reads
+    the buffer it sorts into, as tests/test_steps_cross_gpu.py checks of its other
+    refusals, so a regression fails here whatever the timing).  The
     second call begins on a sort.  steps_device(5), steps_device(4) == 9 per-step
     calls; the return sum to 1e-9 as in test_many_blocks_per_xcd (16 waves a shard)."""
     N = 65536
