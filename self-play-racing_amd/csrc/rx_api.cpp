@@ -1367,115 +1367,235 @@ int rx_rollout_supported(const rx_env* h) {
          max_waypoints(h) <= RX_ROLLOUT_MAX_W;
 }
 
+// ---- the step loops: the argument checks of their entry points, each written once.
+// fn is the entry point's name; every check returns before any HIP call.
+static int precision_arg(const char* fn, const char* field, int32_t precision) {
+  if (precision != RX_PREC_FP32 && precision != RX_PREC_BF16)
+    return fail(RX_EINVAL, "%s: %s=%d (RX_PREC_FP32 or RX_PREC_BF16)", fn, field, precision);
+  return RX_OK;
+}
+
+static int rollout_dims(const char* fn, const rx_env* h, const rx_rollout_io* r) {
+  if (r->T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, r->T);
+  if (r->obs_dim != h->D) return fail(RX_EINVAL, "%s: obs_dim %d != the handle's %d", fn, r->obs_dim, h->D);
+  return RX_OK;
+}
+
+static int rollout_bufs(const char* fn, const rx_rollout_io* r) {
+  const char* null = !r->params ? "params" : !r->log_std ? "log_std" : !r->eps ? "eps" : !r->obs ? "obs"
+                     : !r->actions ? "actions" : !r->logprobs ? "logprobs" : !r->values ? "values"
+                     : !r->rewards ? "rewards" : !r->dones ? "dones" : !r->next_obs ? "next_obs"
+                     : !r->next_done ? "next_done" : nullptr;
+  return null ? fail(RX_EINVAL, "%s: null rollout buffer %s", fn, null) : RX_OK;
+}
+
+// bank: the opponents' parameters come from a league io, so opp_params / opp_log_std are not read
+static int selfplay_bufs(const char* fn, const rx_selfplay_io* sp, bool bank) {
+  const char* null = !bank && !sp->opp_params ? "opp_params" : !bank && !sp->opp_log_std ? "opp_log_std"
+                     : !sp->opp_eps ? "opp_eps" : !sp->env_actions ? "env_actions" : !sp->env_obs ? "env_obs"
+                     : !sp->env_reward ? "env_reward" : !sp->sink ? "sink" : nullptr;
+  return null ? fail(RX_EINVAL, "%s: null self-play buffer %s", fn, null) : RX_OK;
+}
+
+// the evaluation record, and the io rows k_eval_acc reads
+static int record_args(const char* fn, const rx_io* io, const double* acc, const uint8_t* active,
+                       const int32_t* n_active) {
+  if (!acc || !active || !n_active)
+    return fail(RX_EINVAL, "%s: null %s", fn, !acc ? "acc" : !active ? "active" : "n_active");
+  if (!io->obs || !io->reward64 || !io->info || !io->done_f32)
+    return fail(RX_EINVAL, "%s: null io->%s", fn,
+                !io->obs ? "obs" : !io->reward64 ? "reward64" : !io->info ? "info" : "done_f32");
+  return RX_OK;
+}
+
+// bf16 with parameters that are fixed for the whole call: their operand fragments are built once
+// (k_policy_frag) and every step's policy launch reads them -- the same bf16 values rx_policy_act
+// converts per use.  *frag stays null for fp32.
+static int policy_fragments(const char* fn, rx_env* h, int32_t obs_dim, const float* params, int32_t precision,
+                            hipStream_t s, const void** frag) {
+  *frag = nullptr;
+  if (precision != RX_PREC_BF16) return RX_OK;
+  if (rx_launch_policy_frag(obs_dim, params, h->policy_frag.p, s))
+    return fail(RX_EHIP, "%s: fragment launch failed", fn);
+  *frag = h->policy_frag.p;
+  return RX_OK;
+}
+
 int rx_rollout(rx_env* h, const rx_io* io, const rx_rollout_io* r, void* stream) {
   if (!h || !io || !r) return fail(RX_EINVAL, "rx_rollout: null argument");
   if (!rx_rollout_supported(h))
     return fail(RX_ESTATE, "rx_rollout: needs an assigned, bound single-agent handle in the small-N (one env per "
                            "wave) configuration with 15 or 19 observation columns and <= %d waypoints per slot",
                 RX_ROLLOUT_MAX_W);
-  if (r->T <= 0) return fail(RX_EINVAL, "rx_rollout: T=%d must be > 0", r->T);
-  if (r->obs_dim != h->D) return fail(RX_EINVAL, "rx_rollout: obs_dim %d != the handle's %d", r->obs_dim, h->D);
-  if (!r->params || !r->log_std || !r->eps || !r->obs || !r->actions || !r->logprobs || !r->values || !r->rewards ||
-      !r->dones || !r->next_obs || !r->next_done)
-    return fail(RX_EINVAL, "rx_rollout: null rollout buffer");
+  int rc;
+  if ((rc = rollout_dims("rx_rollout", h, r)) != 0 || (rc = rollout_bufs("rx_rollout", r)) != 0) return rc;
   if (h->n_dyn_waves != h->cfg.n_envs) return fail(RX_ESTATE, "rx_rollout: expected one env per dynamics wave");
   rx_kargs a{};
   make_kargs(h, io, RX_MODE_STEP, nullptr, a);
   a.sort_keys = nullptr;
   a.tasks_out = nullptr;
   a.prof_ts = nullptr;
-  int rc;
   if ((rc = rx_launch_rollout(&a, r, max_waypoints(h), (hipStream_t)stream)) != 0)
     return fail(RX_EHIP, "k_rollout launch failed: %s", hipGetErrorString((hipError_t)rc));
   return RX_OK;
 }
 
-int rx_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, int32_t precision, void* stream) {
-  if (!h || !io || !r) return fail(RX_EINVAL, "rx_rollout_steps: null argument");
-  if (!h->assigned || !h->bound) return fail(RX_ESTATE, "rx_rollout_steps: needs an assigned, bound handle");
-  if (h->cfg.n_agents != 1) return fail(RX_EINVAL, "rx_rollout_steps: single-agent handles only");
-  if (r->T <= 0) return fail(RX_EINVAL, "rx_rollout_steps: T=%d must be > 0", r->T);
-  if (r->obs_dim != h->D) return fail(RX_EINVAL, "rx_rollout_steps: obs_dim %d != the handle's %d", r->obs_dim, h->D);
-  if (!r->params || !r->log_std || !r->eps || !r->obs || !r->actions || !r->logprobs || !r->values || !r->rewards ||
-      !r->dones || !r->next_obs || !r->next_done)
-    return fail(RX_EINVAL, "rx_rollout_steps: null rollout buffer");
-  if (precision != RX_PREC_FP32 && precision != RX_PREC_BF16)
-    return fail(RX_EINVAL, "rx_rollout_steps: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", precision);
+// The single-agent rollout loop: per step rx_policy_act on obs[t], then rx_step of actions[t] writing
+// obs[t + 1], rewards[t] and dones[t + 1] (next_obs / next_done after the last).  tc == null is
+// rx_rollout_steps; with tc, rx_track_rollout_steps: one k_track_tally after every step, which reads
+// the done row the step just wrote and the env's terminated / info rows before the next step
+// overwrites them (one stream).  The policy and env launches are the same either way.
+static int rollout_loop(const char* fn, rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
+                        int32_t precision, void* stream) {
   const int64_t N = h->cfg.n_envs, D = h->D;
-  // bf16: the parameters are fixed for the whole rollout, so their bf16 operand
-  // fragments are built once (k_policy_frag) and every step's policy launch
-  // reads them -- the same bf16 values rx_policy_act converts per use
-  const void* frag = nullptr;
-  if (precision == RX_PREC_BF16) {
-    if (rx_launch_policy_frag(r->obs_dim, r->params, h->policy_frag.p, (hipStream_t)stream))
-      return fail(RX_EHIP, "rx_rollout_steps: fragment launch failed");
-    frag = h->policy_frag.p;
-  }
+  hipStream_t hs = (hipStream_t)stream;
+  const void* frag;
+  int rc = policy_fragments(fn, h, r->obs_dim, r->params, precision, hs, &frag);
+  if (rc) return rc;
   for (int32_t t = 0; t < r->T; ++t) {
     const bool last = t + 1 == r->T;
     const rx_policy_io pio{r->obs_dim, N, r->obs + t * N * D, r->eps + t * N * 2, r->params, r->log_std,
                            r->actions + t * N * 2, r->logprobs + t * N, r->values + t * N, 0, 0, precision,
                            nullptr, 0};
-    int rc = rx_launch_policy_act(&pio, (hipStream_t)stream, frag);
-    if (rc) return fail(RX_EHIP, "rx_rollout_steps: policy launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if ((rc = rx_launch_policy_act(&pio, hs, frag)) != 0)
+      return fail(RX_EHIP, "%s: policy launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
     rx_io s = *io;
     s.actions = r->actions + t * N * 2;
     s.obs = last ? r->next_obs : r->obs + (t + 1) * N * D;
     s.reward = r->rewards + t * N;
     s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;
     if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
+    if (tc && (rc = rx_launch_track_tally(tc, N, s.done_f32, io->terminated, io->info, hs)) != 0)
+      return fail(RX_EHIP, "%s: tally launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
   }
   return RX_OK;
 }
 
-int rx_selfplay_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
-                              int32_t precision, void* stream) {
-  if (!h || !io || !r || !sp) return fail(RX_EINVAL, "rx_selfplay_rollout_steps: null argument");
-  if (!h->assigned || !h->bound) return fail(RX_ESTATE, "rx_selfplay_rollout_steps: needs an assigned, bound handle");
-  if (h->cfg.n_agents != 2) return fail(RX_EINVAL, "rx_selfplay_rollout_steps: two-car handles only");
-  if (r->T <= 0) return fail(RX_EINVAL, "rx_selfplay_rollout_steps: T=%d must be > 0", r->T);
-  if (r->obs_dim != h->D) return fail(RX_EINVAL, "rx_selfplay_rollout_steps: obs_dim %d != the handle's %d", r->obs_dim, h->D);
-  if (sp->agent != 0 && sp->agent != 1) return fail(RX_EINVAL, "rx_selfplay_rollout_steps: agent must be 0 or 1");
-  if (!r->params || !r->log_std || !r->eps || !r->obs || !r->actions || !r->logprobs || !r->values || !r->rewards ||
-      !r->dones || !r->next_obs || !r->next_done || !sp->opp_params || !sp->opp_log_std || !sp->opp_eps ||
-      !sp->env_actions || !sp->env_obs || !sp->env_reward || !sp->sink)
-    return fail(RX_EINVAL, "rx_selfplay_rollout_steps: null buffer");
-  if (h->D != 19) return fail(RX_EINVAL, "rx_selfplay_rollout_steps: obs_dim %d (19)", h->D);
-  if ((precision != RX_PREC_FP32 && precision != RX_PREC_BF16) ||
-      (sp->opp_precision != RX_PREC_FP32 && sp->opp_precision != RX_PREC_BF16))
-    return fail(RX_EINVAL, "rx_selfplay_rollout_steps: precision %d / opponent %d", precision, sp->opp_precision);
+// The two-car rollout loop: per step ONE launch for both policies, then rx_step on the env's own
+// buffers; one agent-row copy after the last step.  The opponent's actor runs on its rows of the
+// env's observation buffer (wrappers.py:36-39), actions into its slot of the env's action buffer;
+// the learning agent on obs[t] -- the caller's rows at t = 0 (they may predate an env rebuild),
+// afterwards its rows of the env's buffer, which the launch also copies into obs[t] together with
+// the agent's reward of step t - 1 -- actions into the rollout row and its env slot.
+// lg == null is rx_selfplay_rollout_steps (k_selfplay_act, one frozen opponent).  With lg,
+// rx_league_rollout_steps (k_league_act): env e's opponent is bank member lg->opp_id[e], the
+// opponent's params / log_std are the bank bases, and the tally and redraw of step t's done flags
+// is folded into step t + 1's launch (its opponent waves are the only readers of the ids), so one
+// k_league_draw per rollout remains, for the last step.  RX_LEAGUE_FOLD=0 (an A/B build,
+// tools/bench_league_train.py) launches k_league_draw after every step instead: the same bits,
+// one more launch per step.
+#ifndef RX_LEAGUE_FOLD
+#define RX_LEAGUE_FOLD 1
+#endif
+static int two_car_rollout_loop(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
+                                const rx_league_io* lg, int32_t precision, void* stream) {
   const int64_t N = h->cfg.n_envs, D = h->D;
   const int q = sp->agent, o = 1 - q;
   hipStream_t hs = (hipStream_t)stream;
+  int rc;
   for (int32_t t = 0; t < r->T; ++t) {
     const bool last = t + 1 == r->T;
-    // ONE launch for both policies (k_selfplay_act): the frozen opponent's actor on
-    // its rows of the env's observation buffer (wrappers.py:36-39), actions into its
-    // slot of the env's action buffer; the learning agent on obs[t] -- the caller's
-    // rows at t = 0 (they may predate an env rebuild), afterwards its rows of the
-    // env's buffer, which the launch also copies into obs[t] together with the
-    // agent's reward of step t - 1 -- actions into the rollout row and its env slot
-    const rx_policy_io opp{(int32_t)D, N, sp->env_obs + o * D, sp->opp_eps + t * N * 2, sp->opp_params,
-                           sp->opp_log_std, sp->env_actions + 2 * o, nullptr, sp->sink, 2 * D, 4,
-                           sp->opp_precision, nullptr, 0};
+    const rx_policy_io opp{(int32_t)D, N, sp->env_obs + o * D, sp->opp_eps + t * N * 2,
+                           lg ? lg->params : sp->opp_params, lg ? lg->log_std : sp->opp_log_std,
+                           sp->env_actions + 2 * o, nullptr, sp->sink, 2 * D, 4,
+                           lg ? lg->opp_precision : sp->opp_precision, nullptr, 0};
     const rx_policy_io pio{(int32_t)D, N, t == 0 ? r->obs : sp->env_obs + q * D, r->eps + t * N * 2, r->params,
                            r->log_std, r->actions + t * N * 2, r->logprobs + t * N, r->values + t * N,
                            t == 0 ? 0 : 2 * D, 0, precision, sp->env_actions + 2 * q, 4};
-    int rc = rx_launch_selfplay_act(&pio, &opp, t == 0 ? nullptr : r->obs + t * N * D, sp->env_reward,
-                                    t == 0 ? nullptr : r->rewards + (t - 1) * N, q, hs);
-    if (rc) return fail(RX_EHIP, "self-play policy launch failed: %s", hipGetErrorString((hipError_t)rc));
+    float* obs_out = t == 0 ? nullptr : r->obs + t * N * D;
+    float* rew_out = t == 0 ? nullptr : r->rewards + (t - 1) * N;
+    if (lg) {
+      // io->info still holds step t - 1's rows here: rx_step writes it after this launch
+      const bool fold = RX_LEAGUE_FOLD && t > 0;
+      rc = rx_launch_league_act(&pio, &opp, lg, fold ? r->dones + t * N : nullptr, fold ? io->info : nullptr,
+                                obs_out, sp->env_reward, rew_out, hs);
+    } else {
+      rc = rx_launch_selfplay_act(&pio, &opp, obs_out, sp->env_reward, rew_out, q, hs);
+    }
+    if (rc)
+      return fail(RX_EHIP, "%s policy launch failed: %s", lg ? "league" : "self-play",
+                  hipGetErrorString((hipError_t)rc));
     rx_io s = *io;
     s.actions = sp->env_actions;
     s.obs = sp->env_obs;
     s.reward = sp->env_reward;
     s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;  // dones['__all__'] (wrappers.py:51)
     if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
+    // the envs that ended: count the result against their opponent, draw the next one
+    if (lg && (last || !RX_LEAGUE_FOLD) && (rc = rx_launch_league_draw(lg, N, s.done_f32, io->info, hs)) != 0)
+      return fail(RX_EHIP, "league draw launch failed: %s", hipGetErrorString((hipError_t)rc));
   }
   // the last step's agent rows: next_obs and rewards[T - 1]
-  const int rc = rx_launch_agent_rows((int)N, (int)D, q, sp->env_obs, sp->env_reward, r->next_obs,
-                                      r->rewards + (r->T - 1) * N, hs);
+  rc = rx_launch_agent_rows((int)N, (int)D, q, sp->env_obs, sp->env_reward, r->next_obs, r->rewards + (r->T - 1) * N,
+                            hs);
   if (rc) return fail(RX_EHIP, "agent-row copy launch failed: %s", hipGetErrorString((hipError_t)rc));
   return RX_OK;
+}
+
+// The accumulating loop of an evaluation: per step the policy launch (if any), rx_step of actions[t]
+// in place, k_eval_acc.  ev.params == null is open loop (the caller's actions); with m the policy
+// launch is the bank's (car q of env e on policy m->seat[e][q]), else rx_policy_act over all N * A
+// rows -- both cars of a two-car env are rows of the same launch: one policy drives them
+// (utils/metrics.py:94-101).  ev holds the fields rx_eval_io and rx_match_io share.
+static int record_loop(const char* fn, rx_env* h, const rx_io* io, const rx_eval_io& ev, const rx_match_io* m,
+                       int32_t n_steps, void* stream) {
+  const int64_t N = h->cfg.n_envs, A = h->cfg.n_agents, NA = N * A;
+  hipStream_t hs = (hipStream_t)stream;
+  const void* frag = nullptr;
+  int rc;
+  if (ev.params && !m && (rc = policy_fragments(fn, h, ev.obs_dim, ev.params, ev.precision, hs, &frag)) != 0)
+    return rc;
+  for (int32_t t = 0; t < n_steps; ++t) {
+    float* act = ev.actions + (int64_t)t * NA * 2;
+    if (ev.params) {
+      const rx_policy_io pio{ev.obs_dim, NA, io->obs, ev.eps + (int64_t)t * NA * 2, ev.params, ev.log_std, act,
+                             ev.logp_sink, ev.value_sink, 0, 0, ev.precision, nullptr, 0};
+      if (m) {
+        const rx_policy_bank_io b{pio, m->n_policies, (int32_t)A, m->params_stride, m->seat};
+        rc = rx_launch_policy_act_bank(&b, hs);
+      } else {
+        rc = rx_launch_policy_act(&pio, hs, frag);
+      }
+      if (rc) return fail(RX_EHIP, "%s: policy launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+    }
+    rx_io s = *io;
+    s.actions = act;
+    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
+    // after launch(): its re-sort (if any) has been enqueued, so perm and the working rows agree
+    if ((rc = rx_launch_eval_acc((int)N, (int)A, h->perm[0].p, &h->work, io, ev.acc, ev.active, ev.n_active,
+                                 hs)) != 0)
+      return fail(RX_EHIP, "k_eval_acc launch failed: %s", hipGetErrorString((hipError_t)rc));
+  }
+  return RX_OK;
+}
+
+int rx_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, int32_t precision, void* stream) {
+  const char* fn = "rx_rollout_steps";
+  if (!h || !io || !r) return fail(RX_EINVAL, "%s: null argument", fn);
+  if (!h->assigned || !h->bound) return fail(RX_ESTATE, "%s: needs an assigned, bound handle", fn);
+  if (h->cfg.n_agents != 1) return fail(RX_EINVAL, "%s: single-agent handles only", fn);
+  int rc;
+  if ((rc = rollout_dims(fn, h, r)) != 0 || (rc = rollout_bufs(fn, r)) != 0 ||
+      (rc = precision_arg(fn, "precision", precision)) != 0)
+    return rc;
+  return rollout_loop(fn, h, io, r, nullptr, precision, stream);
+}
+
+int rx_selfplay_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
+                              int32_t precision, void* stream) {
+  const char* fn = "rx_selfplay_rollout_steps";
+  if (!h || !io || !r || !sp) return fail(RX_EINVAL, "%s: null argument", fn);
+  if (!h->assigned || !h->bound) return fail(RX_ESTATE, "%s: needs an assigned, bound handle", fn);
+  if (h->cfg.n_agents != 2) return fail(RX_EINVAL, "%s: two-car handles only", fn);
+  int rc = rollout_dims(fn, h, r);
+  if (rc) return rc;
+  if (sp->agent != 0 && sp->agent != 1) return fail(RX_EINVAL, "%s: agent=%d must be 0 or 1", fn, sp->agent);
+  if ((rc = rollout_bufs(fn, r)) != 0 || (rc = selfplay_bufs(fn, sp, false)) != 0) return rc;
+  if (h->D != 19) return fail(RX_EINVAL, "%s: obs_dim %d (19)", fn, h->D);
+  if ((rc = precision_arg(fn, "precision", precision)) != 0 ||
+      (rc = precision_arg(fn, "opp_precision", sp->opp_precision)) != 0)
+    return rc;
+  return two_car_rollout_loop(h, io, r, sp, nullptr, precision, stream);
 }
 
 // ABI v25: an evaluation's step loop (policy or open-loop actions, rx_step, k_eval_acc
@@ -1486,17 +1606,12 @@ int rx_eval_steps(rx_env* h, const rx_io* io, const rx_eval_io* ev, int32_t n_st
   if (!ev) return fail(RX_EINVAL, "rx_eval_steps: null ev");
   if (n_steps <= 0) return fail(RX_EINVAL, "rx_eval_steps: n_steps=%d must be > 0", n_steps);
   if (!ev->actions) return fail(RX_EINVAL, "rx_eval_steps: null actions");
-  if (!ev->acc || !ev->active || !ev->n_active)
-    return fail(RX_EINVAL, "rx_eval_steps: null %s", !ev->acc ? "acc" : !ev->active ? "active" : "n_active");
-  if (!io->obs || !io->reward64 || !io->info || !io->done_f32)
-    return fail(RX_EINVAL, "rx_eval_steps: null io->%s",
-                !io->obs ? "obs" : !io->reward64 ? "reward64" : !io->info ? "info" : "done_f32");
-  const bool policy = ev->params != nullptr;
-  if (policy) {
+  int rc = record_args("rx_eval_steps", io, ev->acc, ev->active, ev->n_active);
+  if (rc) return rc;
+  if (ev->params) {  // policy mode
     if (ev->obs_dim != 15 && ev->obs_dim != 19)
       return fail(RX_EINVAL, "rx_eval_steps: obs_dim=%d has no policy kernel (15 or 19)", ev->obs_dim);
-    if (ev->precision != RX_PREC_FP32 && ev->precision != RX_PREC_BF16)
-      return fail(RX_EINVAL, "rx_eval_steps: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", ev->precision);
+    if ((rc = precision_arg("rx_eval_steps", "precision", ev->precision)) != 0) return rc;
     if (!ev->log_std || !ev->eps || !ev->logp_sink || !ev->value_sink)
       return fail(RX_EINVAL, "rx_eval_steps: null %s (policy mode)",
                   !ev->log_std ? "log_std" : !ev->eps ? "eps" : !ev->logp_sink ? "logp_sink" : "value_sink");
@@ -1505,33 +1620,7 @@ int rx_eval_steps(rx_env* h, const rx_io* io, const rx_eval_io* ev, int32_t n_st
   if (ev->obs_dim != h->D) return fail(RX_EINVAL, "rx_eval_steps: obs_dim %d != the handle's %d", ev->obs_dim, h->D);
   if (h->n_tracks <= 0 || !h->assigned || !h->bound)
     return fail(RX_ESTATE, "rx_eval_steps: needs an assigned, bound handle");
-  const int64_t N = h->cfg.n_envs, A = h->cfg.n_agents, NA = N * A;
-  hipStream_t hs = (hipStream_t)stream;
-  const void* frag = nullptr;
-  if (policy && ev->precision == RX_PREC_BF16) {  // fixed parameters: bf16 operand fragments once per call
-    if (rx_launch_policy_frag(ev->obs_dim, ev->params, h->policy_frag.p, hs))
-      return fail(RX_EHIP, "rx_eval_steps: fragment launch failed");
-    frag = h->policy_frag.p;
-  }
-  int rc;
-  for (int32_t t = 0; t < n_steps; ++t) {
-    float* act = ev->actions + (int64_t)t * NA * 2;
-    if (policy) {
-      // both cars of a two-car env are rows of the same launch: one policy drives them (utils/metrics.py:94-101)
-      const rx_policy_io pio{ev->obs_dim, NA, io->obs, ev->eps + (int64_t)t * NA * 2, ev->params, ev->log_std, act,
-                             ev->logp_sink, ev->value_sink, 0, 0, ev->precision, nullptr, 0};
-      if ((rc = rx_launch_policy_act(&pio, hs, frag)) != 0)
-        return fail(RX_EHIP, "rx_eval_steps: policy launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    rx_io s = *io;
-    s.actions = act;
-    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
-    // after launch(): its re-sort (if any) has been enqueued, so perm and the working rows agree
-    if ((rc = rx_launch_eval_acc((int)N, (int)A, h->perm[0].p, &h->work, io, ev->acc, ev->active, ev->n_active,
-                                 hs)) != 0)
-      return fail(RX_EHIP, "k_eval_acc launch failed: %s", hipGetErrorString((hipError_t)rc));
-  }
-  return RX_OK;
+  return record_loop("rx_eval_steps", h, io, *ev, nullptr, n_steps, stream);
 }
 
 // ABI v25, additive: rx_eval_steps' policy mode with a seating -- per step one bank launch
@@ -1543,8 +1632,8 @@ int rx_match_steps(rx_env* h, const rx_io* io, const rx_match_io* m, int32_t n_s
   if (n_steps <= 0) return fail(RX_EINVAL, "rx_match_steps: n_steps=%d must be > 0", n_steps);
   if (m->obs_dim != 15 && m->obs_dim != 19)
     return fail(RX_EINVAL, "rx_match_steps: obs_dim=%d has no policy kernel (15 or 19)", m->obs_dim);
-  if (m->precision != RX_PREC_FP32 && m->precision != RX_PREC_BF16)
-    return fail(RX_EINVAL, "rx_match_steps: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", m->precision);
+  int rc = precision_arg("rx_match_steps", "precision", m->precision);
+  if (rc) return rc;
   if (m->n_policies <= 0) return fail(RX_EINVAL, "rx_match_steps: n_policies=%d must be > 0", m->n_policies);
   if (m->params_stride < rx_ppo_n_params(m->obs_dim))
     return fail(RX_EINVAL, "rx_match_steps: params_stride=%lld < the %d parameters of obs_dim %d",
@@ -1553,35 +1642,16 @@ int rx_match_steps(rx_env* h, const rx_io* io, const rx_match_io* m, int32_t n_s
     return fail(RX_EINVAL, "rx_match_steps: null %s",
                 !m->params ? "params" : !m->log_std ? "log_std" : !m->eps ? "eps" : !m->seat ? "seat"
                 : !m->actions ? "actions" : !m->logp_sink ? "logp_sink" : "value_sink");
-  if (!m->acc || !m->active || !m->n_active)
-    return fail(RX_EINVAL, "rx_match_steps: null %s", !m->acc ? "acc" : !m->active ? "active" : "n_active");
-  if (!io->obs || !io->reward64 || !io->info || !io->done_f32)
-    return fail(RX_EINVAL, "rx_match_steps: null io->%s",
-                !io->obs ? "obs" : !io->reward64 ? "reward64" : !io->info ? "info" : "done_f32");
+  if ((rc = record_args("rx_match_steps", io, m->acc, m->active, m->n_active)) != 0) return rc;
   // from here on the handle is read
   if (m->obs_dim != h->D) return fail(RX_EINVAL, "rx_match_steps: obs_dim %d != the handle's %d", m->obs_dim, h->D);
   if (h->n_tracks <= 0 || !h->assigned || !h->bound)
     return fail(RX_ESTATE, "rx_match_steps: needs an assigned, bound handle");
-  const int64_t N = h->cfg.n_envs, A = h->cfg.n_agents, NA = N * A;
-  if (A != 1 && A != 2) return fail(RX_EINVAL, "rx_match_steps: n_agents=%d (1 or 2)", (int)A);
-  hipStream_t hs = (hipStream_t)stream;
-  int rc;
-  for (int32_t t = 0; t < n_steps; ++t) {
-    float* act = m->actions + (int64_t)t * NA * 2;
-    const rx_policy_bank_io b{{m->obs_dim, NA, io->obs, m->eps + (int64_t)t * NA * 2, m->params, m->log_std, act,
-                               m->logp_sink, m->value_sink, 0, 0, m->precision, nullptr, 0},
-                              m->n_policies, (int32_t)A, m->params_stride, m->seat};
-    if ((rc = rx_launch_policy_act_bank(&b, hs)) != 0)
-      return fail(RX_EHIP, "rx_match_steps: policy launch failed: %s", hipGetErrorString((hipError_t)rc));
-    rx_io s = *io;
-    s.actions = act;
-    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
-    // after launch(): its re-sort (if any) has been enqueued, so perm and the working rows agree
-    if ((rc = rx_launch_eval_acc((int)N, (int)A, h->perm[0].p, &h->work, io, m->acc, m->active, m->n_active,
-                                 hs)) != 0)
-      return fail(RX_EHIP, "k_eval_acc launch failed: %s", hipGetErrorString((hipError_t)rc));
-  }
-  return RX_OK;
+  if (h->cfg.n_agents != 1 && h->cfg.n_agents != 2)
+    return fail(RX_EINVAL, "rx_match_steps: n_agents=%d (1 or 2)", h->cfg.n_agents);
+  const rx_eval_io ev{m->obs_dim, m->precision, m->params, m->log_std, m->eps, m->actions, m->logp_sink,
+                      m->value_sink, m->acc, m->active, m->n_active};
+  return record_loop("rx_match_steps", h, io, ev, m, n_steps, stream);
 }
 
 static int gae(int32_t T, int32_t N, const float* r, const float* v, const float* d, const float* nv, const float* nd,
@@ -1964,8 +2034,7 @@ static int check_ppo_batch(const rx_ppo_batch* b) {
   if (!b) return fail(RX_EINVAL, "rx_ppo: batch is null");
   if (b->obs_dim != 15 && b->obs_dim != 19) return fail(RX_EINVAL, "rx_ppo: obs_dim=%d (15 or 19)", b->obs_dim);
   if (b->mb <= 0 || b->n_rows <= 0) return fail(RX_EINVAL, "rx_ppo: mb=%d n_rows=%lld", b->mb, (long long)b->n_rows);
-  if (b->precision != RX_PREC_FP32 && b->precision != RX_PREC_BF16)
-    return fail(RX_EINVAL, "rx_ppo: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", b->precision);
+  if (precision_arg("rx_ppo", "precision", b->precision)) return RX_EINVAL;
   if (!b->obs || !b->actions || !b->logprobs || !b->advantages || !b->returns || !b->values || !b->perm ||
       !b->params || !b->log_std)
     return fail(RX_EINVAL, "rx_ppo: null buffer");
@@ -2095,8 +2164,7 @@ int rx_policy_act(const rx_policy_io* io, void* stream) {
   if (!io) return fail(RX_EINVAL, "rx_policy_act: io is null");
   if (io->obs_dim != 15 && io->obs_dim != 19) return fail(RX_EINVAL, "rx_policy_act: obs_dim=%d (15 or 19)", io->obs_dim);
   if (io->n <= 0) return fail(RX_EINVAL, "rx_policy_act: n=%lld", (long long)io->n);
-  if (io->precision != RX_PREC_FP32 && io->precision != RX_PREC_BF16)
-    return fail(RX_EINVAL, "rx_policy_act: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", io->precision);
+  if (precision_arg("rx_policy_act", "precision", io->precision)) return RX_EINVAL;
   if ((io->obs_stride != 0 && io->obs_stride < io->obs_dim) || (io->act_stride != 0 && io->act_stride < 2) ||
       (io->act2_stride != 0 && io->act2_stride < 2))
     return fail(RX_EINVAL, "rx_policy_act: row strides overlap (obs %lld, act %lld)", (long long)io->obs_stride,
@@ -2119,8 +2187,7 @@ int rx_policy_act_bank(const rx_policy_bank_io* b, void* stream) {
   if (b->params_stride < rx_ppo_n_params(io->obs_dim))
     return fail(RX_EINVAL, "rx_policy_act_bank: params_stride=%lld < the %d parameters of obs_dim %d",
                 (long long)b->params_stride, rx_ppo_n_params(io->obs_dim), io->obs_dim);
-  if (io->precision != RX_PREC_FP32 && io->precision != RX_PREC_BF16)
-    return fail(RX_EINVAL, "rx_policy_act_bank: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", io->precision);
+  if (precision_arg("rx_policy_act_bank", "precision", io->precision)) return RX_EINVAL;
   if ((b->tile_cars != 1 && b->tile_cars != 2) || (b->tile_cars == 2 && (io->n & 1)))
     return fail(RX_EINVAL, "rx_policy_act_bank: tile_cars=%d (1, or 2 with an even n; n=%lld)", b->tile_cars,
                 (long long)io->n);
@@ -2153,9 +2220,7 @@ static int league_args(const char* fn, const rx_league_io* lg, int what) {
   if (lg->params_stride < rx_ppo_n_params(19))
     return fail(RX_EINVAL, "%s: params_stride=%lld < the %d parameters of obs_dim 19", fn,
                 (long long)lg->params_stride, rx_ppo_n_params(19));
-  if (lg->opp_precision != RX_PREC_FP32 && lg->opp_precision != RX_PREC_BF16)
-    return fail(RX_EINVAL, "%s: opp_precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", fn, lg->opp_precision);
-  return RX_OK;
+  return precision_arg(fn, "opp_precision", lg->opp_precision);
 }
 
 static int league_weights_args(const char* fn, const rx_league_io* lg, int32_t n_live, int32_t power, double mix,
@@ -2209,69 +2274,24 @@ int rx_league_draw_host(const rx_league_io* lg, int64_t n, const float* done, co
   return RX_OK;
 }
 
-// rx_selfplay_rollout_steps with a per-env opponent.  Per step: k_league_act, rx_step.  The tally and
-// redraw of step t's done flags is folded into step t + 1's k_league_act (its opponent waves are the
-// only readers of the ids), so one k_league_draw per rollout remains, for the last step.
-// RX_LEAGUE_FOLD=0 (an A/B build, tools/bench_league_train.py) launches k_league_draw after every
-// step instead: the same bits, one more launch per step.
-#ifndef RX_LEAGUE_FOLD
-#define RX_LEAGUE_FOLD 1
-#endif
+// the two-car rollout loop with a per-env opponent from the bank (two_car_rollout_loop)
 int rx_league_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
                             const rx_league_io* lg, int32_t precision, void* stream) {
   const char* fn = "rx_league_rollout_steps";
   // the league io first: its refusals need no handle (tests/test_league_train_cpu.py)
   int rc = league_args(fn, lg, 2);
   if (rc) return rc;
-  if (precision != RX_PREC_FP32 && precision != RX_PREC_BF16)
-    return fail(RX_EINVAL, "%s: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", fn, precision);
+  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
   if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
   if (!io || !r || !sp) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : !r ? "rollout io" : "self-play io");
   if (!h->assigned || !h->bound || h->cfg.n_agents != 2 || h->D != 19)
     return fail(RX_EINVAL, "%s: the handle must be an assigned, bound two-car handle with obs_dim 19", fn);
-  if (r->T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, r->T);
-  if (r->obs_dim != h->D) return fail(RX_EINVAL, "%s: obs_dim %d != the handle's %d", fn, r->obs_dim, h->D);
+  if ((rc = rollout_dims(fn, h, r)) != 0) return rc;
   if (sp->agent != lg->agent)
     return fail(RX_EINVAL, "%s: agent %d of the self-play io != agent %d of the league io", fn, sp->agent, lg->agent);
-  if (!r->params || !r->log_std || !r->eps || !r->obs || !r->actions || !r->logprobs || !r->values || !r->rewards ||
-      !r->dones || !r->next_obs || !r->next_done)
-    return fail(RX_EINVAL, "%s: null rollout buffer", fn);
-  if (!sp->opp_eps || !sp->env_actions || !sp->env_obs || !sp->env_reward || !sp->sink)
-    return fail(RX_EINVAL, "%s: null %s", fn,
-                !sp->opp_eps ? "opp_eps" : !sp->env_actions ? "env_actions" : !sp->env_obs ? "env_obs"
-                : !sp->env_reward ? "env_reward" : "sink");
+  if ((rc = rollout_bufs(fn, r)) != 0 || (rc = selfplay_bufs(fn, sp, true)) != 0) return rc;
   if (!io->info) return fail(RX_EINVAL, "%s: null io->info (the tally reads the terminal step's placement)", fn);
-  const int64_t N = h->cfg.n_envs, D = h->D;
-  const int q = lg->agent, o = 1 - q;
-  hipStream_t hs = (hipStream_t)stream;
-  for (int32_t t = 0; t < r->T; ++t) {
-    const bool last = t + 1 == r->T;
-    // rx_selfplay_rollout_steps' two policy ios; the opponent's params / log_std are the bank bases
-    const rx_policy_io opp{(int32_t)D, N, sp->env_obs + o * D, sp->opp_eps + t * N * 2, lg->params, lg->log_std,
-                           sp->env_actions + 2 * o, nullptr, sp->sink, 2 * D, 4, lg->opp_precision, nullptr, 0};
-    const rx_policy_io pio{(int32_t)D, N, t == 0 ? r->obs : sp->env_obs + q * D, r->eps + t * N * 2, r->params,
-                           r->log_std, r->actions + t * N * 2, r->logprobs + t * N, r->values + t * N,
-                           t == 0 ? 0 : 2 * D, 0, precision, sp->env_actions + 2 * q, 4};
-    // io->info still holds step t - 1's rows here: rx_step writes it after this launch
-    const bool fold = RX_LEAGUE_FOLD && t > 0;
-    rc = rx_launch_league_act(&pio, &opp, lg, fold ? r->dones + t * N : nullptr, fold ? io->info : nullptr,
-                              t == 0 ? nullptr : r->obs + t * N * D, sp->env_reward,
-                              t == 0 ? nullptr : r->rewards + (t - 1) * N, hs);
-    if (rc) return fail(RX_EHIP, "league policy launch failed: %s", hipGetErrorString((hipError_t)rc));
-    rx_io s = *io;
-    s.actions = sp->env_actions;
-    s.obs = sp->env_obs;
-    s.reward = sp->env_reward;
-    s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;
-    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
-    // the envs that ended: count the result against their opponent, draw the next one
-    if ((last || !RX_LEAGUE_FOLD) && (rc = rx_launch_league_draw(lg, N, s.done_f32, io->info, hs)) != 0)
-      return fail(RX_EHIP, "league draw launch failed: %s", hipGetErrorString((hipError_t)rc));
-  }
-  rc = rx_launch_agent_rows((int)N, (int)D, q, sp->env_obs, sp->env_reward, r->next_obs, r->rewards + (r->T - 1) * N,
-                            hs);
-  if (rc) return fail(RX_EHIP, "agent-row copy launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
+  return two_car_rollout_loop(h, io, r, sp, lg, precision, stream);
 }
 
 // ABI v25, additive: the track curriculum (csrc/rx_curriculum.h).  The checks of the four entry
@@ -2364,54 +2384,23 @@ int rx_track_draw_host(const rx_track_io* tc, int64_t n, uint32_t generation, do
   return RX_OK;
 }
 
-// rx_rollout_steps with one k_track_tally after every step: the same policy and env launches in the
-// same order, so every rollout output is rx_rollout_steps'; the tally reads the done row the step just
-// wrote and the env's terminated / info rows before the next step overwrites them (one stream).
+// the single-agent rollout loop with the tally (rollout_loop)
 int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
                            int32_t precision, void* stream) {
   const char* fn = "rx_track_rollout_steps";
   // the track io first: its refusals need no handle (tests/test_curriculum_cpu.py)
   int rc = track_args(fn, tc, 0);
   if (rc) return rc;
-  if (precision != RX_PREC_FP32 && precision != RX_PREC_BF16)
-    return fail(RX_EINVAL, "%s: precision=%d (RX_PREC_FP32 or RX_PREC_BF16)", fn, precision);
+  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
   if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
   if (!io || !r) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : "rollout io");
   if (!h->assigned || !h->bound || h->cfg.n_agents != 1)
     return fail(RX_EINVAL, "%s: the handle must be an assigned, bound single-agent handle", fn);
-  if (r->T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, r->T);
-  if (r->obs_dim != h->D) return fail(RX_EINVAL, "%s: obs_dim %d != the handle's %d", fn, r->obs_dim, h->D);
-  if (!r->params || !r->log_std || !r->eps || !r->obs || !r->actions || !r->logprobs || !r->values || !r->rewards ||
-      !r->dones || !r->next_obs || !r->next_done)
-    return fail(RX_EINVAL, "%s: null rollout buffer", fn);
+  if ((rc = rollout_dims(fn, h, r)) != 0 || (rc = rollout_bufs(fn, r)) != 0) return rc;
   if (!io->terminated || !io->info)
     return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
                 !io->terminated ? "terminated" : "info");
-  const int64_t N = h->cfg.n_envs, D = h->D;
-  hipStream_t hs = (hipStream_t)stream;
-  const void* frag = nullptr;
-  if (precision == RX_PREC_BF16) {  // as rx_rollout_steps: the bf16 operand fragments once per call
-    if (rx_launch_policy_frag(r->obs_dim, r->params, h->policy_frag.p, hs))
-      return fail(RX_EHIP, "%s: fragment launch failed", fn);
-    frag = h->policy_frag.p;
-  }
-  for (int32_t t = 0; t < r->T; ++t) {
-    const bool last = t + 1 == r->T;
-    const rx_policy_io pio{r->obs_dim, N, r->obs + t * N * D, r->eps + t * N * 2, r->params, r->log_std,
-                           r->actions + t * N * 2, r->logprobs + t * N, r->values + t * N, 0, 0, precision,
-                           nullptr, 0};
-    if ((rc = rx_launch_policy_act(&pio, hs, frag)) != 0)
-      return fail(RX_EHIP, "%s: policy launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-    rx_io s = *io;
-    s.actions = r->actions + t * N * 2;
-    s.obs = last ? r->next_obs : r->obs + (t + 1) * N * D;
-    s.reward = r->rewards + t * N;
-    s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;
-    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
-    if ((rc = rx_launch_track_tally(tc, N, s.done_f32, io->terminated, io->info, hs)) != 0)
-      return fail(RX_EHIP, "%s: tally launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-  }
-  return RX_OK;
+  return rollout_loop(fn, h, io, r, tc, precision, stream);
 }
 
 // ABI v25, additive: the curriculum's replay scores (csrc/rx_track_replay.h).  The checks of the four

@@ -124,44 +124,21 @@ class TrackCurriculum:
 
 
 class CurriculumStepRollout(StepRollout):
-    """rx_track_rollout_steps driver: StepRollout's call with one rx_track_tally
-    after every step.  The step runs with the env's terminated and info rows, which
-    the tally reads; every rollout output equals StepRollout's bit for bit
-    (tests/test_curriculum_gpu.py).  Every address handed to the library is fixed, so
-    a captured graph of the call stays valid until the tracks are swapped."""
+    """rx_track_rollout_steps driver: the single-agent rollout loop with one
+    rx_track_tally after every step.  The step runs with the env's terminated and
+    info rows, which the tally reads; every rollout output equals StepRollout's bit
+    for bit (tests/test_curriculum_gpu.py).  Every address handed to the library is
+    fixed, so a captured graph of the call stays valid until the tracks are swapped."""
+
+    FN = "rx_track_rollout_steps"
 
     def __init__(self, agent, flat, venv, T, curriculum, prec=_lib.RX_PREC_FP32):
         super().__init__(agent, flat, venv, T, prec)
         self.curriculum = curriculum
 
-    def __call__(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done, eps=None, stream=None):
-        T, n, D = self.T, self.n, self.obs_dim
-        e = self.eps if eps is None else eps
-        key = tuple(t.data_ptr() for t in (obs, actions, logprobs, dones, rewards, values, next_obs, next_done, e))
-        r = self._cache.get(key)
-        if r is None:
-            shapes = {"obs": (obs, (T, n, D)), "actions": (actions, (T, n, 2)), "logprobs": (logprobs, (T, n)),
-                      "values": (values, (T, n)), "rewards": (rewards, (T, n)), "dones": (dones, (T, n)),
-                      "next_obs": (next_obs, (n, D)), "next_done": (next_done, (n,)), "eps": (e, (T, n, 2))}
-            for k, (t, shp) in shapes.items():
-                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise ValueError(f"rx_track_rollout_steps: {k} must be a contiguous float32 {shp}, got "
-                                     f"{tuple(t.shape)} {t.dtype}")
-            if len(self._cache) > 64:
-                self._cache.clear()
-            r = self._cache[key] = _lib.RxRolloutIO(
-                T, D, _lib.ptr(self.flat.flat_param), _lib.ptr(self.agent.log_std), _lib.ptr(e), _lib.ptr(obs),
-                _lib.ptr(actions), _lib.ptr(logprobs), _lib.ptr(values), _lib.ptr(rewards), _lib.ptr(dones),
-                _lib.ptr(next_obs), _lib.ptr(next_done))
-        if eps is None:
-            self.eps.normal_()
-        # the step's plain io plus the info rows the tally reads (no float64 reward copy); once per rollout
-        base = self.venv._io()
-        io = _lib.RxIO(*(getattr(base, k) for k in _lib.IO_FIELDS))
-        io.info = _lib.ptr(self.venv.buf["info"])
-        _lib.check(self.L.rx_track_rollout_steps(self.venv._h, io, r, ctypes.byref(self.curriculum.tc), self.prec,
-                                                 _lib.stream_ptr(stream)), "rx_track_rollout_steps")
-        self.venv._launched(stream)
+    def _enqueue(self, args, stream):
+        _lib.check(self.L.rx_track_rollout_steps(self.venv._h, self.venv._io_info(), *args,
+                                                 ctypes.byref(self.curriculum.tc), self.prec, stream), self.FN)
 
 
 class CurriculumPPO(PPO):

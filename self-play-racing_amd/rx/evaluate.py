@@ -119,19 +119,43 @@ class FusedEval:
                              _lib.ptr(self._lp), _lib.ptr(self._val), _lib.ptr(self.acc), _lib.ptr(self.active),
                              _lib.ptr(self.n_active))
 
-    def policy_chunk(self, flat, log_std, n, deterministic=False, prec="fp32"):
-        """``n`` <= chunk policy-in-the-loop steps (one normal_() over the chunk's noise,
-        or zeros = the mean action); the actions taken are in ``self.actions[:n]``.
-        Returns the number of episodes still running."""
+    def check_n(self, n):
         if not 0 < n <= self.chunk:
             raise ValueError(f"n={n}: 1 .. {self.chunk}")
-        if deterministic:
-            if not self._eps_zero:
-                self.eps.zero_()
-        else:
+
+    def draw_noise(self, deterministic):
+        """The next chunk's noise in ``self.eps``: one normal_() over the whole chunk,
+        or zeros (= the mean action), written once and kept while they stay zeros."""
+        if not deterministic:
             self.eps.normal_()
+        elif not self._eps_zero:
+            self.eps.zero_()
         self._eps_zero = bool(deterministic)
+
+    def policy_chunk(self, flat, log_std, n, deterministic=False, prec="fp32"):
+        """``n`` <= chunk policy-in-the-loop steps (``draw_noise``); the actions taken are
+        in ``self.actions[:n]``.  Returns the number of episodes still running."""
+        self.check_n(n)
+        self.draw_noise(deterministic)
         return self._call(self._ev(self.actions, flat, log_std, _lib.PRECISION[prec]), n)
+
+    def run_chunks(self, chunk, max_steps, record_actions=False):
+        """Reset, then ``chunk(n)`` (n steps -> the episodes still running) until
+        ``max_steps`` or until every episode has ended.  Returns the [N, A, RX_EVAL_W]
+        record as a numpy array, and with ``record_actions`` also the [T, N, A, 2]
+        actions of the T steps executed."""
+        self.begin()
+        taken, t = [], 0
+        while t < max_steps:
+            n = min(self.chunk, max_steps - t)
+            left = chunk(n)
+            if record_actions:
+                taken.append(self.actions[:n].clone())
+            t += n
+            if left == 0:
+                break
+        rec = self.record()
+        return (rec, torch.cat(taken)) if record_actions else rec
 
     def actions_chunk(self, actions):
         """Open-loop steps of ``actions`` [n, N, A, 2] (contiguous float32 on the env's
@@ -148,8 +172,7 @@ class FusedEval:
     @torch.no_grad()
     def run_policy(self, agent, max_steps, deterministic=False, prec="fp32", record_actions=False):
         """One evaluation with ``agent`` in the loop (two-car envs: it drives both
-        cars).  Returns the [N, A, RX_EVAL_W] record as a numpy array, and with
-        ``record_actions`` also the [T, N, A, 2] actions of the T steps executed."""
+        cars): ``run_chunks`` of ``policy_chunk``."""
         from .ppo_fused import policy_supported
         if prec not in _lib.PRECISION:
             raise ValueError(f"prec={prec!r}: 'fp32' or 'bf16'")
@@ -159,19 +182,8 @@ class FusedEval:
         flat = _flat_policy(agent)
         if flat.device != self.acc.device:
             raise ValueError(f"the agent is on {flat.device}, the evaluation env on {self.acc.device}")
-        self.begin()
-        taken = []
-        t = 0
-        while t < max_steps:
-            n = min(self.chunk, max_steps - t)
-            left = self.policy_chunk(flat, agent.log_std, n, deterministic, prec)
-            if record_actions:
-                taken.append(self.actions[:n].clone())
-            t += n
-            if left == 0:
-                break
-        rec = self.record()
-        return (rec, torch.cat(taken)) if record_actions else rec
+        return self.run_chunks(lambda n: self.policy_chunk(flat, agent.log_std, n, deterministic, prec), max_steps,
+                               record_actions)
 
     @torch.no_grad()
     def run_actions(self, actions, max_steps):

@@ -300,24 +300,17 @@ class Match:
         self.fe.begin()
 
     def steps(self, bank, n, deterministic=False, prec="fp32"):
-        """``n`` <= chunk steps (one normal_() over the chunk's noise, or zeros = the
-        mean action); the actions taken are in ``self.fe.actions[:n]``.  Returns the
-        number of episodes still running."""
+        """``n`` <= chunk steps (noise: ``FusedEval.draw_noise``); the actions taken are
+        in ``self.fe.actions[:n]``.  Returns the number of episodes still running."""
         fe, v = self.fe, self.venv
-        if not 0 < n <= self.chunk:
-            raise ValueError(f"n={n}: 1 .. {self.chunk}")
+        fe.check_n(n)
         if prec not in _lib.PRECISION:
             raise ValueError(f"prec={prec!r}: 'fp32' or 'bf16'")
         if bank.obs_dim != v.D:
             raise ValueError(f"the bank's policies read {bank.obs_dim} observation columns, the env has {v.D}")
         if bank.params.device != fe.acc.device:
             raise ValueError(f"the bank is on {bank.params.device}, the env on {fe.acc.device}")
-        if deterministic:
-            if not fe._eps_zero:
-                fe.eps.zero_()
-        else:
-            fe.eps.normal_()
-        fe._eps_zero = bool(deterministic)
+        fe.draw_noise(deterministic)
         m = _lib.RxMatchIO(v.D, _lib.PRECISION[prec], _lib.ptr(bank.params), _lib.ptr(bank.log_std), _lib.ptr(fe.eps),
                            _lib.ptr(fe.actions), _lib.ptr(fe._lp), _lib.ptr(fe._val), _lib.ptr(fe.acc),
                            _lib.ptr(fe.active), _lib.ptr(fe.n_active), bank.n_policies, 0, bank.stride,
@@ -331,18 +324,7 @@ class Match:
     def run(self, bank, max_steps, deterministic=False, prec="fp32", record_actions=False):
         """Reset, then step until ``max_steps`` or until every episode has ended.  Returns
         the [N, A, RX_EVAL_W] record (and with ``record_actions`` the [T, N, A, 2] actions)."""
-        self.begin()
-        taken, t = [], 0
-        while t < max_steps:
-            n = min(self.chunk, max_steps - t)
-            left = self.steps(bank, n, deterministic, prec)
-            if record_actions:
-                taken.append(self.fe.actions[:n].clone())
-            t += n
-            if left == 0:
-                break
-        rec = self.fe.record()
-        return (rec, torch.cat(taken)) if record_actions else rec
+        return self.fe.run_chunks(lambda n: self.steps(bank, n, deterministic, prec), max_steps, record_actions)
 
 
 class League:

@@ -26,6 +26,7 @@ from . import _lib
 from . import dist as rdist
 from .league import STRIDE_ALIGN
 from .ppo import PPO
+from .ppo_fused import SelfPlayStepRollout, policy_supported
 from .selfplay import SelfPlayPPO, SelfPlayVectorEnv
 
 MAX_SLOTS = _lib.RX_LEAGUE_MAX_SLOTS
@@ -64,7 +65,9 @@ class PoolSlots:
         return [self.slot_of(s) for s in self.members()]
 
 
-def flat_policy(agent):
+def flat_policy_copy(agent):
+    """A COPY of the agent's parameters as one flat tensor (a bank row's source).  Not
+    rx.evaluate._flat_policy, which returns the module's own storage when it is packed."""
     return torch.cat([p.detach().reshape(-1) for p in agent.parameters()])
 
 
@@ -118,7 +121,7 @@ class LeagueVectorEnv(SelfPlayVectorEnv):
         slot that held another snapshot starts its tally again."""
         if not 0 <= int(k) < self.pool_size:
             raise ValueError(f"slot {k} outside 0..{self.pool_size - 1}")
-        flat = flat_policy(agent)
+        flat = flat_policy_copy(agent)
         if flat.numel() != self.n_params or flat.dtype != torch.float32:
             raise ValueError(f"slot {k}: the policy has {flat.numel()} {flat.dtype} parameters, the bank's layout "
                              f"has {self.n_params} float32")
@@ -160,29 +163,19 @@ class LeagueVectorEnv(SelfPlayVectorEnv):
         return o, r, done
 
 
-class LeagueStepRollout:
-    """rx_league_rollout_steps driver, modelled on ppo_fused.SelfPlayStepRollout: per
-    step one policy launch (learner actor + critic, opponents through the bank),
-    rx_step; the tally and redraw of a step runs inside the next step's policy
-    launch, with one small launch after the last.  Noise of both sides is drawn up front.  Every
-    address handed to the library is fixed and nothing that changes between updates
-    (the number of live slots, the table, the ids) is a by-value argument, so a
-    captured graph of the call stays valid while the pool fills."""
+class LeagueStepRollout(SelfPlayStepRollout):
+    """rx_league_rollout_steps driver: the two-car rollout loop with the opponents
+    from the bank -- per step one policy launch (learner actor + critic, opponents
+    through the bank), rx_step; the tally and redraw of a step runs inside the next
+    step's policy launch, with one small launch after the last.  Every address
+    handed to the library is fixed and nothing that changes between updates (the
+    number of live slots, the table, the ids) is a by-value argument or part of the
+    cache key, so a captured graph of the call stays valid while the pool fills."""
 
-    def __init__(self, agent, flat, lenv, T, prec=_lib.RX_PREC_FP32):
-        self.L = _lib.load()
-        self.agent, self.flat, self.spenv, self.T, self.prec = agent, flat, lenv, int(T), int(prec)
-        self.venv = lenv.venv
-        self.n, self.obs_dim = self.venv.num_envs, self.venv.D
-        dev = flat.flat_param.device
-        self.eps = torch.empty((self.T, self.n, 2), dtype=torch.float32, device=dev)
-        self.opp_eps = torch.empty((self.T, self.n, 2), dtype=torch.float32, device=dev)
-        self.sink = torch.empty(2 * self.n, dtype=torch.float32, device=dev)
-        self._cache = {}
+    FN = "rx_league_rollout_steps"
 
     @staticmethod
     def supported(lenv, agent, config):
-        from .ppo_fused import policy_supported
         mode = config.get("rollout_steps", "auto")
         if mode is False or mode == "off":
             return False
@@ -190,41 +183,12 @@ class LeagueStepRollout:
         return (v is not None and hasattr(v, "_h") and hasattr(lenv, "lg") and lenv.n_live > 0 and v.n_agents == 2
                 and policy_supported(agent, v.D))
 
-    def __call__(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done, eps=None, opp_eps=None,
-                 stream=None):
-        T, n, D = self.T, self.n, self.obs_dim
-        e = self.eps if eps is None else eps
-        oe = self.opp_eps if opp_eps is None else opp_eps
-        key = tuple(t.data_ptr() for t in (obs, actions, logprobs, dones, rewards, values, next_obs, next_done, e, oe))
-        r = self._cache.get(key)
-        if r is None:
-            shapes = {"obs": (obs, (T, n, D)), "actions": (actions, (T, n, 2)), "logprobs": (logprobs, (T, n)),
-                      "values": (values, (T, n)), "rewards": (rewards, (T, n)), "dones": (dones, (T, n)),
-                      "next_obs": (next_obs, (n, D)), "next_done": (next_done, (n,)), "eps": (e, (T, n, 2)),
-                      "opp_eps": (oe, (T, n, 2))}
-            for k, (t, shp) in shapes.items():
-                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise ValueError(f"rx_league_rollout_steps: {k} must be a contiguous float32 {shp}")
-            if len(self._cache) > 64:
-                self._cache.clear()
-            b = self.venv.buf
-            r = self._cache[key] = (
-                _lib.RxRolloutIO(T, D, _lib.ptr(self.flat.flat_param), _lib.ptr(self.agent.log_std), _lib.ptr(e),
-                                 _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logprobs), _lib.ptr(values),
-                                 _lib.ptr(rewards), _lib.ptr(dones), _lib.ptr(next_obs), _lib.ptr(next_done)),
-                _lib.RxSelfplayIO(None, None, _lib.ptr(oe), _lib.ptr(self.spenv._act), _lib.ptr(b["obs"]),
-                                  _lib.ptr(b["reward"]), _lib.ptr(self.sink), self.spenv.agent_idx, 0))
-        if eps is None:
-            self.eps.normal_()
-        if opp_eps is None:
-            self.opp_eps.normal_()
-        # the step's plain io plus the info rows the tally reads (no float64 reward copy); once per rollout
-        base = self.venv._io()
-        io = _lib.RxIO(*(getattr(base, k) for k in _lib.IO_FIELDS))
-        io.info = _lib.ptr(self.venv.buf["info"])
-        _lib.check(self.L.rx_league_rollout_steps(self.venv._h, io, r[0], r[1], ctypes.byref(self.spenv.lg), self.prec,
-                                                  _lib.stream_ptr(stream)), "rx_league_rollout_steps")
-        self.venv._launched(stream)
+    def _opponent(self):
+        return None, None, 0  # the bank is in the league io: nothing of it in the struct or the cache key
+
+    def _enqueue(self, args, stream):
+        _lib.check(self.L.rx_league_rollout_steps(self.venv._h, self.venv._io_info(), *args,
+                                                  ctypes.byref(self.spenv.lg), self.prec, stream), self.FN)
 
 
 class LeagueSelfPlayPPO(SelfPlayPPO):
@@ -257,7 +221,6 @@ class LeagueSelfPlayPPO(SelfPlayPPO):
         if not self.pfsp_prior > 0.0:
             raise ValueError(f"pfsp_prior={self.pfsp_prior} must be > 0")
         super().__init__(env_fn, config, device)
-        from .ppo_fused import policy_supported
         if not policy_supported(self.agent, self.envs.venv.D):
             raise ValueError("LeagueSelfPlayPPO: the policy does not have the reference actor-critic layout")
 

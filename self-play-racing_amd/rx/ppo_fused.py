@@ -225,21 +225,97 @@ def policy_supported(agent, obs_dim):
     return sum(p.numel() for p in agent.parameters()) == _lib.load().rx_ppo_n_params(obs_dim)
 
 
-class Rollout:
+
+
+class RolloutDriver:
+    """What the rollout drivers share (the step loops): the buffers
+    of one T-step rollout marshalled into an rx_rollout_io, and the call.
+
+    A subclass names its entry point (``FN``) and makes the library call
+    (``_enqueue``); a two-car driver (``two_car``) also has the opponent's noise
+    ``opp_eps``, the scratch ``sink`` and a second struct (``_extra``).  The
+    N(0, 1) noise of all T steps is drawn up front with ONE torch normal_() per
+    policy on [T, N, 2] -- the same distribution as per-step draws (with T = 1
+    the same sample) -- unless the caller passes ``eps`` / ``opp_eps`` (tests);
+    given the same noise every output equals the per-step path bit for bit.
+
+    The structs are validated and built once per set of buffer addresses (a
+    trainer reuses the same buffers every update) and kept in a bounded cache;
+    noise is drawn after validation and before the call."""
+
+    FN = None  # the entry point, named in every error
+
+    def __init__(self, agent, flat, venv, T, prec=_lib.RX_PREC_FP32, two_car=False):
+        self.L = _lib.load()
+        self.agent, self.flat, self.venv, self.T, self.prec = agent, flat, venv, int(T), int(prec)
+        self.n, self.obs_dim = venv.num_envs, venv.D
+        dev = flat.flat_param.device
+        self.eps = torch.empty((self.T, self.n, 2), dtype=torch.float32, device=dev)
+        self.opp_eps = torch.empty_like(self.eps) if two_car else None
+        if two_car:
+            self.sink = torch.empty(2 * self.n, dtype=torch.float32, device=dev)
+        self._cache = {}
+
+    def _key(self):
+        """What the cached structs depend on besides the buffers' addresses."""
+        return ()
+
+    def _extra(self, opp_eps):
+        """The structs that follow the rx_rollout_io in the library call."""
+        return ()
+
+    def _enqueue(self, args, stream):
+        raise NotImplementedError
+
+    def _args(self, bufs, eps, opp_eps):
+        T, n, D = self.T, self.n, self.obs_dim
+        e = self.eps if eps is None else eps
+        oe = self.opp_eps if opp_eps is None else opp_eps
+        noise = (e,) if oe is None else (e, oe)
+        key = tuple(t.data_ptr() for t in bufs + noise) + self._key()
+        args = self._cache.get(key)
+        if args is None:
+            obs, actions, logprobs, dones, rewards, values, next_obs, next_done = bufs
+            shapes = {"obs": (obs, (T, n, D)), "actions": (actions, (T, n, 2)), "logprobs": (logprobs, (T, n)),
+                      "values": (values, (T, n)), "rewards": (rewards, (T, n)), "dones": (dones, (T, n)),
+                      "next_obs": (next_obs, (n, D)), "next_done": (next_done, (n,)), "eps": (e, (T, n, 2))}
+            if oe is not None:
+                shapes["opp_eps"] = (oe, (T, n, 2))
+            for k, (t, shp) in shapes.items():
+                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError(f"{self.FN}: {k} must be a contiguous float32 {shp}, got {tuple(t.shape)} "
+                                     f"{t.dtype} with strides {t.stride()}")
+            if len(self._cache) > 64:
+                self._cache.clear()
+            r = _lib.RxRolloutIO(T, D, _lib.ptr(self.flat.flat_param), _lib.ptr(self.agent.log_std), _lib.ptr(e),
+                                 _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logprobs), _lib.ptr(values),
+                                 _lib.ptr(rewards), _lib.ptr(dones), _lib.ptr(next_obs), _lib.ptr(next_done))
+            args = self._cache[key] = (r,) + self._extra(oe)
+        if eps is None:
+            self.eps.normal_()
+        if opp_eps is None and self.opp_eps is not None:
+            self.opp_eps.normal_()
+        return args
+
+    def _run(self, bufs, eps, opp_eps, stream):
+        self._enqueue(self._args(bufs, eps, opp_eps), _lib.stream_ptr(stream))
+        self.venv._launched(stream)
+
+    def __call__(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done, eps=None, stream=None):
+        """obs[0] / dones[0] hold the rollout's first observation / done flags;
+        fills the rest like collect_rollout's step loop."""
+        self._run((obs, actions, logprobs, dones, rewards, values, next_obs, next_done), eps, None, stream)
+
+
+class Rollout(RolloutDriver):
     """rx_rollout driver: a whole T-step rollout of few single-agent envs as
     ONE persistent launch (include/rx.h; k_rollout) instead of T x (noise
-    draw + rx_policy_act + two env kernels).  The N(0, 1) noise of all T steps
-    is drawn up front with ONE torch normal_() on a [T, N, 2] buffer: the same
-    distribution as the per-step draws but a different sample of torch's
-    stream; given the same noise, every output equals the per-step fused path
-    (rx_policy_act + rx_step) bit for bit (tests/test_rollout_gpu.py)."""
+    draw + rx_policy_act + two env kernels); tests/test_rollout_gpu.py."""
+
+    FN = "rx_rollout"
 
     def __init__(self, agent, flat, venv, T):
-        self.L = _lib.load()
-        self.agent, self.flat, self.venv, self.T = agent, flat, venv, int(T)
-        self.n, self.obs_dim = venv.num_envs, venv.D
-        self.eps = torch.empty((self.T, self.n, 2), dtype=torch.float32, device=flat.flat_param.device)
-        self._cache = {}
+        super().__init__(agent, flat, venv, T)
 
     @staticmethod
     def supported(venv, agent, config):
@@ -252,50 +328,17 @@ class Rollout:
             return False
         return mode is True or venv.num_envs <= ROLLOUT_AUTO_MAX_ENVS
 
-    def __call__(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done, eps=None, stream=None):
-        """obs[0] / dones[0] hold the rollout's first observation / done flags;
-        fills the rest like collect_rollout's step loop.  ``eps`` (tests): a
-        [T, N, 2] noise tensor to use instead of a fresh draw."""
-        T, n, D = self.T, self.n, self.obs_dim
-        shapes = {"obs": (obs, (T, n, D)), "actions": (actions, (T, n, 2)), "logprobs": (logprobs, (T, n)),
-                  "values": (values, (T, n)), "rewards": (rewards, (T, n)), "dones": (dones, (T, n)),
-                  "next_obs": (next_obs, (n, D)), "next_done": (next_done, (n,))}
-        for k, (t, shp) in shapes.items():
-            if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"rx_rollout: {k} must be a contiguous float32 {shp}, got {tuple(t.shape)} {t.dtype}")
-        e = self.eps if eps is None else eps
-        key = tuple(t.data_ptr() for t in (obs, actions, logprobs, dones, rewards, values, next_obs, next_done, e))
-        r = self._cache.get(key)
-        if r is None:
-            if len(self._cache) > 64:
-                self._cache.clear()
-            r = self._cache[key] = _lib.RxRolloutIO(
-                T, D, _lib.ptr(self.flat.flat_param), _lib.ptr(self.agent.log_std), _lib.ptr(e), _lib.ptr(obs),
-                _lib.ptr(actions), _lib.ptr(logprobs), _lib.ptr(values), _lib.ptr(rewards), _lib.ptr(dones),
-                _lib.ptr(next_obs), _lib.ptr(next_done))
-        if eps is None:
-            self.eps.normal_()
-        io = self.venv._io()
-        _lib.check(self.L.rx_rollout(self.venv._h, io, r, _lib.stream_ptr(stream)), "rx_rollout")
-        self.venv._launched(stream)
+    def _enqueue(self, args, stream):
+        _lib.check(self.L.rx_rollout(self.venv._h, self.venv._io(), *args, stream), self.FN)
 
 
-class StepRollout:
+class StepRollout(RolloutDriver):
     """rx_rollout_steps driver: the T-step rollout of any single-agent handle as
     ONE library call that enqueues T x (rx_policy_act + rx_step) -- the kernels
     of the per-step loop, in its order, with pointer arithmetic in C instead of
-    T x (tensor slicing + two ctypes calls) of host time.  The N(0, 1) noise of
-    all T steps is drawn up front with ONE torch normal_() on [T, N, 2] (the
-    same distribution; with T = 1 the same sample as a per-step draw); given
-    the same noise every output equals the per-step loop bit for bit
-    (tests/test_rollout_gpu.py)."""
+    T x (tensor slicing + two ctypes calls) of host time; tests/test_rollout_gpu.py."""
 
-    def __init__(self, agent, flat, venv, T, prec=_lib.RX_PREC_FP32):
-        self.L = _lib.load()
-        self.agent, self.flat, self.venv, self.T, self.prec = agent, flat, venv, int(T), int(prec)
-        self.n, self.obs_dim = venv.num_envs, venv.D
-        self.eps = torch.empty((self.T, self.n, 2), dtype=torch.float32, device=flat.flat_param.device)
-        self._cache = {}
+    FN = "rx_rollout_steps"
 
     @staticmethod
     def supported(venv, agent, config):
@@ -304,54 +347,23 @@ class StepRollout:
         mode = config.get("rollout_steps", "auto")
         return not (mode is False or mode == "off")
 
-    def __call__(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done, eps=None, stream=None):
-        T, n, D = self.T, self.n, self.obs_dim
-        shapes = {"obs": (obs, (T, n, D)), "actions": (actions, (T, n, 2)), "logprobs": (logprobs, (T, n)),
-                  "values": (values, (T, n)), "rewards": (rewards, (T, n)), "dones": (dones, (T, n)),
-                  "next_obs": (next_obs, (n, D)), "next_done": (next_done, (n,))}
-        e = self.eps if eps is None else eps
-        key = tuple(t.data_ptr() for t in (obs, actions, logprobs, dones, rewards, values, next_obs, next_done, e))
-        r = self._cache.get(key)
-        if r is None:
-            for k, (t, shp) in shapes.items():
-                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise ValueError(f"rx_rollout_steps: {k} must be a contiguous float32 {shp}, got "
-                                     f"{tuple(t.shape)} {t.dtype}")
-            if tuple(e.shape) != (T, n, 2) or e.dtype != torch.float32 or not e.is_contiguous():
-                raise ValueError("rx_rollout_steps: eps must be a contiguous float32 [T, N, 2]")
-            if len(self._cache) > 64:
-                self._cache.clear()
-            r = self._cache[key] = _lib.RxRolloutIO(
-                T, D, _lib.ptr(self.flat.flat_param), _lib.ptr(self.agent.log_std), _lib.ptr(e), _lib.ptr(obs),
-                _lib.ptr(actions), _lib.ptr(logprobs), _lib.ptr(values), _lib.ptr(rewards), _lib.ptr(dones),
-                _lib.ptr(next_obs), _lib.ptr(next_done))
-        if eps is None:
-            self.eps.normal_()
-        io = self.venv._io()
-        _lib.check(self.L.rx_rollout_steps(self.venv._h, io, r, self.prec, _lib.stream_ptr(stream)),
-                   "rx_rollout_steps")
-        self.venv._launched(stream)
+    def _enqueue(self, args, stream):
+        _lib.check(self.L.rx_rollout_steps(self.venv._h, self.venv._io(), *args, self.prec, stream), self.FN)
 
 
-class SelfPlayStepRollout:
+class SelfPlayStepRollout(RolloutDriver):
     """rx_selfplay_rollout_steps driver: the self-play rollout of a two-car handle
     (rx.selfplay.SelfPlayVectorEnv with a frozen-policy opponent on
-    rx_policy_act) as ONE library call enqueueing per step the opponent's and the
-    agent's rx_policy_act, rx_step and one agent-row copy -- five launches where
-    the per-step Python path ran nine (two noise draws, three copies).  Noise of
-    both policies is drawn up front ([T, N, 2] each); given the same noise every
-    output equals the per-step path bit for bit (tests/test_selfplay_train_gpu.py)."""
+    rx_policy_act) as ONE library call enqueueing per step one launch for the
+    opponent's and the agent's policy, rx_step, and one agent-row copy at the end
+    -- where the per-step Python path ran nine launches per step (two noise draws,
+    three copies); tests/test_selfplay_train_gpu.py."""
+
+    FN = "rx_selfplay_rollout_steps"
 
     def __init__(self, agent, flat, spenv, T, prec=_lib.RX_PREC_FP32):
-        self.L = _lib.load()
-        self.agent, self.flat, self.spenv, self.T, self.prec = agent, flat, spenv, int(T), int(prec)
-        self.venv = spenv.venv
-        self.n, self.obs_dim = self.venv.num_envs, self.venv.D
-        dev = flat.flat_param.device
-        self.eps = torch.empty((self.T, self.n, 2), dtype=torch.float32, device=dev)
-        self.opp_eps = torch.empty((self.T, self.n, 2), dtype=torch.float32, device=dev)
-        self.sink = torch.empty(2 * self.n, dtype=torch.float32, device=dev)
-        self._cache = {}
+        super().__init__(agent, flat, spenv.venv, T, prec, two_car=True)
+        self.spenv = spenv
 
     @staticmethod
     def supported(spenv, agent, config):
@@ -362,41 +374,28 @@ class SelfPlayStepRollout:
         return (v is not None and hasattr(v, "_h") and v.n_agents == 2 and spenv._opp_fused is not None
                 and policy_supported(agent, v.D))
 
+    def _opponent(self):
+        """(parameters, log_std, precision) of the frozen opponent.  They are part of
+        the cache key: a new opponent rebuilds the struct."""
+        opp = self.spenv._opp_fused
+        return opp.flat.flat_param, opp.agent.log_std, opp.prec
+
+    def _key(self):
+        return tuple(x.data_ptr() if torch.is_tensor(x) else x for x in self._opponent())
+
+    def _extra(self, opp_eps):
+        params, log_std, prec = self._opponent()
+        b = self.venv.buf
+        return (_lib.RxSelfplayIO(_lib.ptr(params), _lib.ptr(log_std), _lib.ptr(opp_eps), _lib.ptr(self.spenv._act),
+                                  _lib.ptr(b["obs"]), _lib.ptr(b["reward"]), _lib.ptr(self.sink),
+                                  self.spenv.agent_idx, prec),)
+
+    def _enqueue(self, args, stream):
+        _lib.check(self.L.rx_selfplay_rollout_steps(self.venv._h, self.venv._io(), *args, self.prec, stream), self.FN)
+
     def __call__(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done, eps=None, opp_eps=None,
                  stream=None):
-        T, n, D = self.T, self.n, self.obs_dim
-        e = self.eps if eps is None else eps
-        oe = self.opp_eps if opp_eps is None else opp_eps
-        opp = self.spenv._opp_fused
-        key = tuple(t.data_ptr() for t in (obs, actions, logprobs, dones, rewards, values, next_obs, next_done, e, oe,
-                                           opp.flat.flat_param, opp.agent.log_std)) + (opp.prec,)
-        r = self._cache.get(key)
-        if r is None:
-            shapes = {"obs": (obs, (T, n, D)), "actions": (actions, (T, n, 2)), "logprobs": (logprobs, (T, n)),
-                      "values": (values, (T, n)), "rewards": (rewards, (T, n)), "dones": (dones, (T, n)),
-                      "next_obs": (next_obs, (n, D)), "next_done": (next_done, (n,)), "eps": (e, (T, n, 2)),
-                      "opp_eps": (oe, (T, n, 2))}
-            for k, (t, shp) in shapes.items():
-                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise ValueError(f"rx_selfplay_rollout_steps: {k} must be a contiguous float32 {shp}")
-            if len(self._cache) > 64:
-                self._cache.clear()
-            b = self.venv.buf
-            r = self._cache[key] = (
-                _lib.RxRolloutIO(T, D, _lib.ptr(self.flat.flat_param), _lib.ptr(self.agent.log_std), _lib.ptr(e),
-                                 _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logprobs), _lib.ptr(values),
-                                 _lib.ptr(rewards), _lib.ptr(dones), _lib.ptr(next_obs), _lib.ptr(next_done)),
-                _lib.RxSelfplayIO(_lib.ptr(opp.flat.flat_param), _lib.ptr(opp.agent.log_std), _lib.ptr(oe),
-                                  _lib.ptr(self.spenv._act), _lib.ptr(b["obs"]), _lib.ptr(b["reward"]),
-                                  _lib.ptr(self.sink), self.spenv.agent_idx, opp.prec))
-        if eps is None:
-            self.eps.normal_()
-        if opp_eps is None:
-            self.opp_eps.normal_()
-        io = self.venv._io()
-        _lib.check(self.L.rx_selfplay_rollout_steps(self.venv._h, io, r[0], r[1], self.prec, _lib.stream_ptr(stream)),
-                   "rx_selfplay_rollout_steps")
-        self.venv._launched(stream)
+        self._run((obs, actions, logprobs, dones, rewards, values, next_obs, next_done), eps, opp_eps, stream)
 
 
 # config["fused_rollout"] = "auto": the persistent rollout up to this many envs

@@ -322,6 +322,14 @@ class RacingVectorEnv:
             io = self._io_cache[key] = self._make_io(actions, obs, reward, done, full)
         return io
 
+    def _io_info(self):
+        """The step's plain io plus the info rows (no float64 reward copy): what a
+        rollout loop with a tally reads.  A fresh struct; once per rollout."""
+        base = self._io()
+        io = _lib.RxIO(*(getattr(base, k) for k in _lib.IO_FIELDS))
+        io.info = _lib.ptr(self.buf["info"])
+        return io
+
     def _make_io(self, actions, obs, reward, done, full):
         b = self.buf
         return _lib.RxIO(
