@@ -151,7 +151,8 @@ typedef struct {
   int32_t* finished_step;/* [N*A] -1 = None (A==2 only; may be NULL for A==1) */
   uint8_t* flags;        /* [N*A] RX_F_* */
   int32_t* steps;        /* [N] */
-  int32_t* track;        /* [N] track slot (read-only for the kernels; set by rx_assign) */
+  int32_t* track;        /* [N] track slot: set by rx_assign, read-only for the step kernels; rewritten per
+                            env by rx_track_episode (episodic track draws) when its episode ends */
   uint8_t* env_flags;    /* [N] RX_EF_* */
   double* ep_return;     /* [N] episode return of agent 0 */
   int32_t* ep_length;    /* [N] */
@@ -1063,6 +1064,62 @@ int rx_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double 
 int rx_track_draw_host(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, void* stream);
 int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
                            int32_t precision, void* stream);
+
+/* ABI v25, additive: EPISODIC TRACK DRAWS -- an env takes a new track slot when its own
+ * episode ends, as prioritised level replay does, instead of every env being reset at a
+ * pool-level redraw (rx.track_episodic).  No episode is dropped and no env is reset by
+ * the curriculum.  For handles on the lane-varying schedule (rx_config.lane_tracks) with
+ * next-step autoreset: their wave order does not depend on the assignment and the kernels
+ * read an env's slot from one array, so rewriting that entry between the terminal step and
+ * the step that resets the env moves the env to another track.  The step, ray and policy
+ * kernels are the ones every other rollout runs.
+ *
+ * rx_track_episode over n envs: rx_track_tally, and every env it tallies (done[e] != 0,
+ * 0 <= track[e] < n_tracks) then draws its next slot, in this order:
+ *   tally row track[e] (rx_track_tally's rule);
+ *   g = draws[e];  k' = rx_track_draw's slot of env e at generation g under
+ *   seed ^ RX_TRACK_EPISODE_SALT (csrc/rx_curriculum.h: the keys (draws[e], e) stay apart
+ *   from rx_track_draw's (generation, e));  draws[e] = g + 1;  track[e] = k';
+ *   pos_slot[env_pos[e]] = k' when the two arrays are given (an env_pos outside [0, n)
+ *   is not written).
+ * slot_out[e], when given, receives the slot env e was on during this step, for every
+ * e < n, ended or not.  An env whose slot lies outside the table is neither tallied nor
+ * redrawn.  rx_track_io.track is WRITTEN here (and only here): it must be writable device
+ * memory although the field is declared const.  cdf is read as it stands (rx_track_scores
+ * fills it); p and track_of_env are not read.  The draw counters live in device memory,
+ * so a captured graph keeps advancing them on replay.  rx_track_episode_host: the same
+ * arguments as host pointers, no HIP call, the same bits.
+ *
+ * rx_track_episode_step: rx_track_episode on the handle's own wave-order arrays (the
+ * caller's env_pos / pos_slot are ignored) and the rows of `io` (terminated, info; `done`
+ * NULL = io->done_f32), after a step the caller enqueued on `stream`: eager loops and tests.
+ * rx_track_episodic_rollout_steps: rx_track_rollout_steps with rx_track_episode in the
+ * place of rx_track_tally: one launch per step, no host wait and no allocation; with
+ * `slots` (device int32 [T][N]) row t is step t's slot_out (ep->slot_out is ignored).
+ * In both, tc->track must be the handle's bound rx_state.track.
+ *
+ * Checked before any HIP call (RX_EINVAL, the message names the field): everything
+ * rx_track_tally and rx_track_draw check, null draws, exactly one of env_pos / pos_slot,
+ * a handle that is not an assigned, bound single-agent handle, a handle whose schedule is
+ * not lane-varying (set rx_config.lane_tracks = 1; that needs one lane per env, which
+ * handles of at most 2,048 envs take only with dyn_lpe = 1), an autoreset mode other than
+ * RX_AUTORESET_NEXT_STEP (same-step autoreset resets inside the step on the old slot;
+ * without autoreset nothing resets the env). */
+typedef struct rx_track_episode_io {
+  uint32_t* draws;        /* [N] draws taken so far by env e (zero-filled by the caller) */
+  const int32_t* env_pos; /* [N] position of env e in the wave order, or NULL */
+  int32_t* pos_slot;      /* [N] slot at each position, or NULL (both or neither) */
+  int32_t* slot_out;      /* [N] out, or NULL: the slot of env e during this step */
+  double mix;             /* rx_track_draw's mix, in [0, 1] */
+} rx_track_episode_io;
+int rx_track_episode(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, const float* done,
+                     const uint8_t* terminated, const double* info, void* stream);
+int rx_track_episode_host(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, const float* done,
+                          const uint8_t* terminated, const double* info, void* stream);
+int rx_track_episode_step(rx_env* h, const rx_track_io* tc, const rx_track_episode_io* ep, const rx_io* io,
+                          const float* done, void* stream);
+int rx_track_episodic_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
+                                    const rx_track_episode_io* ep, int32_t* slots, int32_t precision, void* stream);
 
 /* ABI v25, additive: the track curriculum's REPLAY SCORES -- the learning-potential
  * score, rank prioritisation and staleness of prioritised level replay (Jiang et

@@ -120,6 +120,8 @@ struct rx_env {
   int32_t task_sort = 1;                   // ray-task direction sort every task_sort dynamics launches
   int32_t lane_tracks = 0;                 // lane-varying slots (rx_config.lane_tracks, rx_assign's choice)
   DevBuf<int32_t> pos_slot;                // with lane_tracks: [N] slot of the env at each position
+  DevBuf<int32_t> env_pos;                 // with lane_tracks: [N] position of each env, the inverse of perm
+                                           // (rx_track_episode_step: the episodic draw rewrites pos_slot)
   DevBuf<uint8_t> policy_frag;  // the bf16 rollout's operand fragments of both trunks (k_policy_frag, rx_rollout_steps)
   int32_t ray_tail_from = -1;              // first ray wave of the tail (-1 = none)
   DevBuf<double> rel_angles;
@@ -408,6 +410,7 @@ int rx_destroy(rx_env* h) {
   }
   h->policy_frag.release();
   h->pos_slot.release();
+  h->env_pos.release();
   h->prof_buf.release();
   h->resets.release();
   h->draw_rank.release();
@@ -656,6 +659,8 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
     std::vector<int32_t> ps(N);
     for (int p = 0; p < N; ++p) ps[p] = track_of_env[perm[p]];
     if ((rc = upload(h->pos_slot, ps.data(), ps.size()))) return rc;
+    for (int p = 0; p < N; ++p) ps[perm[p]] = p;
+    if ((rc = upload(h->env_pos, ps.data(), ps.size()))) return rc;
   } else if (h->cfg.sort_interval > 0) {
     // spatial sort bins: slot k owns (W_k >> shift) + 1 consecutive bins from
     // sort_base[k]; the smallest shift that keeps all bins <= RX_SORT_MAX_BINS.
@@ -1445,8 +1450,11 @@ int rx_rollout(rx_env* h, const rx_io* io, const rx_rollout_io* r, void* stream)
 // rx_rollout_steps; with tc, rx_track_rollout_steps: one k_track_tally after every step, which reads
 // the done row the step just wrote and the env's terminated / info rows before the next step
 // overwrites them (one stream).  The policy and env launches are the same either way.
+// With ep as well, rx_track_episodic_rollout_steps: k_track_episode in the tally's place, so an env
+// that ended in step t is reset by step t + 1 from the slot it just drew; slots: [T][N] or null.
 static int rollout_loop(const char* fn, rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
-                        int32_t precision, void* stream) {
+                        int32_t precision, void* stream, const rx_track_episode_io* ep = nullptr,
+                        int32_t* slots = nullptr) {
   const int64_t N = h->cfg.n_envs, D = h->D;
   hipStream_t hs = (hipStream_t)stream;
   const void* frag;
@@ -1465,7 +1473,12 @@ static int rollout_loop(const char* fn, rx_env* h, const rx_io* io, const rx_rol
     s.reward = r->rewards + t * N;
     s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;
     if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
-    if (tc && (rc = rx_launch_track_tally(tc, N, s.done_f32, io->terminated, io->info, hs)) != 0)
+    if (ep) {
+      rx_track_episode_io e = *ep;
+      e.slot_out = slots ? slots + t * N : nullptr;
+      if ((rc = rx_launch_track_episode(tc, &e, N, s.done_f32, io->terminated, io->info, hs)) != 0)
+        return fail(RX_EHIP, "%s: episode launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+    } else if (tc && (rc = rx_launch_track_tally(tc, N, s.done_f32, io->terminated, io->info, hs)) != 0)
       return fail(RX_EHIP, "%s: tally launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
   }
   return RX_OK;
@@ -2401,6 +2414,93 @@ int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, c
     return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
                 !io->terminated ? "terminated" : "info");
   return rollout_loop(fn, h, io, r, tc, precision, stream);
+}
+
+// ABI v25, additive: episodic track draws (rx_track_episode, csrc/rx_curriculum.h).  The checks that
+// need no handle: rx_track_tally's, rx_track_draw's table and mix, and the episode io.
+static int track_episode_args(const char* fn, const rx_track_io* tc, const rx_track_episode_io* ep) {
+  const int rc = track_args(fn, tc, 0);
+  if (rc) return rc;
+  if (!tc->cdf) return fail(RX_EINVAL, "%s: null cdf", fn);
+  if (!ep) return fail(RX_EINVAL, "%s: null episode io", fn);
+  if (!ep->draws) return fail(RX_EINVAL, "%s: null draws", fn);
+  if (!ep->env_pos != !ep->pos_slot)
+    return fail(RX_EINVAL, "%s: null %s (env_pos and pos_slot: both or neither)", fn,
+                !ep->env_pos ? "env_pos" : "pos_slot");
+  if (!(ep->mix >= 0.0 && ep->mix <= 1.0)) return fail(RX_EINVAL, "%s: mix=%g outside [0, 1]", fn, ep->mix);
+  return RX_OK;
+}
+
+// the handle of the two handle-bound forms: lane-varying slots and next-step autoreset
+static int track_episode_handle(const char* fn, const rx_env* h, const rx_track_io* tc) {
+  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
+  if (!h->assigned || !h->bound || h->cfg.n_agents != 1)
+    return fail(RX_EINVAL, "%s: the handle must be an assigned, bound single-agent handle", fn);
+  if (!h->lane_tracks)
+    return fail(RX_EINVAL, "%s: the handle's schedule is not lane-varying: set rx_config.lane_tracks = 1 (it needs "
+                           "one lane per env: with at most %d envs set dyn_lpe = 1 as well)", fn, RX_WIDE_N);
+  if (h->cfg.autoreset != RX_AUTORESET_NEXT_STEP)
+    return fail(RX_EINVAL, "%s: autoreset=%d must be RX_AUTORESET_NEXT_STEP: the step after a terminal one resets "
+                           "the env from the slot just drawn", fn, h->cfg.autoreset);
+  if (tc->track != h->st.track)
+    return fail(RX_EINVAL, "%s: track must be the handle's bound rx_state.track", fn);
+  return RX_OK;
+}
+
+int rx_track_episode(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, const float* done,
+                     const uint8_t* terminated, const double* info, void* stream) {
+  const char* fn = "rx_track_episode";
+  int rc = track_episode_args(fn, tc, ep);
+  if (rc || (rc = track_tally_args(fn, tc, n, done, terminated, info)) != 0) return rc;
+  if ((rc = rx_launch_track_episode(tc, ep, n, done, terminated, info, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_episode_host(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, const float* done,
+                          const uint8_t* terminated, const double* info, void* /*stream*/) {
+  const char* fn = "rx_track_episode_host";
+  int rc = track_episode_args(fn, tc, ep);
+  if (rc || (rc = track_tally_args(fn, tc, n, done, terminated, info)) != 0) return rc;
+  rx_host_track_episode(tc, ep, n, done, terminated, info);
+  return RX_OK;
+}
+
+int rx_track_episode_step(rx_env* h, const rx_track_io* tc, const rx_track_episode_io* ep, const rx_io* io,
+                          const float* done, void* stream) {
+  const char* fn = "rx_track_episode_step";
+  int rc = track_episode_args(fn, tc, ep);
+  if (rc || (rc = track_episode_handle(fn, h, tc)) != 0) return rc;
+  if (!io) return fail(RX_EINVAL, "%s: null io", fn);
+  if (!done) done = io->done_f32;
+  if (!done || !io->terminated || !io->info)
+    return fail(RX_EINVAL, "%s: null %s", fn, !done ? "done" : !io->terminated ? "io->terminated" : "io->info");
+  rx_track_episode_io e = *ep;
+  e.env_pos = h->env_pos.p;
+  e.pos_slot = h->pos_slot.p;
+  if ((rc = rx_launch_track_episode(tc, &e, h->cfg.n_envs, done, io->terminated, io->info, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+// the single-agent rollout loop with the tally and the episodic draw (rollout_loop)
+int rx_track_episodic_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
+                                    const rx_track_episode_io* ep, int32_t* slots, int32_t precision, void* stream) {
+  const char* fn = "rx_track_episodic_rollout_steps";
+  // the track and episode ios first: their refusals need no handle
+  int rc = track_episode_args(fn, tc, ep);
+  if (rc) return rc;
+  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
+  if ((rc = track_episode_handle(fn, h, tc)) != 0) return rc;
+  if (!io || !r) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : "rollout io");
+  if ((rc = rollout_dims(fn, h, r)) != 0 || (rc = rollout_bufs(fn, r)) != 0) return rc;
+  if (!io->terminated || !io->info)
+    return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
+                !io->terminated ? "terminated" : "info");
+  rx_track_episode_io e = *ep;
+  e.env_pos = h->env_pos.p;
+  e.pos_slot = h->pos_slot.p;
+  return rollout_loop(fn, h, io, r, tc, precision, stream, &e, slots);
 }
 
 // ABI v25, additive: the curriculum's replay scores (csrc/rx_track_replay.h).  The checks of the four

@@ -26,6 +26,10 @@
 //      F == 0 or u < mix:  slot = mulhi64(h2, n_tracks)            (uniform)
 //      otherwise:          r = mulhi64(h2, F), slot = the smallest k with r < cdf_k
 //    so a slot with W_k == 0 is reached through the uniform part only.
+//  * the EPISODIC draw (rx_track_episode): an env whose episode ended on slot k is
+//    tallied into row k and then takes the draw above at generation g = draws[e], its
+//    own count of draws so far, under seed ^ RX_TRACK_EPISODE_SALT; draws[e] = g + 1.
+//    The salt keeps the keys (draws[e], e) apart from rx_track_draw's (generation, e).
 #pragma once
 
 #include <stdint.h>
@@ -39,6 +43,7 @@
 #define RX_TRACK_SCORES_CHUNK 1024 // slots k_track_scores scans per pass (one lane each)
 #define RX_TRACK_SCORE_FAIL 0
 #define RX_TRACK_SCORE_POTENTIAL 1
+#define RX_TRACK_EPISODE_SALT 0x9c3b5e2d7f1a8046ull  // the episodic draw's seed = seed ^ this
 
 RX_FN uint64_t rx_tc_mulhi64(uint64_t a, uint64_t b) {
 #if defined(__HIPCC__)
@@ -87,4 +92,19 @@ RX_FN int32_t rx_tc_draw(const int64_t* cdf, int32_t n_tracks, uint64_t seed, ui
   const uint64_t F = (uint64_t)cdf[n_tracks - 1];
   if (F == 0 || u < mix) return (int32_t)rx_tc_mulhi64(h2, (uint64_t)n_tracks);
   return rx_tc_search(cdf, n_tracks, rx_tc_mulhi64(h2, F));
+}
+
+// The episodic draw of env e, whose episode just ended on a slot inside the table: its
+// next slot at generation draws[e], which advances; track[e] and, when the wave-order
+// arrays are given, pos_slot[env_pos[e]] take it (a position outside [0, n) is not written).
+RX_FN int32_t rx_tc_episode_draw(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, int64_t e) {
+  const uint32_t g = ep->draws[e];
+  const int32_t k = rx_tc_draw(tc->cdf, tc->n_tracks, tc->seed ^ RX_TRACK_EPISODE_SALT, g, (uint32_t)e, ep->mix);
+  ep->draws[e] = g + 1u;
+  const_cast<int32_t*>(tc->track)[e] = k;
+  if (ep->env_pos) {
+    const int64_t pos = ep->env_pos[e];
+    if (pos >= 0 && pos < n) ep->pos_slot[pos] = k;
+  }
+  return k;
 }

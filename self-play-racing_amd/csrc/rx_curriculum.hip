@@ -1,8 +1,10 @@
-// rx_curriculum.hip -- the track curriculum's three kernels (ABI v25 additive;
+// rx_curriculum.hip -- the track curriculum's four kernels (ABI v25 additive;
 // rules in rx_curriculum.h, DESIGN.md §4 "Track curriculum"):
 //   k_track_tally   once per rollout step, a lane per env: the envs whose episode
 //                   ended are summed per track slot INSIDE the wave and one lane
 //                   per slot issues the int64 atomic adds;
+//   k_track_episode k_track_tally plus the episodic draw: an env that ended takes its
+//                   next slot at once (rx_track_episode);
 //   k_track_scores  once per resample, ONE workgroup: per-slot weight and the
 //                   inclusive integer scan into cdf, RX_TRACK_SCORES_CHUNK slots
 //                   per pass with the running total carried along;
@@ -74,6 +76,64 @@ __global__ __launch_bounds__(256) void k_track_tally(track_tally_args a) {
   }
 }
 
+struct track_episode_args {
+  rx_track_io tc;
+  rx_track_episode_io ep;
+  const float* done;
+  const uint8_t* terminated;
+  const double* info;  // [n][RX_INFO_W]
+  int64_t n;
+};
+
+// k_track_tally plus the episodic draw (rx_curriculum.h): an env that ended is tallied on
+// the slot it ran and then draws its next one into track[e] and pos_slot[env_pos[e]], which
+// the step after this launch resets it from (next-step autoreset).  The ballot, the fold
+// per slot inside the wave and the adders are k_track_tally's; every lane touches only its
+// own env's track / draws / pos_slot entries (env_pos is a permutation), so the draw needs
+// no atomics.  slot_out[e] is the slot env e was on, ended or not, written before the draw.
+__global__ __launch_bounds__(256) void k_track_episode(track_episode_args a) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = e < a.n;
+  const bool ended = in && a.done[e] != 0.0f;
+  const bool any = __ballot(ended) != 0ull;
+  int32_t k = -1;
+  if (in && (ended || a.ep.slot_out)) k = a.tc.track[e];
+  if (in && a.ep.slot_out) a.ep.slot_out[e] = k;
+  if (!any) return;
+  int32_t slot = -1;
+  int out = 0;
+  long long pq = 0;
+  if (ended && k >= 0 && k < a.tc.n_tracks) {  // a slot outside the table is neither counted nor redrawn
+    const double progress = a.info[(size_t)e * RX_INFO_W + RX_INFO_PROGRESS];
+    slot = k;
+    out = rx_tc_outcome(progress, a.terminated[e]);
+    pq = (long long)rx_tc_progress_q(progress);
+  }
+  const bool live = slot >= 0;
+  unsigned long long todo = __ballot(live);
+  const unsigned long long fin = __ballot(live && (out & 1)), crash = __ballot(live && (out & 2));
+  const int lane = (int)(threadIdx.x & 63);
+  while (todo) {
+    const int leader = __ffsll(todo) - 1;
+    const int32_t s = __builtin_amdgcn_readlane(slot, leader);  // wave-uniform: in [0, n_tracks)
+    const bool mine = live && slot == s;
+    const unsigned long long same = __ballot(mine);
+    long long sum = mine ? pq : 0;
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == leader) {
+      unsigned long long* row = reinterpret_cast<unsigned long long*>(a.tc.tally + (size_t)s * RX_TRACK_TALLY_W);
+      const unsigned long long nf = (unsigned long long)__popcll(same & fin);
+      const unsigned long long nc = (unsigned long long)__popcll(same & crash);
+      atomicAdd(row, (unsigned long long)__popcll(same));
+      if (nf) atomicAdd(row + 1, nf);
+      if (nc) atomicAdd(row + 2, nc);
+      if (sum) atomicAdd(row + 3, (unsigned long long)sum);
+    }
+    todo &= ~same;
+  }
+  if (live) rx_tc_episode_draw(&a.tc, &a.ep, a.n, e);
+}
+
 constexpr int kScoreThreads = RX_TRACK_SCORES_CHUNK;
 constexpr int kScoreWaves = kScoreThreads / 64;
 
@@ -126,6 +186,14 @@ extern "C" int rx_launch_track_tally(const rx_track_io* tc, int64_t n, const flo
                                      const double* info, hipStream_t s) {
   const track_tally_args a{tc->track, tc->tally, done, terminated, info, n, tc->n_tracks};
   hipLaunchKernelGGL(k_track_tally, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rx_launch_track_episode(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n,
+                                       const float* done, const uint8_t* terminated, const double* info,
+                                       hipStream_t s) {
+  const track_episode_args a{*tc, *ep, done, terminated, info, n};
+  hipLaunchKernelGGL(k_track_episode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
 

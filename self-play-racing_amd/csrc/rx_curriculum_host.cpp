@@ -1,6 +1,6 @@
 // rx_curriculum_host.cpp -- the host twins of the track curriculum's kernels
-// (rx_track_tally_host / rx_track_scores_host / rx_track_draw_host, ABI v25
-// additive): the loops of rx_curriculum.hip one env / one slot at a time over the
+// (rx_track_tally_host / rx_track_episode_host / rx_track_scores_host /
+// rx_track_draw_host, ABI v25 additive): the loops of rx_curriculum.hip one env / one slot at a time over the
 // same rx_curriculum.h functions.  Compiled as plain C++ (not as HIP), so
 // rx_curriculum.h takes its host form; rx_api.cpp checks the arguments before it
 // calls in here.  No HIP call.
@@ -20,6 +20,24 @@ extern "C" void rx_host_track_tally(const rx_track_io* tc, int64_t n, const floa
     if (out & 1) row[1] += 1;
     if (out & 2) row[2] += 1;
     row[3] += rx_tc_progress_q(progress);
+  }
+}
+
+// k_track_episode one env at a time: slot_out, the tally on the slot the env ran, then its draw
+extern "C" void rx_host_track_episode(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n,
+                                      const float* done, const uint8_t* terminated, const double* info) {
+  for (int64_t e = 0; e < n; ++e) {
+    const int32_t k = tc->track[e];
+    if (ep->slot_out) ep->slot_out[e] = k;
+    if (done[e] == 0.0f || k < 0 || k >= tc->n_tracks) continue;
+    const double progress = info[(size_t)e * RX_INFO_W + RX_INFO_PROGRESS];
+    const int out = rx_tc_outcome(progress, terminated[e]);
+    int64_t* row = tc->tally + (size_t)k * RX_TRACK_TALLY_W;
+    row[0] += 1;
+    if (out & 1) row[1] += 1;
+    if (out & 2) row[2] += 1;
+    row[3] += rx_tc_progress_q(progress);
+    rx_tc_episode_draw(tc, ep, n, e);
   }
 }
 

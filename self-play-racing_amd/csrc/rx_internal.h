@@ -397,6 +397,12 @@ extern "C" void rx_host_track_tally(const rx_track_io* tc, int64_t n, const floa
                                     const double* info);
 extern "C" void rx_host_track_scores(const rx_track_io* tc, int power, double prior);
 extern "C" void rx_host_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double mix);
+// the episodic draw: the tally plus the next slot of every env that ended, on the device and as a host loop
+extern "C" int rx_launch_track_episode(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n,
+                                       const float* done, const uint8_t* terminated, const double* info,
+                                       hipStream_t s);
+extern "C" void rx_host_track_episode(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n,
+                                      const float* done, const uint8_t* terminated, const double* info);
 // rx_track_replay.hip: advantages -> per-slot (samples, mag_q); the score fold; rank + the two integer tables;
 // the three-way env -> slot draw (arguments checked by rx_api.cpp)
 extern "C" int rx_launch_track_learn_tally(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,

@@ -41,7 +41,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_track_draw", "rx_track_draw_host", "rx_track_rollout_steps", "rx_track_learn_tally",
            "rx_track_learn_tally_host", "rx_track_learn_fold", "rx_track_learn_fold_host", "rx_track_learn_tables",
            "rx_track_learn_tables_host", "rx_track_learn_draw", "rx_track_learn_draw_host", "rx_track_evolve_plan",
-           "rx_track_evolve_plan_host", "rx_track_evolve", "rx_track_evolve_host")
+           "rx_track_evolve_plan_host", "rx_track_evolve", "rx_track_evolve_host", "rx_track_episode",
+           "rx_track_episode_host", "rx_track_episode_step", "rx_track_episodic_rollout_steps")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -166,6 +167,14 @@ TRACK_SCORES = {"fail": 0, "potential": 1}
 class RxTrackIO(ctypes.Structure):
     _fields_ = [("n_tracks", ctypes.c_int32), ("score", ctypes.c_int32), ("track", _P), ("tally", _P), ("cdf", _P),
                 ("p", _P), ("track_of_env", _P), ("seed", ctypes.c_uint64)]
+
+
+# episodic track draws (ABI v25, additive): an env takes a new slot when its episode ends (include/rx.h)
+RX_TRACK_EPISODE_SALT = 0x9C3B5E2D7F1A8046  # csrc/rx_curriculum.h
+
+
+class RxTrackEpisodeIO(ctypes.Structure):
+    _fields_ = [("draws", _P), ("env_pos", _P), ("pos_slot", _P), ("slot_out", _P), ("mix", ctypes.c_double)]
 
 
 # the curriculum's replay scores (ABI v25, additive): value-loss scores, rank and staleness draws (include/rx.h)
@@ -301,7 +310,14 @@ def load(build_if_missing=True):
                                           ctypes.POINTER(RxSelfplayIO), ctypes.POINTER(RxLeagueIO), ctypes.c_int32, _P]
     L.rx_track_rollout_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxRolloutIO),
                                          ctypes.POINTER(RxTrackIO), ctypes.c_int32, _P]
+    L.rx_track_episode_step.argtypes = [_P, ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackEpisodeIO),
+                                        ctypes.POINTER(RxIO), _P, _P]
+    L.rx_track_episodic_rollout_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxRolloutIO),
+                                                  ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackEpisodeIO), _P,
+                                                  ctypes.c_int32, _P]
     for sfx in ("", "_host"):
+        getattr(L, "rx_track_episode" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackEpisodeIO),
+                                                         ctypes.c_int64, _P, _P, _P, _P]
         getattr(L, "rx_track_tally" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.c_int64, _P, _P, _P, _P]
         getattr(L, "rx_track_scores" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.c_int32, ctypes.c_double, _P]
         getattr(L, "rx_track_draw" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.c_int64, ctypes.c_uint32,

@@ -86,6 +86,28 @@ class TrackCurriculum:
                                          _lib.ptr(b["done_f32"] if done is None else done), _lib.ptr(b["terminated"]),
                                          _lib.ptr(b["info"]), _lib.stream_ptr(stream)), "rx_track_tally")
 
+    def episodic(self):
+        """The episodic draw's io (rx_track_episode_io), made on first use: ``draws``
+        int32 [N] (the bits of the library's uint32 counters), zero-filled, at a fixed
+        address like the other tensors.  The handle-bound calls use the handle's own
+        wave-order arrays, so env_pos / pos_slot stay null here."""
+        if getattr(self, "ep", None) is None:
+            self.draws = torch.zeros(self.venv.num_envs, dtype=torch.int32, device=self.venv.device)
+            self.ep = _lib.RxTrackEpisodeIO(_lib.ptr(self.draws), None, None, None, self.mix)
+        return self.ep
+
+    def episode_step(self, done=None, stream=None):
+        """``tally_step`` plus the episodic draw (rx_track_episode_step): every env whose
+        episode ended in the step just enqueued is tallied and takes its next slot from
+        the table ``scores`` left, which the next step resets it on.  Lane-varying
+        handles with next-step autoreset only; the step must have run with
+        ``full_info=True``."""
+        ep, v = self.episodic(), self.venv
+        _lib.check(self.L.rx_track_episode_step(v._h, ctypes.byref(self.tc), ctypes.byref(ep), v._io_info(),
+                                                _lib.ptr(v.buf["done_f32"] if done is None else done),
+                                                _lib.stream_ptr(stream)), "rx_track_episode_step")
+        v._track_ids_stale = True  # the device moved envs between slots: track_ids() downloads them
+
     def scores(self, stream=None):
         """tallies -> ``p`` and the integer sampling table ``cdf`` (rx_track_scores)."""
         _lib.check(self.L.rx_track_scores(ctypes.byref(self.tc), self.power, self.prior, _lib.stream_ptr(stream)),
@@ -203,9 +225,16 @@ class CurriculumPPO(PPO):
         T, prec = obs.shape[0], ppo_fused.precision(c)
         sr = self.__dict__.get("_tc_steps_rollout")
         if sr is None or sr.T != T or sr.n != self.envs.num_envs or sr.prec != prec:
-            sr = self._tc_steps_rollout = CurriculumStepRollout(self.agent, self._flat, self.envs, T,
-                                                                 self.curriculum, prec)
+            sr = self._tc_steps_rollout = self._make_step_rollout(T, prec)
         return sr
+
+    def _make_step_rollout(self, T, prec):
+        """The rollout driver; with ``_after_step`` the two places a subclass changes what follows a step."""
+        return CurriculumStepRollout(self.agent, self._flat, self.envs, T, self.curriculum, prec)
+
+    def _after_step(self, done):
+        """The per-step loop's launch after every step: the tally of its done row."""
+        self.curriculum.tally_step(done)
 
     def _rollout_body(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done):
         sr = self._step_rollout(obs)
@@ -232,7 +261,7 @@ class CurriculumPPO(PPO):
             _, _, done = self.envs.step_device(action, obs_out=next_obs if last else obs[step + 1],
                                                reward_out=rewards[step],
                                                done_out=next_done if last else dones[step + 1], full_info=True)
-            self.curriculum.tally_step(done)
+            self._after_step(done)
 
     # ------------------------------------------------------------ resampling
     def _mastered(self):

@@ -1,0 +1,135 @@
+"""Episodic track draws: an env takes a new track when its own episode ends.
+
+``CurriculumPPO`` moves envs between tracks only by resetting all of them at a
+pool-level redraw, which drops the episodes in flight and runs rx_assign in host
+code.  Here the draw follows the episode, as prioritised level replay does: the
+kernel that tallies an ended episode (rx_track_episode, include/rx.h) also draws
+the env's next slot, and the next step's autoreset starts it there.  Nothing is
+dropped, nothing is reset by the curriculum, and the step, ray and policy kernels
+are the ones every other rollout runs.
+
+It needs a handle on the lane-varying schedule (``sched=dict(lane_tracks=1)``:
+the wave order does not depend on the assignment) with next-step autoreset.
+
+``EpisodicStepRollout``     ppo_fused.StepRollout on rx_track_episodic_rollout_steps;
+``EpisodicCurriculumPPO``   the trainer: CurriculumPPO without the global redraw.
+
+The rules are csrc/rx_curriculum.h; DESIGN.md §4 "Episodic track draws".
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from .curriculum import CurriculumPPO, CurriculumStepRollout
+from .ppo import build_vector_env
+from . import dist as rdist
+
+
+class EpisodicStepRollout(CurriculumStepRollout):
+    """rx_track_episodic_rollout_steps driver: CurriculumStepRollout with the
+    episodic draw in the tally's place.  ``record_slots=True`` keeps ``slots``,
+    int32 [T, N]: the slot every env ran at every step of the last rollout.  The
+    draw counters (``curriculum.draws``) and ``slots`` sit at fixed addresses and
+    the counters live on the device, so a captured graph of the call keeps drawing
+    fresh slots on replay."""
+
+    FN = "rx_track_episodic_rollout_steps"
+
+    def __init__(self, agent, flat, venv, T, curriculum, prec=_lib.RX_PREC_FP32, record_slots=False):
+        super().__init__(agent, flat, venv, T, curriculum, prec)
+        self.ep = curriculum.episodic()
+        self.slots = torch.zeros((T, venv.num_envs), dtype=torch.int32, device=venv.device) if record_slots else None
+
+    def _enqueue(self, args, stream):
+        _lib.check(self.L.rx_track_episodic_rollout_steps(self.venv._h, self.venv._io_info(), *args,
+                                                          ctypes.byref(self.curriculum.tc), ctypes.byref(self.ep),
+                                                          _lib.ptr(self.slots), self.prec, stream), self.FN)
+        self.venv._track_ids_stale = True  # the device moved envs between slots: track_ids() downloads them
+
+
+class EpisodicCurriculumPPO(CurriculumPPO):
+    """CurriculumPPO whose envs change track one at a time, when their episode ends.
+
+    The envs are built on the lane-varying schedule (``lane_tracks`` = 1); the
+    sampling table is refreshed (rx_track_scores) before the rollout of every
+    ``config["episodic_scores_every"]`` (1) updates; ``reassign_tracks`` is never
+    called.  ``resample_tracks`` with nothing to retire only refreshes the scores
+    and hands back the rollout's own next_obs / next_done; with slots retired it is
+    the parent's ``set_tracks`` path, which resets every env: set
+    ``curriculum_refresh`` to 0 to keep the run free of global resets.
+    ``config["episodic_slots"]`` = True records the [T, N] slots of each rollout
+    (``slots()``).
+
+    Refused (ValueError): what CurriculumPPO refuses, and envs whose schedule does
+    not come out lane-varying or whose autoreset is not next-step."""
+
+    def __init__(self, env_fn, config, device="cuda"):
+        self.scores_every = int(config.get("episodic_scores_every", 1))
+        if self.scores_every < 1:
+            raise ValueError(f"episodic_scores_every={self.scores_every} must be >= 1")
+        self._updates = 0
+        self._carry = None  # the last rollout's (next_obs, next_done)
+        super().__init__(env_fn, config, device)
+
+    def _make_envs(self, env_fn):
+        c = self.config
+        lo, n = rdist.shard(c["num_envs"])
+        fn = env_fn if lo == 0 else (lambda i: env_fn(lo + i))
+        envs = build_vector_env(fn, n, c["seed"] + rdist.rank(), self.device,
+                                track_backend=c.get("track_backend", "scipy"), sched=dict(lane_tracks=1))
+        check_episodic(envs)
+        return envs
+
+    # ------------------------------------------------------------ rollout
+    def _make_step_rollout(self, T, prec):
+        return EpisodicStepRollout(self.agent, self._flat, self.envs, T, self.curriculum, prec,
+                                   bool(self.config.get("episodic_slots", False)))
+
+    def _after_step(self, done):
+        self.curriculum.episode_step(done)  # the per-step loop: the tally and the draw of every step
+
+    def collect_rollout(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done):
+        if self._updates % self.scores_every == 0:
+            self.curriculum.scores()  # outside any captured graph: the draws read the table it leaves
+        self._updates += 1
+        out = super().collect_rollout(obs, actions, logprobs, dones, rewards, values, next_obs, next_done)
+        self._carry = (out[6], out[7])
+        return out
+
+    def slots(self):
+        """int32 [T, N]: the slot of every env at every step of the last rollout
+        (``config["episodic_slots"]``), or None."""
+        sr = self.__dict__.get("_tc_steps_rollout")
+        return None if sr is None else sr.slots
+
+    # ------------------------------------------------------------ resampling
+    def resample_tracks(self, control_points=None, widths=None):
+        """With no arguments and no slot to retire: the scores only; the envs keep
+        running and the rollout's own (next_obs, next_done) come back.  Otherwise
+        ``CurriculumPPO.resample_tracks``' ``set_tracks`` path: new tracks in the retired
+        slots, every env redrawn and reset."""
+        if control_points is None and widths is None:
+            self.curriculum.scores()
+            if not len(self._mastered()):
+                self.retired.append([])
+                if self._carry is not None:
+                    return self._carry
+                return self.envs.buf["obs"].clone(), torch.zeros(self.num_local_envs, device=self.device)
+        return super().resample_tracks(control_points, widths)
+
+
+def check_episodic(envs):
+    """ValueError unless ``envs`` can take episodic draws: single-agent, lane-varying
+    schedule, next-step autoreset (what rx_track_episode_step refuses, before any launch)."""
+    if envs.n_agents != 1:
+        raise ValueError("episodic track draws move single-agent envs only (DESIGN.md §8)")
+    if envs.autoreset != "next_step":
+        raise ValueError(f"episodic track draws need autoreset='next_step', got {envs.autoreset!r}: same-step "
+                         "autoreset resets inside the step on the old slot (DESIGN.md §8)")
+    if not envs.schedule()["lane_tracks"]:
+        raise ValueError("episodic track draws need the lane-varying schedule: build the envs with "
+                         "sched=dict(lane_tracks=1) (with at most 2,048 envs, dyn_lpe=1 as well)")
+
+
+__all__ = ["EpisodicStepRollout", "EpisodicCurriculumPPO", "check_episodic"]

@@ -242,6 +242,27 @@ class RacingVectorEnv:
     def tracks(self, track_set):
         self._tracks = track_set
 
+    @property
+    def track_of_env(self):
+        """The slot of every env, host int32 [N].  Once episodic track draws have run
+        (rx.track_episodic sets ``_track_ids_stale``) the device moves envs between
+        slots, and a read first downloads the current ids (``track_ids``)."""
+        if self._track_ids_stale:
+            self.track_ids()
+        return self._track_of_env
+
+    @track_of_env.setter
+    def track_of_env(self, slots):
+        self._track_of_env, self._track_ids_stale = slots, False
+
+    def track_ids(self):
+        """Download the envs' current slots (the bound ``track`` array, which rx_assign
+        sets and rx_track_episode rewrites per env) -> ``track_of_env``, host int32 [N].
+        Synchronises with the device."""
+        torch.cuda.synchronize(self.device)  # the draws may have run on another stream
+        self.track_of_env = self._st["track"].cpu().numpy()
+        return self._track_of_env
+
     def set_tracks(self, table, track_of_env=None):
         """Swap the track pool of the live env for ``table`` (an
         rx.track_device.DeviceTrackTable on this env's device): env i runs slot

@@ -4,6 +4,7 @@
     python tools/curriculum_train.py --envs 64 --steps 32 --updates 6 --tracks 8 --resample-every 2 --no-uniform
     python tools/curriculum_train.py --replay value_l1 --envs 4096 --steps 128 --updates 60 --tracks 512
     python tools/curriculum_train.py --evolve --envs 4096 --steps 128 --updates 60 --tracks 512
+    python tools/curriculum_train.py --episodic --envs 4096 --steps 128 --updates 60 --tracks 512
 
 ``CurriculumPPO`` on a pool of ``--tracks`` distinct tracks (env i starts on slot
 i % tracks): every finished episode is tallied against its slot on the device;
@@ -22,6 +23,10 @@ instead of the finish tallies; ``off`` (the default) runs ``CurriculumPPO``.
 With ``--evolve`` it is ``rx.track_evolve.EvolvingCurriculumPPO``: the replay draw
 (``--replay``, value_l1 when left off) and the retired slots filled on the device,
 a fraction ``--evolve-edit`` of them by edited children of high-ranked tracks.
+With ``--episodic`` it is ``rx.track_episodic.EpisodicCurriculumPPO``: an env draws
+its next slot when its own episode ends, no episode is dropped, and a resample
+with nothing to retire resets nobody.  Every curriculum run also reports the
+episodes tallied per update and the slots that reached ``--min-episodes``.
 """
 import argparse
 import json
@@ -67,11 +72,18 @@ def run(kind, args, evaluator):
     if evolve:
         from rx.track_evolve import EvolvingCurriculumPPO as cls
         cfg["evolve_edit"] = args.evolve_edit
+    episodic = kind == "curriculum" and args.episodic
+    if episodic:
+        if replay or evolve:
+            sys.exit("--episodic draws by the finish tallies: not with --replay or --evolve (DESIGN.md §8)")
+        from rx.track_episodic import EpisodicCurriculumPPO as cls
     t = cls(lambda i: RacingEnv(num_sensors=11, track_pool=pool, track_id=i % n, track_width=widths[i % n]), cfg,
             device="cuda")
-    info, curve = {"steps": [], "rewards": []}, []
+    info, curve, tallied = {"steps": [], "rewards": []}, [], []
     for update, num_updates, gstep, ep in t.train_iter():
         t._log(update, num_updates, gstep, ep, info)
+        if kind == "curriculum":  # the tally's running episode total (retired slots start again at 0)
+            tallied.append(int(t.curriculum.tally[:, 0].sum().item()))
         if (update + 1) % args.eval_every == 0 or update + 1 == num_updates:
             s = evaluator.run(t.agent)
             curve.append({"update": update + 1, "env_steps": gstep, "success_rate": s["success_rate"],
@@ -88,6 +100,9 @@ def run(kind, args, evaluator):
         out["track_table"] = {k: [None if isinstance(x, float) and np.isnan(x) else x for x in v.tolist()]
                               for k, v in tab.items()}
         out["retired_per_resample"] = [len(r) for r in t.retired]
+        out["episodic"] = bool(episodic)
+        out["tally_episodes_after_update"] = tallied
+        out["slots_at_min_episodes"] = int((np.asarray(tab["episodes"]) >= args.min_episodes).sum())
     t.envs.close()
     return out
 
@@ -115,6 +130,8 @@ def main():
     ap.add_argument("--evolve", action="store_true",
                     help="fill the retired slots on the device (rx.track_evolve): fresh tracks and edited children")
     ap.add_argument("--evolve-edit", type=float, default=0.5, help="the fraction of retired slots filled by an edit")
+    ap.add_argument("--episodic", action="store_true",
+                    help="an env draws its next slot when its episode ends (rx.track_episodic), no global redraw")
     ap.add_argument("--prec", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--show", type=int, default=20, help="slots of the table to print, the most failed first")
