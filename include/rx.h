@@ -1194,6 +1194,57 @@ int rx_track_learn_draw(const rx_track_learn_io* lt, int64_t n, uint32_t generat
 int rx_track_learn_draw_host(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix,
                              double stale_mix, void* stream);
 
+/* ABI v25, additive: the REPLAY SCORES ON EPISODIC DRAWS -- prioritised level replay per
+ * episode: an env whose episode ends draws its next slot from the score / staleness /
+ * uniform mix, and the advantages are tallied by the slot every step ran on
+ * (rx.track_replay_episodic).  The two blocks above are untouched.
+ *
+ * rx_track_learn_tally_slots over adv f32 [T][n], slots int32 [T][n] and dones f32 [T][n]
+ * (or NULL): element (t, e) is counted iff adv[t][e] is finite, 0 <= slots[t][e] <
+ * n_tracks, and dones is NULL or dones[t][e] == 0; a counted element adds samples += 1,
+ * mag_q += q (rx_track_learn_tally's q and kind) to row slots[t][e] of learn.  A rollout
+ * row entered with dones[t][e] != 0 is the autoreset step (next-step autoreset): its
+ * observation is the old track's terminal one, its action is ignored, its successor is the
+ * new track's first observation and the recorded slot is already the new one, so its
+ * advantage belongs to neither slot.  Integer sums: the result does not depend on the grid,
+ * the chunking or the order of arrival and equals the serial host loop bit for bit; with
+ * slots[t][e] == track[e] for every t and dones NULL it is rx_track_learn_tally's.  Only
+ * n_tracks, kind and learn of the io are read (track may be NULL).
+ *
+ * rx_track_learn_episode: rx_track_episode with the next slot drawn from the replay tables:
+ *   k' = rx_track_learn_draw's slot of env e at generation g = draws[e] under
+ *   lt->seed ^ RX_TRACK_EPISODE_SALT, with ep->mix and stale_mix.
+ * The tally into tc->tally, slot_out (written before the draw), draws, track and pos_slot are
+ * rx_track_episode's; a slot outside the table is neither tallied nor redrawn.  tc supplies
+ * n_tracks, track and tally (cdf and p are not read); lt supplies cdf_score, cdf_stale
+ * (may be NULL when stale_mix == 0) and seed.  With lt->cdf_score == tc->cdf, lt->seed ==
+ * tc->seed and stale_mix == 0 every output equals rx_track_episode's bit for bit.
+ * rx_track_learn_episode_step and rx_track_learn_episodic_rollout_steps are the
+ * counterparts of rx_track_episode_step and rx_track_episodic_rollout_steps (the same
+ * handle rules, the same launches but for the draw's kernel).
+ *
+ * Checked before any HIP call (RX_EINVAL, the message names the field): what
+ * rx_track_learn_tally checks but for track, null slots; everything rx_track_episode checks
+ * but for tc->cdf, lt->n_tracks != tc->n_tracks, null cdf_score, stale_mix or mix +
+ * stale_mix outside [0, 1] or NaN, null cdf_stale with stale_mix > 0; the handle rules of
+ * rx_track_episode_step. */
+int rx_track_learn_tally_slots(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
+                               const int32_t* slots, const float* dones, void* stream);
+int rx_track_learn_tally_slots_host(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
+                                    const int32_t* slots, const float* dones, void* stream);
+int rx_track_learn_episode(const rx_track_io* tc, const rx_track_learn_io* lt, const rx_track_episode_io* ep,
+                           double stale_mix, int64_t n, const float* done, const uint8_t* terminated,
+                           const double* info, void* stream);
+int rx_track_learn_episode_host(const rx_track_io* tc, const rx_track_learn_io* lt, const rx_track_episode_io* ep,
+                                double stale_mix, int64_t n, const float* done, const uint8_t* terminated,
+                                const double* info, void* stream);
+int rx_track_learn_episode_step(rx_env* h, const rx_track_io* tc, const rx_track_learn_io* lt,
+                                const rx_track_episode_io* ep, double stale_mix, const rx_io* io, const float* done,
+                                void* stream);
+int rx_track_learn_episodic_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
+                                          const rx_track_learn_io* lt, const rx_track_episode_io* ep, double stale_mix,
+                                          int32_t* slots, int32_t precision, void* stream);
+
 /* ABI v25, additive: TRACK EVOLUTION -- what fills the track slots the curriculum
  * retires, written by a kernel into a device-resident control-point buffer
  * (rx.track_evolve): a fresh track of the host generator's distribution, or a small

@@ -1452,9 +1452,10 @@ int rx_rollout(rx_env* h, const rx_io* io, const rx_rollout_io* r, void* stream)
 // overwrites them (one stream).  The policy and env launches are the same either way.
 // With ep as well, rx_track_episodic_rollout_steps: k_track_episode in the tally's place, so an env
 // that ended in step t is reset by step t + 1 from the slot it just drew; slots: [T][N] or null.
+// With lt too, rx_track_learn_episodic_rollout_steps: k_track_learn_episode in that launch's place.
 static int rollout_loop(const char* fn, rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
                         int32_t precision, void* stream, const rx_track_episode_io* ep = nullptr,
-                        int32_t* slots = nullptr) {
+                        int32_t* slots = nullptr, const rx_track_learn_io* lt = nullptr, double stale_mix = 0.0) {
   const int64_t N = h->cfg.n_envs, D = h->D;
   hipStream_t hs = (hipStream_t)stream;
   const void* frag;
@@ -1476,8 +1477,9 @@ static int rollout_loop(const char* fn, rx_env* h, const rx_io* io, const rx_rol
     if (ep) {
       rx_track_episode_io e = *ep;
       e.slot_out = slots ? slots + t * N : nullptr;
-      if ((rc = rx_launch_track_episode(tc, &e, N, s.done_f32, io->terminated, io->info, hs)) != 0)
-        return fail(RX_EHIP, "%s: episode launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+      rc = lt ? rx_launch_track_learn_episode(tc, lt, &e, stale_mix, N, s.done_f32, io->terminated, io->info, hs)
+              : rx_launch_track_episode(tc, &e, N, s.done_f32, io->terminated, io->info, hs);
+      if (rc != 0) return fail(RX_EHIP, "%s: episode launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
     } else if (tc && (rc = rx_launch_track_tally(tc, N, s.done_f32, io->terminated, io->info, hs)) != 0)
       return fail(RX_EHIP, "%s: tally launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
   }
@@ -2418,10 +2420,12 @@ int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, c
 
 // ABI v25, additive: episodic track draws (rx_track_episode, csrc/rx_curriculum.h).  The checks that
 // need no handle: rx_track_tally's, rx_track_draw's table and mix, and the episode io.
-static int track_episode_args(const char* fn, const rx_track_io* tc, const rx_track_episode_io* ep) {
+// table: whether the draw reads tc->cdf (the replay forms read rx_track_learn_io's tables instead).
+static int track_episode_args(const char* fn, const rx_track_io* tc, const rx_track_episode_io* ep,
+                              bool table = true) {
   const int rc = track_args(fn, tc, 0);
   if (rc) return rc;
-  if (!tc->cdf) return fail(RX_EINVAL, "%s: null cdf", fn);
+  if (table && !tc->cdf) return fail(RX_EINVAL, "%s: null cdf", fn);
   if (!ep) return fail(RX_EINVAL, "%s: null episode io", fn);
   if (!ep->draws) return fail(RX_EINVAL, "%s: null draws", fn);
   if (!ep->env_pos != !ep->pos_slot)
@@ -2623,6 +2627,118 @@ int rx_track_learn_draw_host(const rx_track_learn_io* lt, int64_t n, uint32_t ge
   if (rc) return rc;
   rx_host_track_learn_draw(lt, n, generation, mix, stale_mix);
   return RX_OK;
+}
+
+// ABI v25, additive: the replay scores on episodic draws -- the tally by per-step slot and the
+// episode-end draw from the replay tables (csrc/rx_track_replay.h).  Checks before any HIP call.
+static int learn_tally_slots_args(const char* fn, const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
+                                  const int32_t* slots) {
+  const int rc = learn_io(fn, lt);
+  if (rc) return rc;
+  if (lt->kind != 0 && lt->kind != 1) return fail(RX_EINVAL, "%s: kind=%d must be 0 or 1", fn, lt->kind);
+  if (!lt->learn) return learn_null(fn, "learn");
+  if (T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, T);
+  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
+  if (!adv) return learn_null(fn, "adv");
+  if (!slots) return learn_null(fn, "slots");
+  return RX_OK;
+}
+
+int rx_track_learn_tally_slots(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
+                               const int32_t* slots, const float* dones, void* stream) {
+  const char* fn = "rx_track_learn_tally_slots";
+  int rc = learn_tally_slots_args(fn, lt, T, n, adv, slots);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_learn_tally_slots(lt, T, n, adv, slots, dones, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_learn_tally_slots_host(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
+                                    const int32_t* slots, const float* dones, void* /*stream*/) {
+  const int rc = learn_tally_slots_args("rx_track_learn_tally_slots_host", lt, T, n, adv, slots);
+  if (rc) return rc;
+  rx_host_track_learn_tally_slots(lt, T, n, adv, slots, dones);
+  return RX_OK;
+}
+
+// the checks of the replay episodic forms that need no handle: rx_track_episode's but for tc->cdf,
+// then the learn io's tables and the two mixes (rx_track_learn_draw's rules)
+static int learn_episode_args(const char* fn, const rx_track_io* tc, const rx_track_learn_io* lt,
+                              const rx_track_episode_io* ep, double stale_mix) {
+  int rc = track_episode_args(fn, tc, ep, false);
+  if (rc || (rc = learn_io(fn, lt)) != 0) return rc;
+  if (lt->n_tracks != tc->n_tracks)
+    return fail(RX_EINVAL, "%s: n_tracks=%d of the track learn io != n_tracks=%d of the track io", fn, lt->n_tracks,
+                tc->n_tracks);
+  if (!lt->cdf_score) return learn_null(fn, "cdf_score");
+  if (!(stale_mix >= 0.0 && stale_mix <= 1.0))
+    return fail(RX_EINVAL, "%s: stale_mix=%g outside [0, 1]", fn, stale_mix);
+  if (!(ep->mix + stale_mix <= 1.0))
+    return fail(RX_EINVAL, "%s: mix + stale_mix = %g + %g above 1", fn, ep->mix, stale_mix);
+  if (stale_mix > 0.0 && !lt->cdf_stale) return learn_null(fn, "cdf_stale");
+  return RX_OK;
+}
+
+int rx_track_learn_episode(const rx_track_io* tc, const rx_track_learn_io* lt, const rx_track_episode_io* ep,
+                           double stale_mix, int64_t n, const float* done, const uint8_t* terminated,
+                           const double* info, void* stream) {
+  const char* fn = "rx_track_learn_episode";
+  int rc = learn_episode_args(fn, tc, lt, ep, stale_mix);
+  if (rc || (rc = track_tally_args(fn, tc, n, done, terminated, info)) != 0) return rc;
+  if ((rc = rx_launch_track_learn_episode(tc, lt, ep, stale_mix, n, done, terminated, info, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_learn_episode_host(const rx_track_io* tc, const rx_track_learn_io* lt, const rx_track_episode_io* ep,
+                                double stale_mix, int64_t n, const float* done, const uint8_t* terminated,
+                                const double* info, void* /*stream*/) {
+  const char* fn = "rx_track_learn_episode_host";
+  int rc = learn_episode_args(fn, tc, lt, ep, stale_mix);
+  if (rc || (rc = track_tally_args(fn, tc, n, done, terminated, info)) != 0) return rc;
+  rx_host_track_learn_episode(tc, lt, ep, stale_mix, n, done, terminated, info);
+  return RX_OK;
+}
+
+int rx_track_learn_episode_step(rx_env* h, const rx_track_io* tc, const rx_track_learn_io* lt,
+                                const rx_track_episode_io* ep, double stale_mix, const rx_io* io, const float* done,
+                                void* stream) {
+  const char* fn = "rx_track_learn_episode_step";
+  int rc = learn_episode_args(fn, tc, lt, ep, stale_mix);
+  if (rc || (rc = track_episode_handle(fn, h, tc)) != 0) return rc;
+  if (!io) return fail(RX_EINVAL, "%s: null io", fn);
+  if (!done) done = io->done_f32;
+  if (!done || !io->terminated || !io->info)
+    return fail(RX_EINVAL, "%s: null %s", fn, !done ? "done" : !io->terminated ? "io->terminated" : "io->info");
+  rx_track_episode_io e = *ep;
+  e.env_pos = h->env_pos.p;
+  e.pos_slot = h->pos_slot.p;
+  if ((rc = rx_launch_track_learn_episode(tc, lt, &e, stale_mix, h->cfg.n_envs, done, io->terminated, io->info,
+                                          (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+// the single-agent rollout loop with the tally and the episodic draw from the replay tables (rollout_loop)
+int rx_track_learn_episodic_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
+                                          const rx_track_learn_io* lt, const rx_track_episode_io* ep, double stale_mix,
+                                          int32_t* slots, int32_t precision, void* stream) {
+  const char* fn = "rx_track_learn_episodic_rollout_steps";
+  // the track, learn and episode ios first: their refusals need no handle
+  int rc = learn_episode_args(fn, tc, lt, ep, stale_mix);
+  if (rc) return rc;
+  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
+  if ((rc = track_episode_handle(fn, h, tc)) != 0) return rc;
+  if (!io || !r) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : "rollout io");
+  if ((rc = rollout_dims(fn, h, r)) != 0 || (rc = rollout_bufs(fn, r)) != 0) return rc;
+  if (!io->terminated || !io->info)
+    return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
+                !io->terminated ? "terminated" : "info");
+  rx_track_episode_io e = *ep;
+  e.env_pos = h->env_pos.p;
+  e.pos_slot = h->pos_slot.p;
+  return rollout_loop(fn, h, io, r, tc, precision, stream, &e, slots, lt, stale_mix);
 }
 
 // ABI v25, additive: track evolution (csrc/rx_track_evolve.h).  The checks of the two entry points and

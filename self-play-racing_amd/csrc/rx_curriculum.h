@@ -97,14 +97,64 @@ RX_FN int32_t rx_tc_draw(const int64_t* cdf, int32_t n_tracks, uint64_t seed, ui
 // The episodic draw of env e, whose episode just ended on a slot inside the table: its
 // next slot at generation draws[e], which advances; track[e] and, when the wave-order
 // arrays are given, pos_slot[env_pos[e]] take it (a position outside [0, n) is not written).
-RX_FN int32_t rx_tc_episode_draw(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, int64_t e) {
-  const uint32_t g = ep->draws[e];
-  const int32_t k = rx_tc_draw(tc->cdf, tc->n_tracks, tc->seed ^ RX_TRACK_EPISODE_SALT, g, (uint32_t)e, ep->mix);
+// what every episodic draw writes: the counter past generation g, and the slot k drawn at g
+RX_FN void rx_tc_episode_move(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, int64_t e, uint32_t g,
+                              int32_t k) {
   ep->draws[e] = g + 1u;
   const_cast<int32_t*>(tc->track)[e] = k;
   if (ep->env_pos) {
     const int64_t pos = ep->env_pos[e];
     if (pos >= 0 && pos < n) ep->pos_slot[pos] = k;
   }
+}
+
+RX_FN int32_t rx_tc_episode_draw(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, int64_t e) {
+  const uint32_t g = ep->draws[e];
+  const int32_t k = rx_tc_draw(tc->cdf, tc->n_tracks, tc->seed ^ RX_TRACK_EPISODE_SALT, g, (uint32_t)e, ep->mix);
+  rx_tc_episode_move(tc, ep, n, e, g, k);
   return k;
 }
+
+#if defined(__HIPCC__)
+// The tally of one episodic launch, shared by k_track_episode and k_track_learn_episode
+// (rx_track_replay.hip): the envs that ended (slot k inside the table) are folded per slot INSIDE
+// the wave -- a leader slot read from the lowest pending lane, its lanes balloted, the counts
+// popcounts against the finished / crashed ballots, progress_q a butterfly sum -- and ONE lane adds
+// the non-zero columns.  EVERY lane of the wave must call it (ballots and shuffles); returns
+// whether this lane's env was tallied, which is also whether it draws.
+RX_FN bool rx_tc_wave_episode_tally(int64_t* tally, int32_t n_tracks, bool ended, int32_t k,
+                                    const uint8_t* terminated, const double* info, int64_t e) {
+  int32_t slot = -1;
+  int out = 0;
+  long long pq = 0;
+  if (ended && k >= 0 && k < n_tracks) {  // a slot outside the table is neither counted nor redrawn
+    const double progress = info[(size_t)e * RX_INFO_W + RX_INFO_PROGRESS];
+    slot = k;
+    out = rx_tc_outcome(progress, terminated[e]);
+    pq = (long long)rx_tc_progress_q(progress);
+  }
+  const bool live = slot >= 0;
+  unsigned long long todo = __ballot(live);
+  const unsigned long long fin = __ballot(live && (out & 1)), crash = __ballot(live && (out & 2));
+  const int lane = (int)(threadIdx.x & 63);
+  while (todo) {
+    const int leader = __ffsll(todo) - 1;
+    const int32_t s = __builtin_amdgcn_readlane(slot, leader);  // wave-uniform: in [0, n_tracks)
+    const bool mine = live && slot == s;
+    const unsigned long long same = __ballot(mine);
+    long long sum = mine ? pq : 0;
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == leader) {
+      unsigned long long* row = reinterpret_cast<unsigned long long*>(tally + (size_t)s * RX_TRACK_TALLY_W);
+      const unsigned long long nf = (unsigned long long)__popcll(same & fin);
+      const unsigned long long nc = (unsigned long long)__popcll(same & crash);
+      atomicAdd(row, (unsigned long long)__popcll(same));
+      if (nf) atomicAdd(row + 1, nf);
+      if (nc) atomicAdd(row + 2, nc);
+      if (sum) atomicAdd(row + 3, (unsigned long long)sum);
+    }
+    todo &= ~same;
+  }
+  return live;
+}
+#endif

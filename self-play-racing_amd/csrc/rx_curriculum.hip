@@ -88,7 +88,8 @@ struct track_episode_args {
 // k_track_tally plus the episodic draw (rx_curriculum.h): an env that ended is tallied on
 // the slot it ran and then draws its next one into track[e] and pos_slot[env_pos[e]], which
 // the step after this launch resets it from (next-step autoreset).  The ballot, the fold
-// per slot inside the wave and the adders are k_track_tally's; every lane touches only its
+// per slot inside the wave and the adders are k_track_tally's (rx_tc_wave_episode_tally, shared
+// with k_track_learn_episode); every lane touches only its
 // own env's track / draws / pos_slot entries (env_pos is a permutation), so the draw needs
 // no atomics.  slot_out[e] is the slot env e was on, ended or not, written before the draw.
 __global__ __launch_bounds__(256) void k_track_episode(track_episode_args a) {
@@ -100,37 +101,7 @@ __global__ __launch_bounds__(256) void k_track_episode(track_episode_args a) {
   if (in && (ended || a.ep.slot_out)) k = a.tc.track[e];
   if (in && a.ep.slot_out) a.ep.slot_out[e] = k;
   if (!any) return;
-  int32_t slot = -1;
-  int out = 0;
-  long long pq = 0;
-  if (ended && k >= 0 && k < a.tc.n_tracks) {  // a slot outside the table is neither counted nor redrawn
-    const double progress = a.info[(size_t)e * RX_INFO_W + RX_INFO_PROGRESS];
-    slot = k;
-    out = rx_tc_outcome(progress, a.terminated[e]);
-    pq = (long long)rx_tc_progress_q(progress);
-  }
-  const bool live = slot >= 0;
-  unsigned long long todo = __ballot(live);
-  const unsigned long long fin = __ballot(live && (out & 1)), crash = __ballot(live && (out & 2));
-  const int lane = (int)(threadIdx.x & 63);
-  while (todo) {
-    const int leader = __ffsll(todo) - 1;
-    const int32_t s = __builtin_amdgcn_readlane(slot, leader);  // wave-uniform: in [0, n_tracks)
-    const bool mine = live && slot == s;
-    const unsigned long long same = __ballot(mine);
-    long long sum = mine ? pq : 0;
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if (lane == leader) {
-      unsigned long long* row = reinterpret_cast<unsigned long long*>(a.tc.tally + (size_t)s * RX_TRACK_TALLY_W);
-      const unsigned long long nf = (unsigned long long)__popcll(same & fin);
-      const unsigned long long nc = (unsigned long long)__popcll(same & crash);
-      atomicAdd(row, (unsigned long long)__popcll(same));
-      if (nf) atomicAdd(row + 1, nf);
-      if (nc) atomicAdd(row + 2, nc);
-      if (sum) atomicAdd(row + 3, (unsigned long long)sum);
-    }
-    todo &= ~same;
-  }
+  const bool live = rx_tc_wave_episode_tally(a.tc.tally, a.tc.n_tracks, ended, k, a.terminated, a.info, e);
   if (live) rx_tc_episode_draw(&a.tc, &a.ep, a.n, e);
 }
 

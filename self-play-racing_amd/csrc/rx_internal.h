@@ -411,6 +411,19 @@ extern "C" int rx_launch_track_learn_fold(const rx_track_learn_io* lt, int32_t u
 extern "C" int rx_launch_track_learn_tables(const rx_track_learn_io* lt, int32_t power, int32_t now, hipStream_t s);
 extern "C" int rx_launch_track_learn_draw(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix,
                                           double stale_mix, hipStream_t s);
+// the tally by per-step slot and the episodic draw from the replay tables (rx_track_learn_tally_slots,
+// rx_track_learn_episode), on the device and as host loops
+extern "C" int rx_launch_track_learn_tally_slots(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
+                                                 const int32_t* slots, const float* dones, hipStream_t s);
+extern "C" int rx_launch_track_learn_episode(const rx_track_io* tc, const rx_track_learn_io* lt,
+                                             const rx_track_episode_io* ep, double stale_mix, int64_t n,
+                                             const float* done, const uint8_t* terminated, const double* info,
+                                             hipStream_t s);
+extern "C" void rx_host_track_learn_tally_slots(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
+                                                const int32_t* slots, const float* dones);
+extern "C" void rx_host_track_learn_episode(const rx_track_io* tc, const rx_track_learn_io* lt,
+                                            const rx_track_episode_io* ep, double stale_mix, int64_t n,
+                                            const float* done, const uint8_t* terminated, const double* info);
 // rx_track_replay_host.cpp: the same four as host loops (plain C++, no HIP call)
 extern "C" void rx_host_track_learn_tally(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv);
 extern "C" void rx_host_track_learn_fold(const rx_track_learn_io* lt, int32_t update, double alpha);

@@ -30,6 +30,14 @@
 //      u < mix + stale_mix and F_stale > 0:   search cdf_stale with mulhi64(h2, F_stale)
 //      otherwise:                             search cdf_score (uniform when its total is 0)
 //    With stale_mix == 0 it is rx_tc_draw on cdf_score bit for bit.
+//  * the tally by per-step slot (rx_track_learn_tally_slots): element (t, e) counts on row
+//    slots[t][e] iff adv[t][e] is finite, the slot lies inside the table and dones is null or
+//    dones[t][e] == 0.  A row entered with dones != 0 is the autoreset step: its observation is
+//    the old track's terminal one, its successor the new track's first, and its advantage belongs
+//    to neither slot.
+//  * the episodic draw from the replay tables (rx_track_learn_episode): rx_track_episode with
+//    the draw above in rx_tc_draw's place, at generation draws[e] under
+//    seed ^ RX_TRACK_EPISODE_SALT (rx_curriculum.h).
 #pragma once
 
 #include <stdint.h>
@@ -114,4 +122,21 @@ RX_FN int32_t rx_tl_draw(const int64_t* cdf_score, const int64_t* cdf_stale, int
   const uint64_t F = (uint64_t)cdf_score[n_tracks - 1];
   if (F == 0) return (int32_t)rx_tc_mulhi64(h2, (uint64_t)n_tracks);
   return rx_tc_search(cdf_score, n_tracks, rx_tc_mulhi64(h2, F));
+}
+
+// whether element (slot, done flag, advantage) of the per-step tally counts; *q = its magnitude
+RX_FN int rx_tl_counts(int32_t slot, int32_t n_tracks, float done, float a, int kind, int64_t* q) {
+  if (done != 0.0f || slot < 0 || slot >= n_tracks) return 0;
+  return rx_tl_mag_q(a, kind, q);
+}
+
+// rx_tc_episode_draw from the replay tables: the next slot of env e, whose episode just ended on a
+// slot inside the table, at generation draws[e], which advances
+RX_FN int32_t rx_tl_episode_draw(const rx_track_io* tc, const rx_track_episode_io* ep, const int64_t* cdf_score,
+                                 const int64_t* cdf_stale, uint64_t seed, double stale_mix, int64_t n, int64_t e) {
+  const uint32_t g = ep->draws[e];
+  const int32_t k = rx_tl_draw(cdf_score, cdf_stale, tc->n_tracks, seed ^ RX_TRACK_EPISODE_SALT, g, (uint32_t)e,
+                               ep->mix, stale_mix);
+  rx_tc_episode_move(tc, ep, n, e, g, k);
+  return k;
 }

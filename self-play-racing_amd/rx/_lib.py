@@ -42,7 +42,9 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_track_learn_tally_host", "rx_track_learn_fold", "rx_track_learn_fold_host", "rx_track_learn_tables",
            "rx_track_learn_tables_host", "rx_track_learn_draw", "rx_track_learn_draw_host", "rx_track_evolve_plan",
            "rx_track_evolve_plan_host", "rx_track_evolve", "rx_track_evolve_host", "rx_track_episode",
-           "rx_track_episode_host", "rx_track_episode_step", "rx_track_episodic_rollout_steps")
+           "rx_track_episode_host", "rx_track_episode_step", "rx_track_episodic_rollout_steps",
+           "rx_track_learn_tally_slots", "rx_track_learn_tally_slots_host", "rx_track_learn_episode",
+           "rx_track_learn_episode_host", "rx_track_learn_episode_step", "rx_track_learn_episodic_rollout_steps")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -315,6 +317,13 @@ def load(build_if_missing=True):
     L.rx_track_episodic_rollout_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxRolloutIO),
                                                   ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackEpisodeIO), _P,
                                                   ctypes.c_int32, _P]
+    L.rx_track_learn_episode_step.argtypes = [_P, ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackLearnIO),
+                                              ctypes.POINTER(RxTrackEpisodeIO), ctypes.c_double, ctypes.POINTER(RxIO),
+                                              _P, _P]
+    L.rx_track_learn_episodic_rollout_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxRolloutIO),
+                                                        ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackLearnIO),
+                                                        ctypes.POINTER(RxTrackEpisodeIO), ctypes.c_double, _P,
+                                                        ctypes.c_int32, _P]
     for sfx in ("", "_host"):
         getattr(L, "rx_track_episode" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackEpisodeIO),
                                                          ctypes.c_int64, _P, _P, _P, _P]
@@ -324,6 +333,10 @@ def load(build_if_missing=True):
                                                       ctypes.c_double, _P]
         lt = ctypes.POINTER(RxTrackLearnIO)
         getattr(L, "rx_track_learn_tally" + sfx).argtypes = [lt, ctypes.c_int32, ctypes.c_int64, _P, _P]
+        getattr(L, "rx_track_learn_tally_slots" + sfx).argtypes = [lt, ctypes.c_int32, ctypes.c_int64, _P, _P, _P, _P]
+        getattr(L, "rx_track_learn_episode" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), lt,
+                                                               ctypes.POINTER(RxTrackEpisodeIO), ctypes.c_double,
+                                                               ctypes.c_int64, _P, _P, _P, _P]
         getattr(L, "rx_track_learn_fold" + sfx).argtypes = [lt, ctypes.c_int32, ctypes.c_double, _P]
         getattr(L, "rx_track_learn_tables" + sfx).argtypes = [lt, ctypes.c_int32, ctypes.c_int32, _P]
         getattr(L, "rx_track_learn_draw" + sfx).argtypes = [lt, ctypes.c_int64, ctypes.c_uint32, ctypes.c_double,

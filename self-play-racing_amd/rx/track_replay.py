@@ -13,7 +13,9 @@ power), and every env draws its slot from a three-way mix: uniform, staleness
 
 ``TrackReplay``          the device tensors (learn, score, seen, rank, cdf_score,
                          cdf_stale, track_of_env) and the four calls
-                         (rx_track_learn_tally / _fold / _tables / _draw);
+                         (rx_track_learn_tally / _fold / _tables / _draw), plus the
+                         two of the episodic form (``tally_slots``, ``episode_step``:
+                         rx.track_replay_episodic);
 ``ReplayCurriculumPPO``  ``CurriculumPPO`` with the tally after the GAE launch and
                          the replay draw in ``resample_tracks``.
 
@@ -86,6 +88,41 @@ class TrackReplay:
                              f"device, got {tuple(advantages.shape)} {advantages.dtype}")
         _lib.check(self.L.rx_track_learn_tally(ctypes.byref(self.lt), advantages.shape[0], n, _lib.ptr(advantages),
                                                _lib.stream_ptr(stream)), "rx_track_learn_tally")
+
+    def tally_slots(self, advantages, slots, dones=None, stream=None):
+        """``tally`` with the slot of every element read from ``slots`` (int32 [T, N], the
+        slot env e ran at step t: episodic draws move an env inside a rollout) and, with
+        ``dones`` (float32 [T, N], the rollout's done rows), without the autoreset rows
+        ``dones[t, e] != 0``, whose advantage belongs to neither the old slot nor the new
+        one (rx_track_learn_tally_slots)."""
+        n, dev = self.venv.num_envs, self.learn.device
+        T = advantages.shape[0] if advantages.dim() == 2 else -1
+        for name, x, dtype in (("advantages", advantages, torch.float32), ("slots", slots, torch.int32),
+                               ("dones", dones, torch.float32)):
+            if x is None and name == "dones":
+                continue
+            if x is None or tuple(x.shape) != (T, n) or x.dtype != dtype or not x.is_contiguous() or x.device != dev:
+                raise ValueError(f"rx_track_learn_tally_slots: {name} must be a contiguous {dtype} [T, {n}] on the "
+                                 f"env's device, got {None if x is None else (tuple(x.shape), x.dtype)}")
+        _lib.check(self.L.rx_track_learn_tally_slots(ctypes.byref(self.lt), T, n, _lib.ptr(advantages),
+                                                     _lib.ptr(slots), _lib.ptr(dones), _lib.stream_ptr(stream)),
+                   "rx_track_learn_tally_slots")
+
+    def episode_step(self, curriculum, done=None, stream=None, slot_out=None):
+        """``TrackCurriculum.episode_step`` with the next slot drawn from the replay tables
+        (rx_track_learn_episode_step): every env whose episode ended in the step just
+        enqueued is tallied into ``curriculum.tally`` and takes its next slot from the
+        tables ``tables`` left, at its own counter ``curriculum.draws``.  ``slot_out``
+        (int32 [N]) receives the slot every env ran in this step."""
+        v = self.venv
+        ep = curriculum.episodic()
+        if slot_out is not None:
+            ep = _lib.RxTrackEpisodeIO(ep.draws, None, None, _lib.ptr(slot_out), ep.mix)
+        _lib.check(self.L.rx_track_learn_episode_step(v._h, ctypes.byref(curriculum.tc), ctypes.byref(self.lt),
+                                                      ctypes.byref(ep), self.stale_mix, v._io_info(),
+                                                      _lib.ptr(v.buf["done_f32"] if done is None else done),
+                                                      _lib.stream_ptr(stream)), "rx_track_learn_episode_step")
+        v._track_ids_stale = True  # the device moved envs between slots: track_ids() downloads them
 
     def fold(self, update, stream=None):
         """``learn`` -> ``score`` and ``seen`` of the slots that have samples; ``learn``

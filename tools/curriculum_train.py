@@ -5,6 +5,7 @@
     python tools/curriculum_train.py --replay value_l1 --envs 4096 --steps 128 --updates 60 --tracks 512
     python tools/curriculum_train.py --evolve --envs 4096 --steps 128 --updates 60 --tracks 512
     python tools/curriculum_train.py --episodic --envs 4096 --steps 128 --updates 60 --tracks 512
+    python tools/curriculum_train.py --episodic --replay value_l1 --envs 4096 --steps 128 --updates 60 --tracks 512
 
 ``CurriculumPPO`` on a pool of ``--tracks`` distinct tracks (env i starts on slot
 i % tracks): every finished episode is tallied against its slot on the device;
@@ -25,8 +26,13 @@ With ``--evolve`` it is ``rx.track_evolve.EvolvingCurriculumPPO``: the replay dr
 a fraction ``--evolve-edit`` of them by edited children of high-ranked tracks.
 With ``--episodic`` it is ``rx.track_episodic.EpisodicCurriculumPPO``: an env draws
 its next slot when its own episode ends, no episode is dropped, and a resample
-with nothing to retire resets nobody.  Every curriculum run also reports the
-episodes tallied per update and the slots that reached ``--min-episodes``.
+with nothing to retire resets nobody; with ``--replay`` as well it is
+``rx.track_replay_episodic.EpisodicReplayCurriculumPPO``, whose ended envs draw
+from the value-loss scores (prioritised level replay per episode).  ``--episodic
+--evolve`` is refused.  Every curriculum run also reports the
+episodes tallied per update, the slots that reached ``--min-episodes`` and, per
+update, the share of the envs on the fullest slot (with replay scores also on the
+slot ranked first).
 """
 import argparse
 import json
@@ -74,16 +80,21 @@ def run(kind, args, evaluator):
         cfg["evolve_edit"] = args.evolve_edit
     episodic = kind == "curriculum" and args.episodic
     if episodic:
-        if replay or evolve:
-            sys.exit("--episodic draws by the finish tallies: not with --replay or --evolve (DESIGN.md §8)")
         from rx.track_episodic import EpisodicCurriculumPPO as cls
+        if replay:
+            from rx.track_replay_episodic import EpisodicReplayCurriculumPPO as cls
     t = cls(lambda i: RacingEnv(num_sensors=11, track_pool=pool, track_id=i % n, track_width=widths[i % n]), cfg,
             device="cuda")
-    info, curve, tallied = {"steps": [], "rewards": []}, [], []
+    info, curve, tallied, top_share, rank1_share = {"steps": [], "rewards": []}, [], [], [], []
     for update, num_updates, gstep, ep in t.train_iter():
         t._log(update, num_updates, gstep, ep, info)
         if kind == "curriculum":  # the tally's running episode total (retired slots start again at 0)
             tallied.append(int(t.curriculum.tally[:, 0].sum().item()))
+            ids = t.envs._st["track"].long()  # where the envs stand after this update's rollout
+            top_share.append(round(torch.bincount(ids, minlength=n).max().item() / ids.numel(), 4))
+            if hasattr(t, "replay"):  # the slot ranked first by the tables the last draws read
+                first = int(torch.argmin(t.replay.rank).item())
+                rank1_share.append(round((ids == first).float().mean().item(), 4))
         if (update + 1) % args.eval_every == 0 or update + 1 == num_updates:
             s = evaluator.run(t.agent)
             curve.append({"update": update + 1, "env_steps": gstep, "success_rate": s["success_rate"],
@@ -102,6 +113,8 @@ def run(kind, args, evaluator):
         out["retired_per_resample"] = [len(r) for r in t.retired]
         out["episodic"] = bool(episodic)
         out["tally_episodes_after_update"] = tallied
+        out["share_of_envs_on_the_fullest_slot_after_update"] = top_share
+        out["share_of_envs_on_the_rank1_slot_after_update"] = rank1_share if rank1_share else None
         out["slots_at_min_episodes"] = int((np.asarray(tab["episodes"]) >= args.min_episodes).sum())
     t.envs.close()
     return out
@@ -138,6 +151,8 @@ def main():
     ap.add_argument("--no-uniform", action="store_true", help="skip the uniform PPO run")
     ap.add_argument("--out", default="bench_out/curriculum_train.json")
     args = ap.parse_args()
+    if args.episodic and args.evolve:
+        sys.exit("--episodic moves envs between the slots of a fixed table: not with --evolve (DESIGN.md §8)")
     if not torch.cuda.is_available():
         sys.exit("curriculum_train.py trains on the GPU: no device found")
     from rx.evaluate import Evaluator
