@@ -291,6 +291,51 @@ typedef struct {
 } rx_io_strides;
 int rx_steps(rx_env* h, const rx_io* io, int32_t n_steps, const rx_io_strides* strides, void* stream);
 
+/* The launch schedule of an rx_steps call on a single-agent split-step handle, as a pure
+ * function (no device, no handle; additive to ABI v25): the launches of K steps, in order.
+ * A step passes through a KIN part (behind the REWARD of the step before it, or a k_kin1
+ * launch at the head of the call and after every re-sort), a REWARD part, optionally a
+ * ranking of its ray tasks, and its ray cast; rx_steps turns the records into pointers.
+ * Slots index rings: pose 3 * depth (by step), task rows 2 * depth + 1 (by ranking; -1 = the
+ * handle's task buffer), crossing snapshots RX_PLAN_CROSS_RING (by re-sort; -1 = the live
+ * row ids and progress), shadow obs rows depth - 1 (-1 = the caller's rows).
+ * rx_steps_plan fills at most `cap` records and returns how many the call has (< 0: bad
+ * arguments); record 0 is the prologue: no launch, only kin1_after = 0. */
+#define RX_PLAN_MAX_DEPTH 8
+#define RX_PLAN_CROSS_RING 3
+typedef struct {
+  int32_t n_steps;        /* K >= 1 */
+  int32_t depth;          /* sub-steps, rank steps and ray steps per launch: 2 .. RX_PLAN_MAX_DEPTH; 0 = what
+                             rx_steps takes for a call of n_steps (written back) */
+  int32_t sort_interval;  /* 0 = no re-sort; step s is a re-sort step when (dyn_calls + s) % sort_interval == 0 */
+  int32_t dyn_calls;      /* the handle's dynamics launches so far (any value with the right phase) */
+  int32_t task_sort;      /* rank every task_sort-th step and after every re-sort; 0 = the handle ranks nothing */
+  int32_t task_calls;     /* the handle's ranking turns so far (phase) */
+  int32_t tasks_stale;    /* the handle's task buffer is stale: the next step is ranked */
+  int32_t cross;          /* steps may stay queued across a re-sort (snapshots available) */
+  int32_t rank_in_kin;    /* 1 = the lag-1 schedule: KIN parts rank, rays are cast one launch after the KIN;
+                             -1 = what rx_steps takes for a call of n_steps (written back) */
+  /* out: */
+  int32_t ranked;           /* steps ranked by the call */
+  int32_t tasks_stale_out;  /* the handle's task buffer is stale after the call */
+} rx_plan_args;
+typedef struct {
+  int32_t n_sub, n_rank, n_rays;
+  int32_t first_step;                    /* sub-step j is REWARD first_step + j */
+  int32_t kin[RX_PLAN_MAX_DEPTH];        /* ... followed by KIN first_step + j + 1 */
+  int32_t kin_pose[RX_PLAN_MAX_DEPTH];   /* pose slot that KIN stores */
+  int32_t kin_row[RX_PLAN_MAX_DEPTH];    /* rank_in_kin: task row that KIN ranks into, or -1 */
+  int32_t keys;                          /* the last REWARD is a re-sort step's: it writes the sort keys */
+  int32_t keys_snap;                     /* ... and this crossing snapshot, or -1 (nothing stays queued) */
+  int32_t rank_step[RX_PLAN_MAX_DEPTH], rank_pose[RX_PLAN_MAX_DEPTH], rank_row[RX_PLAN_MAX_DEPTH];
+  int32_t ray_step[RX_PLAN_MAX_DEPTH], ray_pose[RX_PLAN_MAX_DEPTH], ray_row[RX_PLAN_MAX_DEPTH];
+  int32_t ray_snap[RX_PLAN_MAX_DEPTH], ray_shadow[RX_PLAN_MAX_DEPTH];
+  int32_t sort_after;                    /* the re-sort runs behind this launch */
+  int32_t kin1_after;                    /* then a k_kin1 launch of this step (-1: none) */
+  int32_t kin1_pose, kin1_row;           /* its pose slot; rank_in_kin: its task row or -1 */
+} rx_plan_launch;
+int32_t rx_steps_plan(rx_plan_args* args, rx_plan_launch* out, int32_t cap);
+
 /* rx_step split into its two kernels, for per-kernel timing with stream
  * events: phases bit 0 = dynamics/reward/done/autoreset (k_dyn), bit 1 =
  * raycast observations (k_rays).  rx_step == phases 3.  Running bit 1 alone

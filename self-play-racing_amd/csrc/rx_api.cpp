@@ -147,11 +147,12 @@ struct rx_env {
   bool split = true;
   // rx_steps' carrying schedule: rings of snapshots of what the ray waves read -- the stepped
   // pose ([3][N] x, y, angle) and the sorted task ids -- written by a step's KIN part, and a
-  // shadow of the obs rows for the older of two ray steps that would write the same rows
-  // (stride-0 outputs)
+  // shadow of the obs rows for every ray step of a launch but its newest, which would write
+  // the same rows (stride-0 outputs); the task rows are written by the RANK workgroups of the
+  // deep launch (rx_internal.h)
   DevBuf<double> snap_pose[RX_PAIR_RING];
-  DevBuf<int32_t> snap_tasks[RX_PAIR_RING];
-  DevBuf<float> obs_shadow;
+  DevBuf<int32_t> snap_tasks[RX_TASK_RING];
+  DevBuf<float> obs_shadow[RX_SHADOW_ROWS];
   DevBuf<int32_t> snap_rows[RX_CROSS_RING];  // the crossing step's row ids and visiting-order hint (pre-sort)
   DevBuf<double> snap_hint[RX_CROSS_RING];
   // rx_profile: per recorded launch, [RX_PROF_SLOTS] wave start + [RX_PROF_SLOTS] wave end stamps
@@ -399,11 +400,9 @@ int rx_destroy(rx_env* h) {
                   &h->slot_n, &h->tasks})
     b->release();
   h->cs_scratch.release();
-  for (int b = 0; b < RX_PAIR_RING; ++b) {
-    h->snap_pose[b].release();
-    h->snap_tasks[b].release();
-  }
-  h->obs_shadow.release();
+  for (int b = 0; b < RX_PAIR_RING; ++b) h->snap_pose[b].release();
+  for (int b = 0; b < RX_TASK_RING; ++b) h->snap_tasks[b].release();
+  for (int b = 0; b < RX_SHADOW_ROWS; ++b) h->obs_shadow[b].release();
   for (int b = 0; b < RX_CROSS_RING; ++b) {
     h->snap_rows[b].release();
     h->snap_hint[b].release();
@@ -705,11 +704,12 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
     const std::vector<double> zd(3 * (size_t)N, 0.0);
     const std::vector<int32_t> zi((size_t)N * R, 0);
     const std::vector<float> zf((size_t)N * h->D, 0.0f);
-    for (int b = 0; b < RX_PAIR_RING; ++b) {
+    for (int b = 0; b < RX_PAIR_RING; ++b)
       if ((rc = upload(h->snap_pose[b], zd.data(), zd.size()))) return rc;
-      if (h->cfg.ray_order == 2 && (rc = upload(h->snap_tasks[b], zi.data(), zi.size()))) return rc;
-    }
-    if ((rc = upload(h->obs_shadow, zf.data(), zf.size()))) return rc;
+    for (int b = 0; b < RX_TASK_RING && h->cfg.ray_order == 2; ++b)
+      if ((rc = upload(h->snap_tasks[b], zi.data(), zi.size()))) return rc;
+    for (int b = 0; b < RX_SHADOW_ROWS; ++b)
+      if ((rc = upload(h->obs_shadow[b], zf.data(), zf.size()))) return rc;
     for (int b = 0; b < RX_CROSS_RING && RX_STEPS_CROSS && h->sort_on; ++b) {  // the crossing step's
       if ((rc = upload(h->snap_rows[b], zi.data(), (size_t)N))) return rc;
       if ((rc = upload(h->snap_hint[b], zd.data(), (size_t)N))) return rc;
@@ -1159,6 +1159,165 @@ static rx_io io_at(const rx_io* io, const rx_io_strides& st, int64_t s) {
   return o;
 }
 
+// The schedule of K steps as launch records (include/rx.h; DESIGN.md §3 "The carried step",
+// "The paired launch", "The crossing step", "The deep launch").  Block b's KIN part of step
+// k + 1 needs only block b's REWARD results of step k, so REWARD workgroup b of a k_step2_pair
+// launch runs it and k_kin1 leaves the step; a launch's REWARD workgroups advance up to
+// `depth` steps D_k = (REWARD k, KIN k + 1).  KIN k + 1 overwrites what the ray waves of step
+// k read, so every KIN part also stores its pose to a snapshot and the ray waves read that.
+// They read nothing else that a later step writes and nothing of a later step reads what they
+// write, so once KIN k's launch has completed they can be cast in ANY later launch.
+//
+// A step goes through two queues.  `to_rank`: KIN done in an earlier launch, ray tasks not
+// ranked yet; `to_cast`: ranked (or passed over by the task_sort cadence) in an earlier
+// launch, rays not cast.  Every launch casts all of to_cast, ranks all of to_rank in RANK
+// workgroups and refills to_rank with the steps its KIN parts (and the k_kin1 behind it)
+// stepped -- so a step's KIN, ranking and rays are three launches in a row, and neither
+// queue ever holds more than `depth` steps:
+//   k_kin1(0) [D0 D1 | rank 0] [D2 D3 | rank 1 2 | rays 0] [D4 D5 | rank 3 4 | rays 1 2] ...
+// A handle that ranks nothing (task_sort 0) and the lag-1 schedule (rank_in_kin: the KIN
+// parts rank, as before the deep launch) skip to_rank, and so does a step passed over by the
+// cadence while to_rank is empty.  A step passed over by the cadence
+// reads the row of the last ranked step before it, or the handle's task buffer when the call
+// has ranked none; the call writes ring rows only and leaves the handle's buffer marked stale
+// once it has ranked anything (a valid, older order; the next dynamics launch sorts).
+//
+// A re-sort step, and the call's last step, has no KIN behind its REWARD and ends its
+// launch's chain; the re-sort step's REWARD writes the keys, the sort follows the launch and
+// a k_kin1 of the next step follows the sort.  With `cross` every step still queued at the
+// sort is cast (and ranked) after it from its ring slots, which the sort leaves alone, and
+// from the snapshots of perm and progress that the key-writing REWARD stored; without it the
+// key-writing REWARD waits for a launch that leaves the queues empty.  At the end of the call
+// launches without sub-steps drain the queues.  Rings: see include/rx.h.
+int32_t rx_steps_plan(rx_plan_args* in, rx_plan_launch* out, int32_t cap) {
+  static_assert(RX_PLAN_CROSS_RING == RX_CROSS_RING && RX_STEPS_DEPTH <= RX_PLAN_MAX_DEPTH, "include/rx.h");
+  if (in && in->n_steps >= 1 && in->rank_in_kin < 0)  // the library's own choice for a call of this length
+    in->rank_in_kin = RX_STEPS_RANK_IN_KIN || in->n_steps < RX_STEPS_DEEP_MIN_K;
+  if (in && in->n_steps >= 1 && in->depth == 0)
+    in->depth = in->rank_in_kin ? 2 : in->n_steps < RX_STEPS_FULL_MIN_K ? std::min(4, RX_STEPS_DEPTH) : RX_STEPS_DEPTH;
+  if (!in || in->n_steps < 1 || in->depth < 2 || in->depth > RX_PLAN_MAX_DEPTH || in->sort_interval < 0 ||
+      in->task_sort < 0 || in->dyn_calls < 0 || in->task_calls < 0 || cap < 0 || (cap > 0 && !out))
+    return -1;
+  const int32_t K = in->n_steps, D = in->depth, P = 3 * D, T = 2 * D + 1, C = RX_PLAN_CROSS_RING;
+  const bool lag1 = in->rank_in_kin != 0, ranking = in->task_sort > 0;
+  struct qstep {
+    int32_t k, pose, row, snap;  // row: what its rays read; snap: -1 while its window is the live one
+    bool ranked;                 // ... and it is ranked into `row` itself
+  };
+  std::vector<qstep> to_rank, to_cast, stepped;
+  bool stale = in->tasks_stale != 0;
+  int64_t tcalls = in->task_calls;
+  int32_t cur_row = -1, tb = 0, cb = 0, ranked = 0, n_out = 0, k = 0;
+  auto resort_step = [&](int32_t s) {
+    return in->sort_interval > 0 && ((int64_t)in->dyn_calls + s) % in->sort_interval == 0;
+  };
+  // step s's KIN part is being scheduled now (in step order: the cadence is K x rx_step's)
+  auto kin = [&](int32_t s) {
+    bool r = false;
+    if (ranking) {
+      r = stale || tcalls % in->task_sort == 0;
+      if (r) stale = false, cur_row = tb, tb = (tb + 1) % T, ++ranked;
+      ++tcalls;
+    }
+    return qstep{s, s % P, cur_row, -1, r};
+  };
+  auto blank = [] {
+    rx_plan_launch L{};
+    L.first_step = -1, L.keys_snap = -1, L.kin1_after = -1, L.kin1_pose = -1, L.kin1_row = -1;
+    for (int i = 0; i < RX_PLAN_MAX_DEPTH; ++i) {
+      L.kin_pose[i] = L.kin_row[i] = L.rank_step[i] = L.rank_pose[i] = L.rank_row[i] = -1;
+      L.ray_step[i] = L.ray_pose[i] = L.ray_row[i] = L.ray_snap[i] = L.ray_shadow[i] = -1;
+    }
+    return L;
+  };
+  auto emit = [&](const rx_plan_launch& L) {
+    if (n_out < cap) out[n_out] = L;
+    ++n_out;
+  };
+  // A stepped step joins to_rank, or to_cast at once when nothing ranks it and no step before
+  // it is still to be ranked (the row it reads was then written by an earlier launch)
+  bool ranks_empty = true;  // the launch being planned ranks nothing and passes nothing on
+  auto enqueue = [&](const qstep& q) {
+    const bool direct = lag1 || !ranking || (!q.ranked && ranks_empty && to_rank.empty());
+    (direct ? to_cast : to_rank).push_back(q);
+  };
+  auto kin1_behind = [&](rx_plan_launch& L, int32_t s) {
+    const qstep q = kin(s);
+    L.kin1_after = s, L.kin1_pose = q.pose, L.kin1_row = lag1 && q.ranked ? q.row : -1;
+    enqueue(q);
+  };
+  {
+    rx_plan_launch L = blank();
+    kin1_behind(L, 0);
+    emit(L);
+  }
+  while (k < K || !to_rank.empty() || !to_cast.empty()) {
+    if ((int32_t)to_cast.size() > D || (int32_t)to_rank.size() > D) return -2;  // (never: see above)
+    rx_plan_launch L = blank();
+    L.n_rays = (int32_t)to_cast.size();
+    for (int32_t r = 0; r < L.n_rays; ++r) {
+      const qstep& q = to_cast[r];
+      L.ray_step[r] = q.k, L.ray_pose[r] = q.pose, L.ray_row[r] = q.row, L.ray_snap[r] = q.snap;
+      L.ray_shadow[r] = r + 1 < L.n_rays ? r : -1;  // the newest writes the caller's rows
+    }
+    to_cast.clear();
+    for (const qstep& q : to_rank) {
+      if (q.ranked) {
+        L.rank_step[L.n_rank] = q.k, L.rank_pose[L.n_rank] = q.pose, L.rank_row[L.n_rank] = q.row;
+        ++L.n_rank;
+      }
+      to_cast.push_back(q);
+    }
+    ranks_empty = to_rank.empty();
+    to_rank.clear();
+    stepped.clear();
+    int32_t n = 0;
+    while (n < D && k < K) {
+      const bool keyed = resort_step(k), last = k + 1 == K;
+      if (keyed) {
+        // may steps stay queued across this sort?  lag 1: the crossing step is the second
+        // sub-step, a step follows it in the call, and its task row is a ring row
+        bool crosses = in->cross != 0;
+        if (lag1) crosses = crosses && n == 1 && !last && (!ranking || stepped.back().row >= 0);
+        if (!crosses && !(n == 0 && ranks_empty)) break;  // else: the launch that empties the queues
+      } else if (lag1 && last && n > 0) {
+        break;  // lag 1: the call's last step keeps its own launch (REWARD beside its own rays)
+      }
+      if (n == 0) L.first_step = k;
+      const bool kin_behind = !keyed && !last;
+      L.kin[n] = kin_behind;
+      if (kin_behind) {
+        const qstep q = kin(k + 1);
+        L.kin_pose[n] = q.pose, L.kin_row[n] = lag1 && q.ranked ? q.row : -1;
+        stepped.push_back(q);
+      }
+      L.keys = keyed;
+      ++k, ++n;
+      if (!kin_behind) break;
+    }
+    L.n_sub = n;
+    for (const qstep& q : stepped) enqueue(q);
+    if (L.keys) {
+      L.sort_after = 1;
+      if (!to_rank.empty() || !to_cast.empty()) {
+        L.keys_snap = cb;
+        for (qstep& q : to_rank)
+          if (q.snap < 0) q.snap = cb;
+        for (qstep& q : to_cast)
+          if (q.snap < 0) q.snap = cb;
+        cb = (cb + 1) % C;
+      }
+      stale = true;  // the re-sort moves envs between blocks
+    }
+    if (n > 0 && !L.kin[n - 1] && k < K) kin1_behind(L, k);
+    if (L.n_sub + L.n_rank + L.n_rays == 0) return -3;  // (never: a launch always makes progress)
+    emit(L);
+  }
+  in->ranked = ranked;
+  in->tasks_stale_out = stale || ranked > 0;
+  return n_out;
+}
+
 // rx_steps' carrying schedule (steps_pair) applies to the split step of single-agent envs at
 // one lane per env -- what k_step2_pair is built for -- while nothing records (rx_profile's
 // stamps and the counters are per launch of rx_step's kernels), with no re-sort left pending
@@ -1166,179 +1325,103 @@ static rx_io io_at(const rx_io* io, const rx_io_strides& st, int64_t s) {
 // rx_assign's snapshot rings and shadow obs rows.  Otherwise rx_steps is K x rx_step.
 static bool steps_carried(const rx_env* h, const rx_io* io) {
   if (!RX_STEPS_CARRY || !split_step(h, RX_MODE_STEP) || h->cfg.n_agents != 1 || h->reward_lpe != 1) return false;
-  if (h->prof || io->counters || h->sort_pending || !h->obs_shadow.p) return false;
+  if (h->prof || io->counters || h->sort_pending) return false;
+  const bool ranks = h->cfg.ray_order == 2 && !h->lane_tracks;
   for (int b = 0; b < RX_PAIR_RING; ++b)
-    if (!h->snap_pose[b].p || (h->cfg.ray_order == 2 && !h->lane_tracks && !h->snap_tasks[b].p)) return false;
+    if (!h->snap_pose[b].p) return false;
+  for (int b = 0; b < RX_TASK_RING; ++b)
+    if (ranks && !h->snap_tasks[b].p) return false;
+  for (int b = 0; b < RX_SHADOW_ROWS; ++b)
+    if (!h->obs_shadow[b].p) return false;
   return true;
 }
 
-// K steps with the actions of all of them in device memory (DESIGN.md §3 "The carried step",
-// "The paired launch").  Block b's KIN part of step k + 1 needs only block b's REWARD results
-// of step k, so REWARD workgroup b of a k_step2_pair launch runs it and k_kin1 leaves the
-// step.  KIN k + 1 overwrites what the ray waves of step k read, so every KIN part also
-// stores its pose and its task row to a snapshot and the ray waves read that.  They read
-// nothing else that a later step writes and nothing of a later step reads what they write,
-// so once KIN k's launch has completed they can be cast in ANY later launch of the window.
-// `pend` is the queue of such steps: KIN done, rays not yet cast (never more than two).
-// Every launch casts all of them and its REWARD workgroups advance up to two steps D_k =
-// (REWARD k, KIN k + 1), which refills the queue:
-//   k_kin1(0) [D0 D1 | rays 0] [D2 D3 | rays 1 2] [D4 D5 | rays 3 4] [D6 | rays 5 6]
-//   k_step2(7, keys) sort k_kin1(8) ...
-// A step whose re-sort is due, and the call's last step, has no KIN behind its REWARD: the
-// plain k_step2 when its own rays are all that is pending, else the paired kernel with one
-// KIN-less sub-step (which writes the keys).  So the queue is empty before every sort (the
-// sort moves rows, and the rays name positions) and at the end of the call.  Pose snapshots
-// are a ring of RX_PAIR_RING by the step's index in the call, task rows a ring by the
-// call's sorts (task_sort > 1: the rays read the row last written, which the next sort must
-// not overwrite under them): a launch stores steps k + 1, k + 2 and reads k - 1, k, and a
-// captured call replays with the same buffers.  Two ray steps that would write the same obs
-// rows (stride 0): the older one writes the handle's shadow rows, so the caller's rows end
-// with the newest step's.  Until the call's first sort the rays read the handle's task
-// buffer, which every sort otherwise also writes (it stays the current order for the launches
-// after the call): a sort in a launch whose rays still read it writes the ring row alone, and
-// if no later sort of the call brings the handle's buffer up to date the call leaves it
-// marked stale (it is a valid, older order; the next dynamics launch sorts).  No launch reads
-// the buffer it sorts into (rx_launch_step2_pair refuses one).  The working state stays
-// single-buffered and is current after every launch; the bookkeeping (dyn_calls, task_calls,
-// the re-sort) advances as K x rx_step.
-// RX_STEPS_CROSS (DESIGN.md §3 "The crossing step"): a re-sort step k + 1 that a step follows
-// in the call gives up its own launch.  REWARD k + 1 is the KIN-less second sub-step of D_k's
-// launch, and step k + 1 stays in the queue ACROSS the sort: the next window's first launch
-// casts it as the older ray step, from its ring slots (which the sort leaves alone) and from
-// the snapshots of perm and progress that REWARD k + 1 stored (which the sort rewrites):
-//   sort k_kin1(8) [D8 D9 | rays 7 8] [D10 D11 | rays 9 10] [D12 D13 | rays 11 12]
-//   [D14 R15 | rays 13 14] sort k_kin1(16) [D16 D17 | rays 15 16] ...
-// A re-sort step that is the call's last keeps the order above, so the queue is still empty
-// at the end of the call.
+// K steps with the actions of all of them in device memory: rx_steps_plan's records turned
+// into pointers.  Calls of at least RX_STEPS_DEEP_MIN_K steps take the deep schedule (at depth
+// 4 below RX_STEPS_FULL_MIN_K steps), shorter ones (and every call of an RX_STEPS_RANK_IN_KIN
+// build) the lag-1 schedule at depth 2, which costs two launches fewer per call.  The working state stays single-buffered and is current
+// after every launch; a captured call replays with the same buffers (the rings count from
+// the start of the call); the bookkeeping (dyn_calls, task_calls, the re-sort) advances as
+// K x rx_step.
 static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32_t K, hipStream_t s) {
   const size_t N = (size_t)h->cfg.n_envs;
   rx_kargs a{};
   make_kargs(h, io, RX_MODE_STEP, nullptr, a);
-  int32_t* const tasks_main = a.tasks_out;  // nullptr: this schedule sorts no ray tasks
-  const int32_t* ray_tasks = h->tasks.p;    // the row the last sort wrote: the handle's before the call's first
-  int tb = 0, rc;
-  bool main_behind = false;  // the last sort left the handle's task buffer out
-  struct ray_step {
-    int32_t k;
-    const int32_t* tasks;
-    const int32_t* rows;  // position -> env and the visiting-order hint: the handle's perm and
-    const double* hint;   // progress, or -- a step that crossed a sort -- their snapshots
-  } pend[2];
-  int n_pend = 0;
-  int cb = 0;  // the crossing snapshots' ring, by the call's crossings (as tb)
-  struct kin_out {
-    double* snap;
-    int32_t* tasks_out;
-    int32_t* tasks_snap;
-  };
-  // the KIN part of step k; reads_main: in a launch one of whose ray steps reads the handle's
-  // task buffer.  Step k joins the queue.
-  auto kin_args = [&](int32_t k, bool reads_main) {
-    kin_out o{h->snap_pose[k % RX_PAIR_RING].p, nullptr, nullptr};
-    if (tasks_main && take_task_sort_turn(h)) {
-      main_behind = reads_main;
-      int32_t* const row = h->snap_tasks[tb].p;
-      if (main_behind)
-        o.tasks_out = row;
-      else
-        o.tasks_out = tasks_main, o.tasks_snap = row;
-      ray_tasks = row;
-      tb = (tb + 1) % RX_PAIR_RING;
-    }
-    pend[n_pend++] = ray_step{k, ray_tasks, a.perm, a.st.progress};
-    return o;
-  };
-  auto kin1 = [&](int32_t k) -> int {
-    const kin_out o = kin_args(k, false);
-    a.io = io_at(io, st, k);
-    a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
-    a.snap_x = o.snap, a.snap_y = o.snap + N, a.snap_angle = o.snap + 2 * N;
-    a.tasks_out = o.tasks_out, a.tasks_snap = o.tasks_snap;
-    const int e = rx_launch_split(&a, 1, RX_SPLIT_KIN, s);
-    return e ? fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)e)) : RX_OK;
-  };
-  // the pending ray steps into p (emptying the queue); do they read the handle's task buffer?
-  auto take_rays = [&](rx_pair& p) {
-    bool reads_main = false;
-    p.n_rays = n_pend;
-    for (int r = 0; r < n_pend; ++r) {
-      p.ray_pose[r] = h->snap_pose[pend[r].k % RX_PAIR_RING].p;
-      p.ray_tasks[r] = pend[r].tasks;
-      p.ray_obs[r] = io_at(io, st, pend[r].k).obs;
-      p.ray_rows[r] = pend[r].rows;
-      p.ray_hint[r] = pend[r].hint;
-      reads_main = reads_main || (tasks_main && pend[r].tasks == tasks_main);
-    }
-    if (n_pend == 2 && p.ray_obs[0] == p.ray_obs[1]) p.ray_obs[0] = h->obs_shadow.p;
-    n_pend = 0;
-    return reads_main;
-  };
-  auto pair = [&](const rx_pair& p) -> int {
-    const int e = rx_launch_step2_pair(&a, &p, s);
-    return e ? fail(RX_EHIP, "k_step2_pair launch failed: %s", hipGetErrorString((hipError_t)e)) : RX_OK;
-  };
-  if ((rc = kin1(0)) != 0) return rc;
-  for (int32_t k = 0; k < K;) {
-    const bool resort = resort_due(h, 0);
-    rx_pair p{};
-    p.n_envs = (int64_t)N;
-    a.io = p.io[0] = io_at(io, st, k);
+  const bool ranks = a.tasks_out != nullptr;  // else this schedule sorts no ray tasks
+  const int32_t* const tasks_main = h->tasks.p;
+  const bool cross = RX_STEPS_CROSS && resort_on(h) && h->snap_rows[RX_CROSS_RING - 1].p &&
+                     h->snap_hint[RX_CROSS_RING - 1].p;
+  const int32_t si = resort_on(h) ? h->cfg.sort_interval : 0;
+  rx_plan_args pa{K, 0, si, si ? (int32_t)(h->dyn_calls % (uint64_t)si) : 0,
+                  ranks ? h->task_sort : 0, ranks ? (int32_t)(h->task_calls % (uint64_t)h->task_sort) : 0,
+                  h->tasks_stale ? 1 : 0, cross ? 1 : 0, -1, 0, 0};  // depth and lag: the planner's choice for K
+  std::vector<rx_plan_launch> plan((size_t)3 * K + 8);  // (at most two launches a step and the drains)
+  const int32_t n_launch = rx_steps_plan(&pa, plan.data(), (int32_t)plan.size());
+  if (n_launch < 0 || (size_t)n_launch > plan.size()) return fail(RX_ESTATE, "rx_steps: no schedule (%d)", n_launch);
+  auto pose = [&](int32_t slot) { return h->snap_pose[slot].p; };
+  auto row = [&](int32_t slot) { return slot < 0 ? nullptr : h->snap_tasks[slot].p; };
+  int rc;
+  for (int32_t i = 0; i < n_launch; ++i) {
+    const rx_plan_launch& L = plan[i];
     a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
     a.snap_x = a.snap_y = a.snap_angle = nullptr;
     a.tasks_out = nullptr, a.tasks_snap = nullptr;
     a.rows_snap = nullptr, a.hint_snap = nullptr;
-    if (!resort && k + 1 < K) {  // D_k, and D_k+1 unless step k + 1 has no KIN behind it
-      const int32_t d = (k + 2 < K && !resort_due(h, 1)) ? 2 : 1;
-      // Step k + 1 is due for the re-sort and a step follows it in the call: it CROSSES the
-      // sort.  Its REWARD runs here as the second sub-step, without a KIN (it writes the keys
-      // and the snapshots), and its rays stay pending across the sort.  Its task row must then
-      // be a row of the ring: the k_kin1 after the sort rewrites the handle's buffer.  Where it
-      // would be the handle's (a call that begins between two task sorts and has not sorted
-      // yet), the window does not cross and step k + 1 keeps its own launch.
-      const bool cross = RX_STEPS_CROSS && k + 2 < K && resort_due(h, 1) && h->snap_rows[cb].p &&
-                         h->snap_hint[cb].p && (!tasks_main || ray_tasks != tasks_main || task_sort_due(h));
-      const bool reads_main = take_rays(p);
-      p.n_sub = cross ? 2 : d;
-      for (int32_t j = 0; j < d; ++j) {
-        const kin_out o = kin_args(k + j + 1, reads_main);
-        p.io[j + 1] = io_at(io, st, k + j + 1);
-        p.kin[j] = 1;
-        p.snap[j] = o.snap, p.tasks_out[j] = o.tasks_out, p.tasks_snap[j] = o.tasks_snap;
+    if (L.n_sub + L.n_rank + L.n_rays > 0) {
+      rx_pair p{};
+      p.n_envs = (int64_t)N;
+      p.n_sub = L.n_sub, p.n_rank = L.n_rank, p.n_rays = L.n_rays;
+      a.io = p.io[0] = io_at(io, st, L.n_sub ? L.first_step : K - 1);
+      for (int32_t j = 0; j < L.n_sub; ++j) {
+        p.kin[j] = L.kin[j];
+        if (!L.kin[j]) continue;
+        p.io[j + 1] = io_at(io, st, L.first_step + j + 1);
+        p.snap[j] = pose(L.kin_pose[j]);
+        p.tasks_out[j] = row(L.kin_row[j]);
       }
-      if (cross) {
+      for (int32_t t = 0; t < L.n_rank; ++t) p.rank_pose[t] = pose(L.rank_pose[t]), p.rank_row[t] = row(L.rank_row[t]);
+      for (int32_t r = 0; r < L.n_rays; ++r) {
+        p.ray_pose[r] = pose(L.ray_pose[r]);
+        p.ray_tasks[r] = L.ray_row[r] < 0 ? tasks_main : row(L.ray_row[r]);
+        p.ray_rows[r] = L.ray_snap[r] < 0 ? a.perm : h->snap_rows[L.ray_snap[r]].p;
+        p.ray_hint[r] = L.ray_snap[r] < 0 ? a.st.progress : h->snap_hint[L.ray_snap[r]].p;
+        p.ray_obs[r] = io_at(io, st, L.ray_step[r]).obs;
+      }
+      // ray steps that would write the same obs rows (stride 0): all but the newest write shadow
+      // rows of their own, so the caller's rows end with the newest step's
+      for (int32_t r = 0; r + 1 < L.n_rays; ++r)
+        if (p.ray_obs[r] == p.ray_obs[L.n_rays - 1]) p.ray_obs[r] = h->obs_shadow[L.ray_shadow[r]].p;
+      if (L.keys) {
         if ((rc = arm_sort_keys(h, a, true, s)) != 0) return rc;
-        a.rows_snap = h->snap_rows[cb].p;
-        a.hint_snap = h->snap_hint[cb].p;
+        if (L.keys_snap >= 0) a.rows_snap = h->snap_rows[L.keys_snap].p, a.hint_snap = h->snap_hint[L.keys_snap].p;
       }
-      if ((rc = pair(p)) != 0) return rc;
-      if (resort_on(h)) h->dyn_calls += (uint64_t)p.n_sub;
-      k += p.n_sub;
-      if (cross) {  // the queue holds step k - 1 alone: from here on it reads the snapshots
-        pend[0].rows = a.rows_snap, pend[0].hint = a.hint_snap;
-        cb = (cb + 1) % RX_CROSS_RING;
-        if ((rc = sort_envs_now(h, s)) != 0 || (rc = kin1(k)) != 0) return rc;
+      if (L.n_sub == 1 && !L.kin[0] && L.n_rank == 0 && L.n_rays == 1 && L.ray_step[0] == L.first_step &&
+          L.ray_snap[0] < 0) {  // a KIN-less REWARD beside its own rays: the plain k_step2
+        rx_kargs a2 = a;
+        a2.ray_x = p.ray_pose[0], a2.ray_y = a2.ray_x + N, a2.ray_angle = a2.ray_x + 2 * N;
+        a2.tasks = p.ray_tasks[0];
+        if ((rc = rx_launch_split(&a2, 1, RX_SPLIT_REWARD_RAYS, s)) != 0)
+          return fail(RX_EHIP, "k_step2 launch failed: %s", hipGetErrorString((hipError_t)rc));
+      } else if ((rc = rx_launch_step2_pair(&a, &p, s)) != 0) {
+        return fail(RX_EHIP, "k_step2_pair launch failed: %s", hipGetErrorString((hipError_t)rc));
       }
-      continue;
     }
-    if (resort_on(h)) ++h->dyn_calls;
-    if (resort && (rc = arm_sort_keys(h, a, true, s)) != 0) return rc;
-    if (n_pend == 1 && pend[0].rows == a.perm) {  // only its own rays are pending: the plain k_step2
-      a.ray_x = h->snap_pose[pend[0].k % RX_PAIR_RING].p;
-      a.ray_y = a.ray_x + N;
-      a.ray_angle = a.ray_x + 2 * N;
-      a.tasks = pend[0].tasks;
-      n_pend = 0;
-      if ((rc = rx_launch_split(&a, 1, RX_SPLIT_REWARD_RAYS, s)) != 0)
-        return fail(RX_EHIP, "k_step2 launch failed: %s", hipGetErrorString((hipError_t)rc));
-    } else {
-      take_rays(p);
-      p.n_sub = 1;
-      if ((rc = pair(p)) != 0) return rc;
+    if (L.sort_after && (rc = sort_envs_now(h, s)) != 0) return rc;
+    if (L.kin1_after >= 0) {
+      a.io = io_at(io, st, L.kin1_after);
+      a.sort_keys = nullptr, a.sort_hist = nullptr, a.sort_off = nullptr;
+      a.rows_snap = nullptr, a.hint_snap = nullptr;
+      a.snap_x = pose(L.kin1_pose), a.snap_y = a.snap_x + N, a.snap_angle = a.snap_x + 2 * N;
+      a.tasks_out = row(L.kin1_row), a.tasks_snap = nullptr;
+      if ((rc = rx_launch_split(&a, 1, RX_SPLIT_KIN, s)) != 0)
+        return fail(RX_EHIP, "k_kin1 launch failed: %s", hipGetErrorString((hipError_t)rc));
     }
-    if (resort && (rc = sort_envs_now(h, s)) != 0) return rc;
-    if (++k < K && (rc = kin1(k)) != 0) return rc;
   }
-  if (main_behind) h->tasks_stale = true;
+  if (resort_on(h)) h->dyn_calls += (uint64_t)K;
+  if (ranks) {
+    h->task_calls += (uint64_t)K;
+    h->tasks_stale = pa.tasks_stale_out != 0;
+  }
   return RX_OK;
 }
 

@@ -220,45 +220,90 @@ struct rx_kargs {
 // leaves the step; a launch advances up to two steps that way (REWARD k, KIN k + 1, REWARD
 // k + 1, KIN k + 2) and its ray workgroups cast the rays of up to two EARLIER-stepped steps,
 // whose KIN parts completed in a previous launch -- half the launch boundaries, half the
-// drains.  0 = a k_kin1 and a k_step2 launch per step.
+// drains (the lag-1 schedule; the deep launch below takes this to RX_STEPS_DEPTH steps).
+// 0 = a k_kin1 and a k_step2 launch per step.
 #ifndef RX_STEPS_CARRY
 #define RX_STEPS_CARRY 1
 #endif
 #ifdef RX_STEPS_PAIR
 #error "RX_STEPS_PAIR is retired: the paired launches are the one carrying schedule; RX_STEPS_CARRY=0 selects a k_kin1 and a k_step2 launch per step"
 #endif
-#define RX_PAIR_RING 4  // pose / task-row snapshots: a launch writes at most two and reads at most two others
+// The deep launch (DESIGN.md §3 "The deep launch"): a k_step2_pair launch advances up to
+// RX_STEPS_DEPTH steps in its REWARD workgroups, ranks the ray tasks of up to as many steps in
+// RANK workgroups of its own (off the REWARD+KIN chain) and casts up to as many steps' rays.
+// A step's KIN, its ranking and its rays run in three different launches, in that order.
+// Same-session A/B at 65,536 envs, 1,000-step calls (profiles/steps_deep/): depth 2 / 4 / 8 =
+// 1,257 / 1,373 / 1,403 M env-steps/s against the parent's 1,192 M.
+#ifndef RX_STEPS_DEPTH
+#define RX_STEPS_DEPTH 8
+#endif
+#if RX_STEPS_DEPTH < 2 || RX_STEPS_DEPTH > 8
+#error "RX_STEPS_DEPTH must be 2 .. 8"
+#endif
+// 1 = the ranking stays in the KIN parts and every call takes the lag-1 schedule of two
+// sub-steps and two ray steps per launch (what calls shorter than RX_STEPS_DEEP_MIN_K take)
+#ifndef RX_STEPS_RANK_IN_KIN
+#define RX_STEPS_RANK_IN_KIN 0
+#endif
+// rx_steps calls of fewer steps take the lag-1 schedule: the deep one pays two more launches
+// per call (a prologue that casts nothing and a drain that only casts).  20 is the smallest
+// measured call length at which the deep schedule is not slower (5 / 10 steps: lag 1 ahead by
+// 11 % / 3 %; 20 / 40 steps: depth 4 ahead by 2.5 % / 5 %; profiles/steps_deep/).
+#ifndef RX_STEPS_DEEP_MIN_K
+#define RX_STEPS_DEEP_MIN_K 20
+#endif
+// ... and deep calls of fewer steps than this are planned at depth 4: a deeper launch fills and
+// drains longer (20 / 40 steps: depth 4 ahead of depth 8 by 7 % / 1.5 %; 100 / 250 / 1,000
+// steps: depth 8 ahead by 1.5 % / 1 % / 2.3 %)
+#ifndef RX_STEPS_FULL_MIN_K
+#define RX_STEPS_FULL_MIN_K 100
+#endif
+// Rings of the snapshots, by the step's index in the call (pose), by the call's rankings
+// (task rows) and by the call's re-sorts (row ids / hint).  In one launch: poses of the steps
+// it advances, of those it ranks and of those it casts; the rows it ranks, the rows it casts
+// from and the row of the last ranked step before them; the snapshots of the windows of the
+// steps it casts (KIN two launches back) and the one its key-writing REWARD stores.
+#define RX_PAIR_RING (3 * RX_STEPS_DEPTH)
+#define RX_TASK_RING (2 * RX_STEPS_DEPTH + 1)
+#define RX_SHADOW_ROWS (RX_STEPS_DEPTH - 1)
 
 // The paired schedule's crossing step (DESIGN.md §3 "The crossing step"): the REWARD of a step
-// whose re-sort is due runs as the second sub-step of the launch before it, KIN-less, and its
-// rays are cast AFTER the sort, in the next window's first launch, from pre-sort snapshots of
-// the row ids and the visiting-order hint -- the re-sort step's own launch leaves the window.
+// whose re-sort is due runs as the last sub-step of the launch before it, KIN-less, and its
+// rays are cast AFTER the sort, from pre-sort snapshots of the row ids and the visiting-order
+// hint -- the re-sort step's own launch leaves the window.  In the deep schedule every step
+// still queued at a sort crosses it on that window's snapshots.
 // 0 = the re-sort step keeps its own launch (REWARD and rays before the sort).
 #ifndef RX_STEPS_CROSS
 #define RX_STEPS_CROSS 1
 #endif
-#define RX_CROSS_RING 2  // row-id / hint snapshots: a launch stores one and may read the other
+#define RX_CROSS_RING 3
 
 // What one k_step2_pair launch runs beside rx_kargs (whose io, ray_*, snap_*, tasks,
 // tasks_out and tasks_snap it ignores).
 struct rx_pair {
-  int32_t n_sub;   // REWARD sub-steps of the launch (1 or 2); the sort keys go with the last one
-  int32_t n_rays;  // ray steps of the launch (1 or 2), oldest first
+  int32_t n_sub;   // REWARD sub-steps of the launch (0 .. RX_STEPS_DEPTH); the sort keys go with the last one
+  int32_t n_rays;  // ray steps of the launch (0 .. RX_STEPS_DEPTH), oldest first
   // sub-step j: REWARD on io[j]'s rows, then -- with kin[j] -- KIN on io[j + 1]'s
-  rx_io io[3];
-  int32_t kin[2];
-  double* snap[2];         // KIN j's pose snapshot: x, y at + N, angle at + 2 N
-  int32_t* tasks_out[2];   // KIN j's ray-task sort (nullptr = not this step), and its second copy
-  int32_t* tasks_snap[2];
-  // ray step s: the pose snapshot and the task row its KIN stored, and the obs rows it writes
-  const double* ray_pose[2];
-  const int32_t* ray_tasks[2];
-  float* ray_obs[2];
+  rx_io io[RX_STEPS_DEPTH + 1];
+  int32_t kin[RX_STEPS_DEPTH];
+  double* snap[RX_STEPS_DEPTH];         // KIN j's pose snapshot: x, y at + N, angle at + 2 N
+  int32_t* tasks_out[RX_STEPS_DEPTH];   // KIN j's ray-task sort (nullptr = not in the chain), and its second copy
+  int32_t* tasks_snap[RX_STEPS_DEPTH];
+  // ray step s: the pose snapshot its KIN stored, its task row, and the obs rows it writes
+  const double* ray_pose[RX_STEPS_DEPTH];
+  const int32_t* ray_tasks[RX_STEPS_DEPTH];
+  float* ray_obs[RX_STEPS_DEPTH];
   // ... and its row ids (position -> env: the obs row) and visiting-order hint: rx_kargs' perm
-  // and st.progress, or -- a crossing step, cast after the re-sort -- their pre-sort snapshots
-  const int32_t* ray_rows[2];
-  const double* ray_hint[2];
+  // and st.progress, or -- a step that crossed a re-sort -- their pre-sort snapshots
+  const int32_t* ray_rows[RX_STEPS_DEPTH];
+  const double* ray_hint[RX_STEPS_DEPTH];
   int64_t n_envs;
+  // rank step t: RANK workgroup (t, b) ranks block b's ray tasks by the angles of the pose
+  // snapshot rank_pose[t] (stored by the step's KIN in an EARLIER launch) into rank_row[t],
+  // which a LATER launch's ray waves read
+  int32_t n_rank;  // 0 .. RX_STEPS_DEPTH
+  const double* rank_pose[RX_STEPS_DEPTH];
+  int32_t* rank_row[RX_STEPS_DEPTH];
 };
 
 extern "C" int rx_launch_step(const rx_kargs* a, int n_agents, int phases, hipStream_t s);

@@ -2277,29 +2277,39 @@ __global__ __launch_bounds__(64, A == 1 ? (LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW
 // earlier steps, the older one first: ray workgroup r is record r % n_ray_waves of step r /
 // n_ray_waves, on that step's pose snapshot, task row, obs rows, row ids and hint.  Their KIN
 // parts ran in an EARLIER launch, so no wave of this launch waits on another.  A step whose
-// re-sort is due can be the second sub-step without a KIN (it writes the keys, and the row-id
+// re-sort is due can be the last sub-step without a KIN (it writes the keys, and the row-id
 // and hint snapshots its rays are cast from after the sort; DESIGN.md §3 "The crossing step").
 // Scheduling knobs, same-session A/B at 65,536 envs (profiles/steps_pair/): issue priority of
 // the REWARD workgroups 0 / 1 / 2 / 3 = 998 / 1,047 / 1,045 / 1,045 M env-steps/s (parent
-// 1,012 M); the two steps' ray records interleaved in octets 1,080 M against 1,085 M for the
-// older step's records first.
+// 1,012 M); two steps' ray records interleaved in octets 1,080 M against 1,085 M for the
+// older step's records first (the interleaved order is gone with the deep launch).
 #ifndef RX_PAIR_PRIO
 #define RX_PAIR_PRIO 1
 #endif
-#ifndef RX_PAIR_INTERLEAVE
-#define RX_PAIR_INTERLEAVE 0
+// The deep launch (DESIGN.md §3 "The deep launch"): up to RX_STEPS_DEPTH sub-steps and ray
+// steps, and a third class of one-wave workgroups, RANK: workgroup (t, b) ranks block b's ray
+// tasks of rank step t -- sort_block_tasks<1>, as a KIN part would, on the angles of the pose
+// snapshot that the step's KIN stored in an earlier launch -- into a row of the task ring that
+// a later launch's ray waves read.  The ranking is then no link of the REWARD+KIN chain (KIN
+// parts of this schedule get no task target).  RANK workgroups keep issue priority 0.  They
+// come last in the grid (RX_RANK_FIRST 0), which leaves the ray workgroups' indices and XCD
+// placement as they were and puts the ranking into the launch's drain; RX_RANK_FIRST 1 puts
+// them between the REWARD and the ray workgroups (n_rw is a multiple of 8: the placement
+// holds there too).  Same-session A/B: profiles/steps_deep/README.md.
+#ifndef RX_RANK_FIRST
+#define RX_RANK_FIRST 0
 #endif
-__device__ __forceinline__ rx_io pair_io(const rx_io& x, const rx_io& y, bool second) {
+__device__ __forceinline__ rx_io pair_io(const rx_io& x, const rx_io& y) {
   rx_io o = x;  // ep_stats and counters are the call's, not the step's
-  o.actions = second ? y.actions : x.actions;
-  o.obs = second ? y.obs : x.obs;
-  o.reward = second ? y.reward : x.reward;
-  o.reward64 = second ? y.reward64 : x.reward64;
-  o.terminated = second ? y.terminated : x.terminated;
-  o.truncated = second ? y.truncated : x.truncated;
-  o.done_f32 = second ? y.done_f32 : x.done_f32;
-  o.info = second ? y.info : x.info;
-  o.ep_done = second ? y.ep_done : x.ep_done;
+  o.actions = y.actions;
+  o.obs = y.obs;
+  o.reward = y.reward;
+  o.reward64 = y.reward64;
+  o.terminated = y.terminated;
+  o.truncated = y.truncated;
+  o.done_f32 = y.done_f32;
+  o.info = y.info;
+  o.ep_done = y.ep_done;
   return o;
 }
 
@@ -2336,24 +2346,23 @@ __device__ __forceinline__ void step2_pair_body(const rx_pair_args& ka) {
       __asm__ volatile("" : "+s"(kp), "+s"(bj));
       const rx_pair_args& k = *(const rx_pair_args*)kp;
       const rx_pair& pp = k.p;
-      const bool second = j != 0;
       rx_kargs an = k.a;
-      an.io = pair_io(pp.io[0], pp.io[1], second);
+      an.io = pair_io(pp.io[0], pp.io[j]);
       if (j + 1 < n_sub) an.sort_keys = nullptr;  // the keys are the launch's last REWARD's
       an.snap_x = nullptr, an.tasks_out = nullptr, an.tasks_snap = nullptr;
       double ang[1], ep[3] = {0.0, 0.0, 0.0};
       int e = -1;
       dyn1_env<1, RX_PART_REWARD, LV>(an, bj, ang, e, ep);
       add_episode_stats(an, ep);
-      const bool kin = (second ? pp.kin[1] : pp.kin[0]) != 0;
+      const bool kin = pp.kin[j] != 0;
       if (kin && bj < an.n_dyn_waves) {  // (n_rw pads the REWARD workgroups to a multiple of 8)
-        an.io = pair_io(pp.io[1], pp.io[2], second);
+        an.io = pair_io(pp.io[0], pp.io[j + 1]);
         an.sort_keys = nullptr;
-        an.snap_x = second ? pp.snap[1] : pp.snap[0];
+        an.snap_x = pp.snap[j];
         an.snap_y = an.snap_x + pp.n_envs;
         an.snap_angle = an.snap_x + 2 * pp.n_envs;
-        an.tasks_out = second ? pp.tasks_out[1] : pp.tasks_out[0];
-        an.tasks_snap = second ? pp.tasks_snap[1] : pp.tasks_snap[0];
+        an.tasks_out = pp.tasks_out[j];
+        an.tasks_snap = pp.tasks_snap[j];
         const bool sorting = an.tasks_out != nullptr;
         if (sorting) cnt[threadIdx.x & 63] = 0;
         double ang1[1], ep1[3];
@@ -2362,28 +2371,53 @@ __device__ __forceinline__ void step2_pair_body(const rx_pair_args& ka) {
         if (sorting) sort_block_tasks<1>(an, uniform(an.dyn_waves[bj].perm_start), p1, ang1, cnt, stage);
       }
     }
-  } else {
-    const rx_kargs& a = ka.a;
-    const rx_pair& pp = ka.p;
-    const int r = b - ka.n_rw;
-#if RX_PAIR_INTERLEAVE
-    // the two steps' records interleaved in octets (an octet keeps its XCDs): record-major
-    const bool newer = pp.n_rays == 2 && ((r >> 3) & 1);
-    const int rec = pp.n_rays == 2 ? (((r >> 4) << 3) | (r & 7)) : r;
-#else
-    const bool newer = r >= a.n_ray_waves;  // (n_rays <= 2): the older step's records first
-    const int rec = newer ? r - a.n_ray_waves : r;
-#endif
-    rx_kargs ar = a;
-    ar.ray_x = newer ? pp.ray_pose[1] : pp.ray_pose[0];
-    ar.ray_y = ar.ray_x + pp.n_envs;
-    ar.ray_angle = ar.ray_x + 2 * pp.n_envs;
-    ar.tasks = newer ? pp.ray_tasks[1] : pp.ray_tasks[0];
-    ar.io.obs = newer ? pp.ray_obs[1] : pp.ray_obs[0];
-    ar.perm = newer ? pp.ray_rows[1] : pp.ray_rows[0];  // a crossing step: the pre-sort snapshots
-    ar.ray_hint = newer ? pp.ray_hint[1] : pp.ray_hint[0];
-    rays_dispatch<1, LPR, LV, LPR == 4>(ar, rec);
+    return;
   }
+  typedef const __attribute__((address_space(4))) rx_pair_args* rx_kap;
+  const rx_pair_args& k = *(const rx_pair_args*)(rx_kap)__builtin_amdgcn_kernarg_segment_ptr();  // indexed reads
+  const rx_kargs& a = ka.a;
+  const rx_pair& pp = k.p;
+  const int n_cast = uniform(ka.p.n_rays) * a.n_ray_waves;
+#if RX_RANK_FIRST
+  const int n_rankw = uniform(ka.p.n_rank) * ka.n_rw;
+  const int r = b - ka.n_rw - n_rankw, q = b - ka.n_rw;
+  const bool rank = q < n_rankw;
+#else
+  const int r = b - ka.n_rw, q = r - n_cast;
+  const bool rank = q >= 0;
+#endif
+  if (rank) {
+    // RANK workgroup (t, bb): block bb's 64 positions, their angles from rank step t's pose
+    // snapshot.  After a re-sort the snapshot is in the PRE-sort order, as the rows and the hint
+    // its ray waves will read; the blocks' position ranges (dyn_waves) do not change.
+    const int t = q / ka.n_rw, bb = q - t * ka.n_rw;
+    if (t >= pp.n_rank || bb >= a.n_dyn_waves) return;
+    extern __shared__ int32_t task_lds[];
+    int32_t* cnt = task_lds;
+    int32_t* stage = cnt + kTaskSectors;
+    const int lane = threadIdx.x & 63;
+    cnt[lane] = 0;
+    const int start = uniform(a.dyn_waves[bb].perm_start), count = uniform(a.dyn_waves[bb].count);
+    const int p = lane < count ? start + lane : -1;
+    double ang[1] = {p >= 0 ? ldc(pp.rank_pose[t] + 2 * pp.n_envs + p) : 0.0};
+    rx_kargs ar = a;
+    ar.tasks_out = pp.rank_row[t];
+    ar.tasks_snap = nullptr;
+    sort_block_tasks<1>(ar, start, p, ang, cnt, stage);
+    return;
+  }
+  if (r >= n_cast) return;
+  // ray workgroup r: record r % n_ray_waves of ray step r / n_ray_waves, the oldest step first
+  const int rs = r / a.n_ray_waves, rec = r - rs * a.n_ray_waves;
+  rx_kargs ar = a;
+  ar.ray_x = pp.ray_pose[rs];
+  ar.ray_y = ar.ray_x + pp.n_envs;
+  ar.ray_angle = ar.ray_x + 2 * pp.n_envs;
+  ar.tasks = pp.ray_tasks[rs];
+  ar.io.obs = pp.ray_obs[rs];
+  ar.perm = pp.ray_rows[rs];  // a step that crossed a re-sort: the pre-sort snapshots
+  ar.ray_hint = pp.ray_hint[rs];
+  rays_dispatch<1, LPR, LV, LPR == 4>(ar, rec);
 }
 
 template <int LPR, bool LV = false>
@@ -2804,15 +2838,19 @@ extern "C" int rx_launch_split(const rx_kargs* a, int n_agents, int part, hipStr
   return (int)hipGetLastError();
 }
 
-// The paired k_step2: n_rw REWARD workgroups, then n_rays copies of the ray table (n_ray_waves
-// is a multiple of 8, so both copies keep the group -> XCD placement).  Every workgroup of the
+// The paired k_step2: n_rw REWARD workgroups (idle when n_sub is 0), then n_rays copies of the
+// ray table (n_ray_waves is a multiple of 8, so every copy keeps the group -> XCD placement),
+// then n_rank x n_rw RANK workgroups.  Any of the three counts may be 0 (a prologue launch casts
+// nothing, a drain launch advances nothing), not all of them.  Every workgroup of the
 // launch gets the KIN part's sort LDS (the ray workgroups leave it unused), so the staging row
 // is sized for the handle's sensors, not for the 16 the sort allows: 64 + 64 R words (3 KiB at
 // 11 sensors; 32 workgroups a CU keep k_step2's 8 waves per SIMD within the CU's LDS up to 16
 // sensors, 4.25 KiB).  Checked here, on the host: no KIN part of the launch stores a pose
 // snapshot or sorts a task row that one of the launch's ray steps reads, two ray steps never
 // write the same obs rows, and no ray step reads a row-id or hint snapshot that the launch's
-// key-writing REWARD stores (those are its OWN step's, cast by a later launch).
+// key-writing REWARD stores (those are its OWN step's, cast by a later launch); no KIN part
+// stores the pose snapshot a RANK class reads, and no RANK class writes a row that a ray step
+// of the launch reads or that another RANK class writes.
 // rx_pair_layout: sizes and offsets for a caller that fills the two structs as bytes (the
 // refusal test): 0 / 1-3 = sizeof rx_kargs / its sort_keys, rows_snap, hint_snap; 4 / 5-9 =
 // sizeof rx_pair / its n_sub, n_rays, ray_obs, ray_rows, ray_hint; else -1.
@@ -2821,33 +2859,60 @@ extern "C" int64_t rx_pair_layout(int what) {
                         offsetof(rx_kargs, hint_snap), sizeof(rx_pair),            offsetof(rx_pair, n_sub),
                         offsetof(rx_pair, n_rays),  offsetof(rx_pair, ray_obs),    offsetof(rx_pair, ray_rows),
                         offsetof(rx_pair, ray_hint)};
-  return what >= 0 && what < 10 ? (int64_t)v[what] : -1;
+  if (what >= 0 && what < 10) return (int64_t)v[what];
+  // 11 = RX_STEPS_DEPTH (the arrays' length); 12-20 = rx_pair's kin, snap, tasks_out, tasks_snap,
+  // ray_pose, ray_tasks, n_rank, rank_pose, rank_row (10 stays -1: the end of the first table)
+  const size_t w[10] = {RX_STEPS_DEPTH,
+                        offsetof(rx_pair, kin),
+                        offsetof(rx_pair, snap),
+                        offsetof(rx_pair, tasks_out),
+                        offsetof(rx_pair, tasks_snap),
+                        offsetof(rx_pair, ray_pose),
+                        offsetof(rx_pair, ray_tasks),
+                        offsetof(rx_pair, n_rank),
+                        offsetof(rx_pair, rank_pose),
+                        offsetof(rx_pair, rank_row)};
+  return what >= 11 && what < 21 ? (int64_t)w[what - 11] : -1;
 }
 
 extern "C" int rx_launch_step2_pair(const rx_kargs* a, const rx_pair* p, hipStream_t s) {
-  if (p->n_sub < 1 || p->n_sub > 2 || p->n_rays < 1 || p->n_rays > 2) return (int)hipErrorInvalidValue;
-  if (p->n_rays == 2 && p->ray_obs[0] == p->ray_obs[1]) return (int)hipErrorInvalidValue;
+  constexpr int D = RX_STEPS_DEPTH;
+  const int bad = (int)hipErrorInvalidValue;
+  if (p->n_sub < 0 || p->n_sub > D || p->n_rays < 0 || p->n_rays > D || p->n_rank < 0 || p->n_rank > D) return bad;
+  if (p->n_sub + p->n_rays + p->n_rank == 0) return bad;
   for (int r = 0; r < p->n_rays; ++r) {
-    if (!p->ray_rows[r] || !p->ray_hint[r]) return (int)hipErrorInvalidValue;
+    for (int q = 0; q < r; ++q)
+      if (p->ray_obs[q] == p->ray_obs[r]) return bad;
+    if (!p->ray_rows[r] || !p->ray_hint[r]) return bad;
     // the key-writing REWARD stores the snapshots of ITS step, whose rays a later launch casts
-    if (a->sort_keys && a->rows_snap && (p->ray_rows[r] == a->rows_snap || p->ray_hint[r] == a->hint_snap))
-      return (int)hipErrorInvalidValue;
+    if (p->n_sub && a->sort_keys && a->rows_snap && (p->ray_rows[r] == a->rows_snap || p->ray_hint[r] == a->hint_snap))
+      return bad;
   }
-  if (a->sort_keys && a->rows_snap && !a->hint_snap) return (int)hipErrorInvalidValue;
-  bool sorting = false;
+  if (a->sort_keys && a->rows_snap && !a->hint_snap) return bad;
+  bool sorting = p->n_rank > 0;
   for (int j = 0; j < p->n_sub; ++j) {
-    if (!p->kin[j]) continue;
-    if (j + 1 == p->n_sub && a->sort_keys) return (int)hipErrorInvalidValue;  // the sort comes before the next KIN
+    if (!p->kin[j]) {
+      if (j + 1 < p->n_sub) return bad;  // REWARD k + 1 needs KIN k + 1
+      continue;
+    }
+    if (j + 1 == p->n_sub && a->sort_keys) return bad;  // the sort comes before the next KIN
     sorting = sorting || p->tasks_out[j];
     for (int r = 0; r < p->n_rays; ++r) {
-      if (p->snap[j] == p->ray_pose[r]) return (int)hipErrorInvalidValue;
-      if (p->tasks_out[j] && (p->tasks_out[j] == p->ray_tasks[r] || p->tasks_snap[j] == p->ray_tasks[r]))
-        return (int)hipErrorInvalidValue;
+      if (p->snap[j] == p->ray_pose[r]) return bad;
+      if (p->tasks_out[j] && (p->tasks_out[j] == p->ray_tasks[r] || p->tasks_snap[j] == p->ray_tasks[r])) return bad;
     }
+    for (int t = 0; t < p->n_rank; ++t)  // a rank step's KIN ran in an earlier launch
+      if (p->snap[j] == p->rank_pose[t]) return bad;
   }
-  if (p->n_sub == 2 && !p->kin[0]) return (int)hipErrorInvalidValue;  // REWARD k + 1 needs KIN k + 1
+  for (int t = 0; t < p->n_rank; ++t) {
+    if (!p->rank_pose[t] || !p->rank_row[t]) return bad;
+    for (int r = 0; r < p->n_rays; ++r)  // a ranked row is read by a LATER launch
+      if (p->rank_row[t] == p->ray_tasks[r]) return bad;
+    for (int q = 0; q < t; ++q)
+      if (p->rank_row[q] == p->rank_row[t]) return bad;
+  }
   const int n_rw = (a->n_dyn_waves + 7) / 8 * 8;
-  const dim3 grid(n_rw + p->n_rays * a->n_ray_waves);
+  const dim3 grid(n_rw + p->n_rays * a->n_ray_waves + p->n_rank * n_rw);
   const size_t lds = sorting ? (size_t)(kTaskSectors + 64 * a->n_sensors) * sizeof(int32_t) : 0;
   const rx_pair_args ka{*a, *p, n_rw};
   if (a->lane_tracks)

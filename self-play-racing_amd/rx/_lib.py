@@ -44,7 +44,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_track_evolve_plan_host", "rx_track_evolve", "rx_track_evolve_host", "rx_track_episode",
            "rx_track_episode_host", "rx_track_episode_step", "rx_track_episodic_rollout_steps",
            "rx_track_learn_tally_slots", "rx_track_learn_tally_slots_host", "rx_track_learn_episode",
-           "rx_track_learn_episode_host", "rx_track_learn_episode_step", "rx_track_learn_episodic_rollout_steps")
+           "rx_track_learn_episode_host", "rx_track_learn_episode_step", "rx_track_learn_episodic_rollout_steps",
+           "rx_steps_plan")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -95,6 +96,50 @@ STRIDE_FIELDS = ("actions", "obs", "reward", "reward64", "terminated", "truncate
 
 class RxIOStrides(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in STRIDE_FIELDS]
+
+
+# rx_steps_plan (additive to ABI v25): the launch schedule of an rx_steps call, host only
+RX_PLAN_MAX_DEPTH, RX_PLAN_CROSS_RING = 8, 3
+PLAN_ARG_FIELDS = ("n_steps", "depth", "sort_interval", "dyn_calls", "task_sort", "task_calls", "tasks_stale", "cross",
+                   "rank_in_kin", "ranked", "tasks_stale_out")
+_PLAN_ROW = ctypes.c_int32 * RX_PLAN_MAX_DEPTH
+
+
+class RxPlanArgs(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in PLAN_ARG_FIELDS]
+
+
+class RxPlanLaunch(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_sub", "n_rank", "n_rays", "first_step")] + \
+               [(k, _PLAN_ROW) for k in ("kin", "kin_pose", "kin_row")] + \
+               [(k, ctypes.c_int32) for k in ("keys", "keys_snap")] + \
+               [(k, _PLAN_ROW) for k in ("rank_step", "rank_pose", "rank_row", "ray_step", "ray_pose", "ray_row",
+                                         "ray_snap", "ray_shadow")] + \
+               [(k, ctypes.c_int32) for k in ("sort_after", "kin1_after", "kin1_pose", "kin1_row")]
+
+
+def steps_plan(n_steps, depth, sort_interval=0, dyn_calls=0, task_sort=1, task_calls=0, tasks_stale=True, cross=True,
+               rank_in_kin=False):
+    """rx_steps_plan: (launch records as dicts of ints / lists, ranked steps, tasks_stale after the call)."""
+    L = load()
+    a = RxPlanArgs(n_steps, depth, sort_interval, dyn_calls, task_sort, task_calls, int(tasks_stale), int(cross),
+                   int(rank_in_kin), 0, 0)
+    n = L.rx_steps_plan(ctypes.byref(a), None, 0)
+    if n < 0:
+        raise RxError(f"rx_steps_plan: bad arguments ({n})")
+    out = (RxPlanLaunch * n)()
+    assert L.rx_steps_plan(ctypes.byref(a), out, n) == n
+    recs = [{k: (list(v) if isinstance(v := getattr(r, k), _PLAN_ROW) else v) for k, _ in RxPlanLaunch._fields_}
+            for r in out]
+    return recs, a.ranked, bool(a.tasks_stale_out)
+
+
+def steps_plan_default(n_steps):
+    """(depth, rank_in_kin) that rx_steps takes for a call of n_steps steps."""
+    a = RxPlanArgs(n_steps, 0, 0, 0, 0, 0, 1, 1, -1, 0, 0)
+    if load().rx_steps_plan(ctypes.byref(a), None, 0) < 0:
+        raise RxError("rx_steps_plan: bad arguments")
+    return a.depth, bool(a.rank_in_kin)
 
 
 class RxAdamConfig(ctypes.Structure):
@@ -256,6 +301,8 @@ def load(build_if_missing=True):
     L.rx_step.argtypes = [_P, ctypes.POINTER(RxIO), _P]
     L.rx_step_phases.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.c_int32, _P]
     L.rx_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.c_int32, ctypes.POINTER(RxIOStrides), _P]
+    L.rx_steps_plan.argtypes = [ctypes.POINTER(RxPlanArgs), ctypes.POINTER(RxPlanLaunch), ctypes.c_int32]
+    L.rx_steps_plan.restype = ctypes.c_int32
     gae_args = [ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P]
     L.rx_gae.argtypes = gae_args
     L.rx_gae_scan.argtypes = gae_args
