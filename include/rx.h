@@ -530,6 +530,69 @@ int rx_build_cull_tables(int32_t n_tracks, const int32_t* wp_off, const double* 
 int rx_upload_tracks_device(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* nrm,
                             const double* seg, const double* meta, void* stream);
 
+/* Replacing slots in place (ABI v25, additive).  A slot's table rows, seg_f rows,
+ * boxes, slot_geo row and header depend on that slot's own rows and offsets only,
+ * so a new track with the SAME waypoint count as the slot it replaces can be
+ * written over that slot: no offset, no box count and no address changes, and every
+ * other slot stays bit for bit what it was.
+ *
+ * rx_track_patch: the n_upd replacement tracks as a small table of their own
+ * (rx_build_tracks' layout for n_upd tracks, src_off its waypoint offsets) and the
+ * slots they go to.
+ *
+ * rx_patch_tracks / rx_patch_tracks_host: handle-free, like rx_build_cull_tables.
+ * For every j < n_upd with k = slots[j] they copy source track j's wp, nrm, seg and
+ * meta rows over slot k's rows of the destination table (wp_off: the destination's
+ * offsets), and, when `t` is given, rewrite slot k's seg_f rows, leaf, super, wchunk
+ * and wsuper boxes (f64 and the five float blocks), slot_geo row and slot_hdr row by
+ * the rules of csrc/rx_cull.h at the offsets slot k already has.  The offset arrays
+ * of `t` are not written (nor read: the offsets are recomputed from wp_off, as
+ * rx_build_cull_tables does).  With t == NULL only the four table arrays are
+ * patched.  cull_chunk <= 0 and cull_super == 0 mean what they mean in
+ * rx_build_cull_tables.  rx_patch_tracks: wp_off, slots and src_off are HOST
+ * arrays, everything else DEVICE pointers; one launch (a wavefront per listed slot,
+ * csrc/rx_cull.hip k_patch_slots) on `stream`, no host wait; the listed slots'
+ * offsets travel through a stream-ordered allocation (not capturable).
+ * rx_patch_tracks_host: every pointer a HOST pointer, no HIP call.
+ *
+ * The contract is bytes: after the call every destination array equals, byte for
+ * byte, what rx_build_tracks(_host) plus rx_build_cull_tables(_host) write for the
+ * updated pool -- host against host, device against device (device against host
+ * keeps rx_build_cull_tables' hypot and signed-zero differences).  Nothing outside
+ * the listed slots' spans is written.
+ *
+ * Checked before any HIP call or write (RX_EINVAL, the message names the slot and
+ * the field): a null pointer among the ones read, n_upd outside 1..n_tracks, slots
+ * not ascending and distinct or out of range, src_off[0] != 0, a source track whose
+ * waypoint count differs from its slot's (a replaced slot keeps its waypoint
+ * count), and what rx_build_cull_tables checks on wp_off, G and S.  The host twin
+ * also refuses a source meta row with width < 0 or max_track_distance not > 0 (NaN
+ * is rx_build_tracks' mark of a bad track).
+ *
+ * rx_replace_tracks_device: the same patch on the handle's own buffers, whichever
+ * door its table came through.  The checks above against the handle's offsets;
+ * then it waits for the device (launches reading the old rows may be in flight on
+ * any stream), downloads the [n_upd][8] source meta block for rx_upload_tracks_device's
+ * width and max_track_distance checks (the slot named), and only then launches and
+ * waits for `stream`.  A refused call leaves the handle byte for byte as it was.
+ * The assignment, n_tracks, the wave order, the bound state and every buffer
+ * address stay; no env is reset: the caller resets the envs on the replaced slots
+ * (rx_reset with a mask).  Single-agent and two-car handles, every schedule.
+ * RX_ESTATE before a table has been uploaded. */
+typedef struct rx_track_patch {
+  int32_t n_upd;           /* slots to replace, 1..n_tracks */
+  const int32_t* slots;    /* HOST [n_upd], ascending, distinct, in [0, n_tracks) */
+  const int32_t* src_off;  /* HOST [n_upd + 1], src_off[0] = 0: waypoint offsets of the source table */
+  const double *wp, *nrm, *seg, *meta; /* the source table: rx_build_tracks' layout for n_upd tracks */
+} rx_track_patch;
+int rx_patch_tracks(int32_t n_tracks, const int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta,
+                    int32_t cull_chunk, int32_t cull_super, const rx_cull_tables* t, const rx_track_patch* p,
+                    void* stream);
+int rx_patch_tracks_host(int32_t n_tracks, const int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta,
+                         int32_t cull_chunk, int32_t cull_super, const rx_cull_tables* t, const rx_track_patch* p,
+                         void* stream);
+int rx_replace_tracks_device(rx_env* h, const rx_track_patch* p, void* stream);
+
 /* Fused optimizer step of PPO.ppo_update (agent/ppo.py:204-207):
  * nn.utils.clip_grad_norm_(params, max_grad_norm) then torch.optim.Adam.step()
  * (the default eps=1e-5 Adam of agent/ppo.py:83, no weight decay/amsgrad),

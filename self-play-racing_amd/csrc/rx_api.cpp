@@ -1996,6 +1996,159 @@ int rx_upload_tracks_device(rx_env* h, int32_t n_tracks, const int32_t* wp_off, 
   return RX_OK;
 }
 
+// ---- slots replaced in place (ABI v25, additive) ---------------------------------
+// What the host can check of a patch, before any HIP call or write; ps receives the
+// listed slots' rows for the kernel and the host twin, tot the table's box totals.
+// t == nullptr: the four table arrays only (G and SG are then not looked at).
+static int patch_check(const char* fn, int32_t n, const int32_t* wp_off, const void* wp, const void* nrm,
+                       const void* seg, const void* meta, int32_t G, int32_t SG, const rx_cull_tables* t,
+                       const rx_track_patch* p, std::vector<rx_patch_slot>* ps, int64_t tot[4]) {
+  if (n <= 0) return fail(RX_EINVAL, "%s: n_tracks must be > 0 (got %d)", fn, n);
+  if (!wp_off) return fail(RX_EINVAL, "%s: wp_off is null", fn);
+  if (!wp) return fail(RX_EINVAL, "%s: wp is null", fn);
+  if (!nrm) return fail(RX_EINVAL, "%s: nrm is null", fn);
+  if (!seg) return fail(RX_EINVAL, "%s: seg is null", fn);
+  if (!meta) return fail(RX_EINVAL, "%s: meta is null", fn);
+  if (!p) return fail(RX_EINVAL, "%s: the patch is null", fn);
+  const struct {
+    const void* q;
+    const char* name;
+  } fields[] = {{p->slots, "slots"}, {p->src_off, "src_off"}, {p->wp, "wp"},
+                {p->nrm, "nrm"},     {p->seg, "seg"},         {p->meta, "meta"}};
+  for (const auto& f : fields)
+    if (!f.q) return fail(RX_EINVAL, "%s: patch->%s is null", fn, f.name);
+  std::vector<int32_t> off;
+  const int rc = t ? cull_check(fn, n, wp_off, wp, seg, meta, G, SG, t, false, &off, tot)
+                   : cull_check(fn, n, wp_off, nullptr, nullptr, nullptr, 0, 0, nullptr, true, &off, tot);
+  if (rc != RX_OK) return rc;
+  if (p->n_upd < 1 || p->n_upd > n)
+    return fail(RX_EINVAL, "%s: patch->n_upd must be 1 .. n_tracks = %d (got %d)", fn, n, p->n_upd);
+  if (p->src_off[0] != 0) return fail(RX_EINVAL, "%s: patch->src_off[0] must be 0 (got %d)", fn, p->src_off[0]);
+  const size_t n1 = (size_t)n + 1;
+  ps->assign((size_t)p->n_upd, rx_patch_slot{});
+  for (int32_t j = 0; j < p->n_upd; ++j) {
+    const int32_t k = p->slots[j];
+    if (k < 0 || k >= n)
+      return fail(RX_EINVAL, "%s: patch->slots[%d] = slot %d is outside [0, %d)", fn, j, k, n);
+    if (j > 0 && k <= p->slots[j - 1])
+      return fail(RX_EINVAL, "%s: patch->slots[%d] = slot %d follows slot %d: the slots must be ascending and "
+                             "distinct", fn, j, k, p->slots[j - 1]);
+    const int64_t Ws = (int64_t)p->src_off[j + 1] - p->src_off[j], W = (int64_t)wp_off[k + 1] - wp_off[k];
+    if (Ws != W)
+      return fail(RX_EINVAL, "%s: slot %d: patch->src_off gives source track %d %lld waypoints, the slot has %lld "
+                             "(a replaced slot keeps its waypoint count)", fn, k, j, (long long)Ws, (long long)W);
+    (*ps)[j] = rx_patch_slot{k, p->src_off[j], wp_off[k], (int32_t)W, off[n1 + k], off[2 * n1 + k],
+                             off[3 * n1 + k], off[4 * n1 + k]};
+  }
+  return RX_OK;
+}
+
+// rx_upload_tracks' per-track checks on the source meta rows (host memory), the slot named
+static int patch_check_meta(const char* fn, const rx_track_patch* p, const double* meta_h) {
+  for (int32_t j = 0; j < p->n_upd; ++j) {
+    const double* m = meta_h + 8 * (size_t)j;
+    if (!(m[3] >= 0))
+      return fail(RX_EINVAL, "%s: slot %d (source track %d): width %g is negative or NaN", fn, p->slots[j], j, m[3]);
+    if (!(m[4] > 0))
+      return fail(RX_EINVAL, "%s: slot %d (source track %d): max_track_distance must be > 0 (got %g; NaN marks a "
+                             "track rx_build_tracks found invalid)", fn, p->slots[j], j, m[4]);
+  }
+  return RX_OK;
+}
+
+// The launch behind rx_patch_tracks and rx_replace_tracks_device: the listed slots' rows
+// go up through a stream-ordered allocation, as cull_launch's offsets do.
+static int patch_launch(const char* fn, const std::vector<rx_patch_slot>& ps, const int64_t tot[4], double* wp,
+                        double* nrm, double* seg, double* meta, int32_t G, int32_t SG, const rx_cull_tables* t,
+                        const rx_track_patch* p, hipStream_t s) {
+  rx_patch_slot* ps_dev = nullptr;
+  const size_t bytes = ps.size() * sizeof(rx_patch_slot);
+  if (hipMallocAsync((void**)&ps_dev, bytes, s) != hipSuccess || !ps_dev)
+    return fail(RX_ENOMEM, "%s: hipMallocAsync(%zu bytes) failed", fn, bytes);
+  hipError_t e = hipMemcpyAsync(ps_dev, ps.data(), bytes, hipMemcpyHostToDevice, s);
+  int lrc = 0;
+  if (e == hipSuccess)
+    lrc = rx_launch_patch_slots((int)ps.size(), t ? G : 0, t ? SG : 0, ps_dev, p, wp, nrm, seg, meta, t, tot[0],
+                                tot[1], s);
+  const hipError_t ef = hipFreeAsync(ps_dev, s);
+  if (e != hipSuccess) return fail(RX_EHIP, "%s: slot list copy failed: %s", fn, hipGetErrorString(e));
+  if (lrc != 0) return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)lrc));
+  if (ef != hipSuccess) return fail(RX_EHIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(ef));
+  return RX_OK;
+}
+
+int rx_patch_tracks(int32_t n, const int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta, int32_t G,
+                    int32_t SG, const rx_cull_tables* t, const rx_track_patch* p, void* stream) {
+  std::vector<rx_patch_slot> ps;
+  int64_t tot[4];
+  const int rc = patch_check("rx_patch_tracks", n, wp_off, wp, nrm, seg, meta, G, SG, t, p, &ps, tot);
+  if (rc != RX_OK) return rc;
+  return patch_launch("rx_patch_tracks", ps, tot, wp, nrm, seg, meta, G, SG, t, p, (hipStream_t)stream);
+}
+
+int rx_patch_tracks_host(int32_t n, const int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta,
+                         int32_t G, int32_t SG, const rx_cull_tables* t, const rx_track_patch* p, void* /*stream*/) {
+  std::vector<rx_patch_slot> ps;
+  int64_t tot[4];
+  int rc = patch_check("rx_patch_tracks_host", n, wp_off, wp, nrm, seg, meta, G, SG, t, p, &ps, tot);
+  if (rc != RX_OK) return rc;
+  if ((rc = patch_check_meta("rx_patch_tracks_host", p, p->meta))) return rc;
+  if (!t) G = SG = 0;
+  for (size_t j = 0; j < ps.size(); ++j) {  // the kernel's steps (rx_cull.hip, k_patch_slots) with one lane
+    const rx_patch_slot& d = ps[j];
+    const int32_t k = d.slot, W = d.W;
+    const double* s = p->seg + 8 * (size_t)d.src0;
+    const double* w = p->wp + 2 * (size_t)d.src0;
+    const double* m = p->meta + 8 * j;
+    rx_cull_copy_rows<2>(w, wp + 2 * (size_t)d.wp0, W, 0, 1);
+    rx_cull_copy_rows<2>(p->nrm + 2 * (size_t)d.src0, nrm + 2 * (size_t)d.wp0, W, 0, 1);
+    rx_cull_copy_rows<4>(s, seg + 8 * (size_t)d.wp0, 2 * W, 0, 1);
+    for (int c = 0; c < 8; ++c) meta[8 * (size_t)k + c] = m[c];
+    if (!t) continue;
+    rx_cull_slot o = {0, 0, 0, 0, tot[0], tot[1], t->chunk_box, t->super_box, t->wchunk_box, t->wsuper_box,
+                      t->chunk_box_f, t->super_box_f};
+    double b[4], longest, geo[4] = {0.0, 0.0, 0.0, 0.0};
+    rx_cull_extent(s, W, 0, 1, t->seg_f + 8 * (size_t)d.wp0, b, &longest);
+    if (G > 0) {
+      rx_cull_geo(b, rx_cull_reach(s, W, 0, 1, 0.5 * (b[0] + b[2]), 0.5 * (b[1] + b[3])), longest, geo);
+      o.chunk0 = d.chunk0;
+      o.super0 = SG > 0 ? d.super0 : 0;
+      o.wchunk0 = d.wchunk0;
+      o.wsuper0 = d.wsuper0;
+      rx_cull_boxes(s, w, W, G, SG, 0, 1, &o);
+      for (int c = 0; c < 4; ++c) t->slot_geo[4 * (size_t)k + c] = geo[c];
+    }
+    rx_cull_header((rx_slot_hdr*)t->slot_hdr + k, d.wp0, W, &o, geo, m);
+  }
+  return RX_OK;
+}
+
+int rx_replace_tracks_device(rx_env* h, const rx_track_patch* p, void* stream) {
+  const char* fn = "rx_replace_tracks_device";
+  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
+  if (h->n_tracks <= 0) return fail(RX_ESTATE, "%s before a track table was uploaded", fn);
+  const int G = h->cfg.cull_chunk, SG = h->cfg.cull_super;
+  const rx_cull_tables t = {h->chunk_off.p, h->super_off.p,  h->wchunk_off.p, h->wsuper_off.p,  h->chunk_box.p,
+                            h->super_box.p, h->wchunk_box.p, h->wsuper_box.p, h->slot_geo.p,    h->chunk_box_f.p,
+                            h->super_box_f.p, h->seg_f.p,    h->slot_hdr.p};
+  std::vector<rx_patch_slot> ps;
+  int64_t tot[4];
+  int rc = patch_check(fn, h->n_tracks, h->wp_off_h.data(), h->wp.p, h->nrm.p, h->seg.p, h->meta.p, G, SG, &t, p, &ps,
+                       tot);
+  if (rc != RX_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  RX_HIP(hipSetDevice(h->cfg.device));
+  RX_HIP(hipDeviceSynchronize());  // launches reading the old rows may be in flight on any stream
+  std::vector<double> meta_h(8 * (size_t)p->n_upd);  // the one transfer to the host
+  RX_HIP(hipMemcpyAsync(meta_h.data(), p->meta, meta_h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  RX_HIP(hipStreamSynchronize(s));
+  if ((rc = patch_check_meta(fn, p, meta_h.data()))) return rc;
+  // nothing of the handle has changed so far
+  if ((rc = patch_launch(fn, ps, tot, h->wp.p, h->nrm.p, h->seg.p, h->meta.p, G, SG, &t, p, s))) return rc;
+  RX_HIP(hipStreamSynchronize(s));
+  return RX_OK;
+}
+
 // ---- rendering (ABI v25, additive) ---------------------------------------------
 static int raster_static_args(const char* fn, int32_t n, int32_t size, int32_t n_edges, const void* edge_off,
                               const void* edges, const void* layer) {

@@ -212,6 +212,20 @@ RX_CULL_HD void rx_cull_boxes(const double* s, const double* w, int32_t W, int32
   }
 }
 
+// rx_patch_tracks: this lane's share of n rows of S doubles copied from src to dst
+// (a row per iteration: 16 B per lane for wp / nrm rows, 32 B for seg rows)
+template <int S>
+RX_CULL_HD void rx_cull_copy_rows(const double* src, double* dst, int32_t n, int lane, int n_lanes) {
+  for (int32_t i = lane; i < n; i += n_lanes)
+    for (int c = 0; c < S; ++c) dst[S * (int64_t)i + c] = src[S * (int64_t)i + c];
+}
+
+// what rx_patch_tracks' kernel is told of a listed slot, 8 int32 per slot
+struct rx_patch_slot {
+  int32_t slot, src0, wp0, W;  // the slot, its first source and destination waypoint row, its waypoints
+  int32_t chunk0, super0, wchunk0, wsuper0;  // the slot's first box in the four box arrays
+};
+
 // the slot's 128-byte header row (geo: the slot's slot_geo row; zeros without culling tables)
 RX_CULL_HD void rx_cull_header(rx_slot_hdr* r, int32_t wp0, int32_t W, const rx_cull_slot* o, const double* geo,
                                const double* meta) {

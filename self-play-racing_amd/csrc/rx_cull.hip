@@ -22,6 +22,9 @@
 // holds wp_off and the four box offset arrays back to back, n + 1 entries each.
 // Reads 2 x 64 W + ~96 W bytes and stores ~(32 + 224 / G) W bytes per slot:
 // bound by the table's bytes, like k_build_tracks.
+//
+// k_patch_slots (rx_patch_tracks): the same passes for a LIST of slots whose tracks
+// are replaced in place, reading a small source table; see the kernel.
 #include <hip/hip_runtime.h>
 
 #include "rx_cull.h"
@@ -84,7 +87,71 @@ __global__ __launch_bounds__(64 * kCullWaves) void k_cull_tables(int n_tracks, i
   rx_cull_header((rx_slot_hdr*)t.slot_hdr + k, wp0, W, &o, geo, meta + 8 * (int64_t)k);
 }
 
+// k_patch_slots (rx_patch_tracks, rx_replace_tracks_device): a wavefront per LISTED
+// slot writes a source track over that slot, at the offsets the slot already has
+// (ps[j], computed by the host from wp_off).  Pass 1 also stores the wp / nrm / seg
+// rows to the destination span; every pass reads the SOURCE rows, so no wave reads
+// its own global stores back and no fence is needed.  The reductions are
+// k_cull_tables' (the same lane strides and shuffles), so the bytes are its bytes.
+// No offset entry is written.  t == nullptr-like (has_t == 0): the table rows only.
+__global__ __launch_bounds__(64 * kCullWaves) void k_patch_slots(
+    int n_upd, int G, int SG, const rx_patch_slot* __restrict__ ps, const double* __restrict__ src_wp,
+    const double* __restrict__ src_nrm, const double* __restrict__ src_seg, const double* __restrict__ src_meta,
+    double* __restrict__ wp, double* __restrict__ nrm, double* __restrict__ seg, double* __restrict__ meta, int has_t,
+    rx_cull_tables t, int64_t n_leaf, int64_t n_super) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int j = blockIdx.x * kCullWaves + wave;
+  if (j >= n_upd) return;  // whole waves leave: nothing below waits for another wave
+  const rx_patch_slot d = ps[j];
+  const int32_t k = d.slot, W = d.W;
+  const double* s = src_seg + 8 * (int64_t)d.src0;
+  const double* w = src_wp + 2 * (int64_t)d.src0;
+  const double* m = src_meta + 8 * (int64_t)j;
+  rx_cull_copy_rows<2>(w, wp + 2 * (int64_t)d.wp0, W, lane, 64);
+  rx_cull_copy_rows<2>(src_nrm + 2 * (int64_t)d.src0, nrm + 2 * (int64_t)d.wp0, W, lane, 64);
+  rx_cull_copy_rows<4>(s, seg + 8 * (int64_t)d.wp0, 2 * W, lane, 64);
+  double geo[4] = {0.0, 0.0, 0.0, 0.0};
+  rx_cull_slot o = {0, 0, 0, 0, n_leaf, n_super, t.chunk_box, t.super_box, t.wchunk_box, t.wsuper_box,
+                    t.chunk_box_f, t.super_box_f};
+  if (has_t) {
+    double b[4], longest;
+    rx_cull_extent(s, W, lane, 64, t.seg_f + 8 * (int64_t)d.wp0, b, &longest);
+    if (G > 0) {
+      for (int x = 32; x >= 1; x >>= 1) {
+        const double other[4] = {__shfl_xor(b[0], x, 64), __shfl_xor(b[1], x, 64), __shfl_xor(b[2], x, 64),
+                                 __shfl_xor(b[3], x, 64)};
+        rx_cull_box_union(b, other);
+      }
+      longest = wave_max(longest);
+      const double cx = 0.5 * (b[0] + b[2]), cy = 0.5 * (b[1] + b[3]);
+      const double reach = wave_max(rx_cull_reach(s, W, lane, 64, cx, cy));
+      rx_cull_geo(b, reach, longest, geo);
+      o.chunk0 = d.chunk0;
+      o.super0 = SG > 0 ? d.super0 : 0;
+      o.wchunk0 = d.wchunk0;
+      o.wsuper0 = d.wsuper0;
+      rx_cull_boxes(s, w, W, G, SG, lane, 64, &o);
+    }
+  }
+  if (lane != 0) return;
+  for (int c = 0; c < 8; ++c) meta[8 * (int64_t)k + c] = m[c];
+  if (!has_t) return;
+  if (G > 0)
+    for (int c = 0; c < 4; ++c) t.slot_geo[4 * (int64_t)k + c] = geo[c];
+  rx_cull_header((rx_slot_hdr*)t.slot_hdr + k, d.wp0, W, &o, geo, m);
+}
+
 }  // namespace
+
+extern "C" int rx_launch_patch_slots(int n_upd, int G, int SG, const rx_patch_slot* ps, const rx_track_patch* p,
+                                     double* wp, double* nrm, double* seg, double* meta, const rx_cull_tables* t,
+                                     int64_t n_leaf, int64_t n_super, hipStream_t s) {
+  const int n_wg = (n_upd + kCullWaves - 1) / kCullWaves;
+  const rx_cull_tables none = {};
+  hipLaunchKernelGGL(k_patch_slots, dim3(n_wg), dim3(64 * kCullWaves), 0, s, n_upd, G, SG, ps, p->wp, p->nrm, p->seg,
+                     p->meta, wp, nrm, seg, meta, t ? 1 : 0, t ? *t : none, n_leaf, n_super);
+  return (int)hipGetLastError();
+}
 
 extern "C" int rx_launch_cull_tables(int n_tracks, int G, int SG, const int32_t* off, const double* wp,
                                      const double* seg, const double* meta, const rx_cull_tables* t, int64_t n_leaf,

@@ -344,6 +344,12 @@ extern "C" int rx_launch_build_tracks(int n_tracks, int factor, const int32_t* c
 extern "C" int rx_launch_cull_tables(int n_tracks, int G, int SG, const int32_t* off, const double* wp,
                                      const double* seg, const double* meta, const rx_cull_tables* t, int64_t n_leaf,
                                      int64_t n_super, hipStream_t s);
+// rx_cull.hip: k_patch_slots, the listed slots rewritten in place (ps: rx_cull.h's rx_patch_slot rows in device
+// memory; t may be null: the four table arrays only)
+struct rx_patch_slot;
+extern "C" int rx_launch_patch_slots(int n_upd, int G, int SG, const rx_patch_slot* ps, const rx_track_patch* p,
+                                     double* wp, double* nrm, double* seg, double* meta, const rx_cull_tables* t,
+                                     int64_t n_leaf, int64_t n_super, hipStream_t s);
 // rx_render.hip: the renderer's three kernels (arguments checked by rx_api.cpp)
 extern "C" int rx_launch_raster_static(int n, int size, int n_edges, const int32_t* edge_off, const int32_t* edges,
                                        uint8_t* layer, hipStream_t s);

@@ -45,7 +45,7 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_track_episode_host", "rx_track_episode_step", "rx_track_episodic_rollout_steps",
            "rx_track_learn_tally_slots", "rx_track_learn_tally_slots_host", "rx_track_learn_episode",
            "rx_track_learn_episode_host", "rx_track_learn_episode_step", "rx_track_learn_episodic_rollout_steps",
-           "rx_steps_plan")
+           "rx_steps_plan", "rx_patch_tracks", "rx_patch_tracks_host", "rx_replace_tracks_device")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -266,6 +266,14 @@ class RxCullTables(ctypes.Structure):
     _fields_ = [(k, _P) for k in CULL_FIELDS]
 
 
+# slots replaced in place (ABI v25, additive; include/rx.h): the small source table and the slots it goes to
+PATCH_FIELDS = ("slots", "src_off", "wp", "nrm", "seg", "meta")
+
+
+class RxTrackPatch(ctypes.Structure):
+    _fields_ = [("n_upd", ctypes.c_int32)] + [(k, _P) for k in PATCH_FIELDS]
+
+
 class RxError(RuntimeError):
     pass
 
@@ -352,6 +360,10 @@ def load(build_if_missing=True):
                                        ctypes.POINTER(RxCullTables), _P]
     L.rx_build_cull_tables_host.argtypes = L.rx_build_cull_tables.argtypes
     L.rx_upload_tracks_device.argtypes = [_P, ctypes.c_int32, _P, _P, _P, _P, _P, _P]
+    L.rx_patch_tracks.argtypes = [ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32,
+                                  ctypes.POINTER(RxCullTables), ctypes.POINTER(RxTrackPatch), _P]
+    L.rx_patch_tracks_host.argtypes = L.rx_patch_tracks.argtypes
+    L.rx_replace_tracks_device.argtypes = [_P, ctypes.POINTER(RxTrackPatch), _P]
     L.rx_eval_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxEvalIO), ctypes.c_int32, _P]
     L.rx_policy_act_bank.argtypes = [ctypes.POINTER(RxPolicyBankIO), _P]
     L.rx_match_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxMatchIO), ctypes.c_int32, _P]

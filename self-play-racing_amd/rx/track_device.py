@@ -16,6 +16,8 @@ reference's numpy expressions.  ``from_arrays`` uploads a
 ``TrackSet.arrays()`` dict as it is, so an env swapped onto it steps bit for bit
 like one constructed on that TrackSet.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -147,6 +149,66 @@ class DeviceTrackTable:
         dev = torch.device(device)
         up = {k: torch.from_numpy(np.ascontiguousarray(arrays[k], dtype=np.float64)).to(dev) for k in KEYS}
         return cls(arrays["wp_off"], up["wp"], up["nrm"], up["seg"], up["meta"])
+
+    @staticmethod
+    def patch(source):
+        """The rx_track_patch struct that puts ``source`` (``replacement``'s table)
+        into its ``slots``, and the arrays it points to: keep the second value
+        alive until the call that takes the struct returns."""
+        keep = (source.slots, source.wp_off, source.wp, source.nrm, source.seg, source.meta)
+        return _lib.RxTrackPatch(len(source.slots), *[_lib.ptr(x) for x in keep]), keep
+
+    def replacement(self, slots, control_points, widths):
+        """The first half of ``replace``: the checks, then the small table of the new
+        tracks (``build``: one rx_build_tracks launch), in ascending slot order; its
+        ``slots`` attribute holds those slots (int32), row for row.  Nothing of this
+        table changes."""
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        n = len(self)
+        if len(slots) == 0 or len(control_points) != len(slots) or len(widths) != len(slots):
+            raise ValueError("replace: need at least one slot, and one track and one width per slot")
+        if slots.min() < 0 or slots.max() >= n or len(np.unique(slots)) != len(slots):
+            raise ValueError(f"replace: the slots must be distinct and lie in [0, {n})")
+        order = np.argsort(slots, kind="stable")
+        slots = slots[order]
+        cps = [DEFAULT_CONTROL_POINTS if control_points[i] is None else control_points[i] for i in order]
+        ws = [DEFAULT_WIDTH if widths[i] is None else widths[i] for i in order]
+        for k, c in zip(slots, cps):
+            have, want = len(c) * self.factor, int(self.wp_off[k + 1] - self.wp_off[k])
+            if have != want:
+                raise ValueError(f"replace: slot {k} has {want} waypoints ({want / self.factor:g} control points x "
+                                 f"{self.factor}), its new track {len(c)} control points: a replaced slot keeps its "
+                                 "point count")
+        source = DeviceTrackTable.build(cps, ws, factor=self.factor, device=self.device)
+        source.slots = np.ascontiguousarray(slots, dtype=np.int32)
+        return source
+
+    def apply(self, source):
+        """The second half of ``replace``: ``source``'s rows written over its slots'
+        rows of this table (rx_patch_tracks: one launch on torch's current stream, no
+        wait, no download), and the control points and widths this table knows."""
+        p, keep = self.patch(source)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().rx_patch_tracks(len(self), _lib.ptr(self.wp_off), _lib.ptr(self.wp),
+                                                   _lib.ptr(self.nrm), _lib.ptr(self.seg), _lib.ptr(self.meta), 0, 0,
+                                                   None, ctypes.byref(p), _lib.stream_ptr()), "rx_patch_tracks")
+        del keep
+        if self.control_points is not None:  # (a build_from_device table downloads them here)
+            for k, c, w in zip(source.slots, source.control_points, source.widths):
+                self._control_points[k], self._widths[k] = c, w
+        self._track_set = None
+
+    def replace(self, slots, control_points, widths):
+        """New tracks in the given slots of this table, in place.  A slot keeps its
+        waypoint count, so every offset and address stays: a track whose point count
+        differs from its slot's is refused (ValueError naming the slot) before
+        anything is built.  ``slots`` must be distinct; they are taken in ascending
+        order with their tracks.  Returns the small source table (``replacement``).
+        A track only device memory shows to be bad is copied as it is, NaN mark
+        included: ``RacingVectorEnv.replace_tracks`` refuses it before it gets here."""
+        source = self.replacement(slots, control_points, widths)
+        self.apply(source)
+        return source
 
     def download(self):
         """The raw table as a dict of host arrays (rx_upload_tracks' layout)."""

@@ -18,6 +18,7 @@ The rules are csrc/rx_curriculum.h; DESIGN.md §4 "Episodic track draws".
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -56,8 +57,14 @@ class EpisodicCurriculumPPO(CurriculumPPO):
     ``config["episodic_scores_every"]`` (1) updates; ``reassign_tracks`` is never
     called.  ``resample_tracks`` with nothing to retire only refreshes the scores
     and hands back the rollout's own next_obs / next_done; with slots retired it is
-    the parent's ``set_tracks`` path, which resets every env: set
-    ``curriculum_refresh`` to 0 to keep the run free of global resets.
+    by default the parent's ``set_tracks`` path, which resets every env.
+    ``config["episodic_partial"]`` = True (default False) keeps the run free of
+    global resets: the retired slots' tracks are replaced in place
+    (``RacingVectorEnv.replace_tracks``), only the envs on those slots are reset,
+    every other episode goes on, rx_assign does not run and the captured rollout
+    graphs stay (no address moved).  A slot keeps its point count there
+    (``spawn_same_points``), so the pool's point-count histogram stays the initial
+    pool's.
     ``config["episodic_slots"]`` = True records the [T, N] slots of each rollout
     (``slots()``).
 
@@ -68,6 +75,7 @@ class EpisodicCurriculumPPO(CurriculumPPO):
         self.scores_every = int(config.get("episodic_scores_every", 1))
         if self.scores_every < 1:
             raise ValueError(f"episodic_scores_every={self.scores_every} must be >= 1")
+        self.partial = bool(config.get("episodic_partial", False))
         self._updates = 0
         self._carry = None  # the last rollout's (next_obs, next_done)
         super().__init__(env_fn, config, device)
@@ -104,19 +112,68 @@ class EpisodicCurriculumPPO(CurriculumPPO):
         return None if sr is None else sr.slots
 
     # ------------------------------------------------------------ resampling
+    def _after_retire(self, retired):
+        """The partial path's hook between the tallies' reset and the new scores: what else a
+        subclass keeps per slot starts again here."""
+
+    def _resample_partial(self, retired):
+        """``retired`` (ascending) replaced in place: fresh tracks of the slots' own point
+        counts (``spawn_same_points``, generation g), their tallies start again, the envs
+        on them are reset; everything else goes on.  No ``set_tracks``, no
+        ``reassign_tracks``, no draw: an env leaves a replaced slot when its episode ends."""
+        cur, envs = self.curriculum, self.envs
+        g = envs.track_generation + 1
+        cps, widths = spawn_same_points(self.config["seed"], g, [len(self._cps[k]) for k in retired])
+        cur.reset_slots(retired)
+        self._after_retire(retired)
+        cur.scores()  # a fresh slot weighs what an unseen one does
+        obs, mask = envs.replace_tracks(retired, cps, widths)
+        for k, cp, w in zip(retired, cps, widths):
+            self._cps[k], self._widths[k] = cp, w
+        if self._carry is None:
+            next_obs, next_done = obs.clone(), torch.zeros(self.num_local_envs, device=self.device)
+        else:  # the carried rows, the reset envs' replaced: their reset observations, not done
+            next_obs, next_done = self._carry
+            hit = mask.bool()
+            next_obs[hit] = obs[hit]
+            next_done[hit] = 0
+        self.retired.append([int(k) for k in retired])
+        return next_obs, next_done
+
     def resample_tracks(self, control_points=None, widths=None):
         """With no arguments and no slot to retire: the scores only; the envs keep
-        running and the rollout's own (next_obs, next_done) come back.  Otherwise
+        running and the rollout's own (next_obs, next_done) come back.  With slots to
+        retire and ``episodic_partial``: ``_resample_partial``.  Otherwise
         ``CurriculumPPO.resample_tracks``' ``set_tracks`` path: new tracks in the retired
         slots, every env redrawn and reset."""
         if control_points is None and widths is None:
             self.curriculum.scores()
-            if not len(self._mastered()):
+            retired = self._mastered()
+            if not len(retired):
                 self.retired.append([])
                 if self._carry is not None:
                     return self._carry
                 return self.envs.buf["obs"].clone(), torch.zeros(self.num_local_envs, device=self.device)
+            if self.partial:
+                return self._resample_partial(np.sort(retired))
         return super().resample_tracks(control_points, widths)
+
+
+def spawn_same_points(seed, generation, point_counts):
+    """Fresh tracks for retired slots that keep their point counts -> (control points,
+    widths), one per entry of ``point_counts``.  The RandomState of
+    ``CurriculumPPO._spawn_tracks`` (``seed + 7919 * generation``); per slot the
+    parameters of ``gen_tracks`` (``_draw_params``, its drawn point count discarded for
+    the slot's own), the track, then one ``randint(6, 10)`` width.  Host only;
+    ``np.random`` does not move."""
+    from .track import _draw_params, gen_random_track
+    rng = np.random.RandomState((int(seed) + 7919 * int(generation)) % 2 ** 32)
+    cps, widths = [], []
+    for P in point_counts:
+        _, base, var, jit, smooth = _draw_params(rng)
+        cps.append(gen_random_track(int(P), base, var, jit, smooth, None, rng))
+        widths.append(int(rng.randint(6, 10)))
+    return cps, widths
 
 
 def check_episodic(envs):
@@ -132,4 +189,4 @@ def check_episodic(envs):
                          "sched=dict(lane_tracks=1) (with at most 2,048 envs, dyn_lpe=1 as well)")
 
 
-__all__ = ["EpisodicStepRollout", "EpisodicCurriculumPPO", "check_episodic"]
+__all__ = ["EpisodicStepRollout", "EpisodicCurriculumPPO", "check_episodic", "spawn_same_points"]

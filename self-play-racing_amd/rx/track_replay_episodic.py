@@ -55,8 +55,10 @@ class EpisodicReplayCurriculumPPO(EpisodicCurriculumPPO):
     slots without the autoreset rows and folded into the scores.  The finish tallies
     are kept and still decide which slots are retired; a resample that retires slots
     is ``ReplayCurriculumPPO``'s: the retired slots start again as never scored and
-    every env is redrawn by ``replay.draw`` and reset (set ``curriculum_refresh`` to 0
-    to keep the run free of global resets).
+    every env is redrawn by ``replay.draw`` and reset.  With ``episodic_partial`` the
+    retired slots are replaced in place instead (``EpisodicCurriculumPPO``): they start
+    again as never scored, only their envs are reset, and the run stays free of global
+    resets.
 
     Refused (ValueError) as in ``EpisodicCurriculumPPO`` and ``ReplayCurriculumPPO``,
     before a device is touched."""
@@ -109,6 +111,10 @@ class EpisodicReplayCurriculumPPO(EpisodicCurriculumPPO):
         self.replay.fold(self.replay_updates)
         self.replay_updates += 1
         return advantages, returns
+
+    def _after_retire(self, retired):
+        self.replay.reset_slots(retired)  # the partial path: the replaced slots read as never scored
+        self.replay.tables(self.replay_updates)
 
     def _draw_tracks(self, generation, retired):
         if len(retired):

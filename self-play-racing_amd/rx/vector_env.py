@@ -324,6 +324,45 @@ class RacingVectorEnv:
         self._episode_start[:] = time.perf_counter()
         return obs
 
+    def replace_tracks(self, slots, control_points, widths):
+        """New tracks in some slots of the live env's pool, in place, without the
+        global reset of ``set_tracks``: ``control_points[j]`` / ``widths[j]`` go into
+        slot ``slots[j]`` and must have the slot's point count (ValueError naming the
+        slot otherwise).  The tracks are built on the device and written over the
+        slots' rows of the resident table (``DeviceTrackTable.replace``; the table is
+        uploaded from the host ``TrackSet`` on first use) and of the handle's own
+        buffers (rx_replace_tracks_device: the culling tables, headers and float
+        copies of those slots only); no offset, address, assignment or wave order
+        changes.  Then only the envs that sit on a replaced slot are reset: their
+        episodes in flight are dropped untallied, every other env is untouched bit
+        for bit.  A track librx refuses (RxError naming the slot) leaves the env as
+        it was.  Returns (obs, mask): the env's obs rows, the reset envs' replaced by
+        their reset observations, and the uint8 [N] device mask of the reset envs."""
+        from .track_device import DeviceTrackTable
+        table = self._table
+        if table is None:
+            table = DeviceTrackTable.from_arrays(self.tracks.arrays(), self.device)
+        with torch.cuda.device(self.device):
+            source = table.replacement(slots, control_points, widths)
+            p, keep = table.patch(source)
+            # the handle first: it sees the source's meta rows and refuses a bad track before anything is written
+            _lib.check(self.L.rx_replace_tracks_device(self._h, ctypes.byref(p), _lib.stream_ptr()),
+                       "rx_replace_tracks_device")
+            del keep
+            table.apply(source)
+            flag = torch.zeros(len(table), dtype=torch.uint8, device=self.device)
+            flag[torch.from_numpy(source.slots.astype(np.int64)).to(self.device)] = 1
+            mask = flag[self._st["track"].long()]
+            self._table, self._tracks = table, None
+            self.track_generation += 1
+            obs = self.reset_device(mask)
+        if self._track_ids_stale:  # the device moved envs between slots: the mask knows, the host does not
+            hit = mask.bool().cpu().numpy()
+        else:
+            hit = np.isin(self._track_of_env, source.slots)
+        self._episode_start[hit] = time.perf_counter()
+        return obs, mask
+
     def _upload_tracks(self):
         t = self.tracks.arrays()
         n = len(t["meta"])

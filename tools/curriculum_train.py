@@ -29,6 +29,8 @@ its next slot when its own episode ends, no episode is dropped, and a resample
 with nothing to retire resets nobody; with ``--replay`` as well it is
 ``rx.track_replay_episodic.EpisodicReplayCurriculumPPO``, whose ended envs draw
 from the value-loss scores (prioritised level replay per episode).  ``--episodic
+--partial`` (``episodic_partial``) also replaces the retired slots in place, so a
+resample that retires slots resets only the envs on them.  ``--episodic
 --evolve`` is refused.  Every curriculum run also reports the
 episodes tallied per update, the slots that reached ``--min-episodes`` and, per
 update, the share of the envs on the fullest slot (with replay scores also on the
@@ -83,6 +85,7 @@ def run(kind, args, evaluator):
         from rx.track_episodic import EpisodicCurriculumPPO as cls
         if replay:
             from rx.track_replay_episodic import EpisodicReplayCurriculumPPO as cls
+        cfg["episodic_partial"] = bool(args.partial)
     t = cls(lambda i: RacingEnv(num_sensors=11, track_pool=pool, track_id=i % n, track_width=widths[i % n]), cfg,
             device="cuda")
     info, curve, tallied, top_share, rank1_share = {"steps": [], "rewards": []}, [], [], [], []
@@ -112,6 +115,7 @@ def run(kind, args, evaluator):
                               for k, v in tab.items()}
         out["retired_per_resample"] = [len(r) for r in t.retired]
         out["episodic"] = bool(episodic)
+        out["episodic_partial"] = bool(episodic and args.partial)
         out["tally_episodes_after_update"] = tallied
         out["share_of_envs_on_the_fullest_slot_after_update"] = top_share
         out["share_of_envs_on_the_rank1_slot_after_update"] = rank1_share if rank1_share else None
@@ -145,6 +149,9 @@ def main():
     ap.add_argument("--evolve-edit", type=float, default=0.5, help="the fraction of retired slots filled by an edit")
     ap.add_argument("--episodic", action="store_true",
                     help="an env draws its next slot when its episode ends (rx.track_episodic), no global redraw")
+    ap.add_argument("--partial", action="store_true",
+                    help="with --episodic: retired slots are replaced in place and only their envs reset "
+                         "(episodic_partial), no global reset")
     ap.add_argument("--prec", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--show", type=int, default=20, help="slots of the table to print, the most failed first")
@@ -153,6 +160,8 @@ def main():
     args = ap.parse_args()
     if args.episodic and args.evolve:
         sys.exit("--episodic moves envs between the slots of a fixed table: not with --evolve (DESIGN.md §8)")
+    if args.partial and not args.episodic:
+        sys.exit("--partial replaces retired slots under the episodic trainers: pass --episodic as well")
     if not torch.cuda.is_available():
         sys.exit("curriculum_train.py trains on the GPU: no device found")
     from rx.evaluate import Evaluator
