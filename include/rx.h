@@ -227,6 +227,33 @@ int rx_upload_tracks(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const d
  * track (segment loads become scalar/broadcast). */
 int rx_assign(rx_env* h, const int32_t* track_of_env);
 
+/* The assignment as a pure function (no device, no handle; additive to ABI v25): what
+ * rx_assign would resolve and build for a handle created with *cfg over n_tracks slots of
+ * wp_off[k + 1] - wp_off[k] waypoints (host int32 [n_tracks + 1]) and track_of_env (host
+ * int32 [n_envs]).  rx_assign uploads exactly this plan, so the tables that decide which lane
+ * casts which ray can be checked on the CPU.  Refusals are rx_create's range checks of *cfg
+ * (cfg->device is not looked at) and rx_assign's own (a slot id out of range, more than 16
+ * sensors at ray_order 2), with the same codes and rx_last_error texts; a refused call
+ * writes nothing.  Sizes by cap and count, as rx_ray_waves: the call always writes
+ * n_dyn_waves and n_ray_waves, and nothing else unless schedule, perm, dyn_waves and
+ * ray_waves are set and the two caps suffice. */
+typedef struct {
+  int32_t dyn_cap, ray_cap;         /* in: records that dyn_waves / ray_waves can hold */
+  int32_t n_dyn_waves, n_ray_waves; /* out: the tables' lengths */
+  int32_t sort_bins, sort_shift;    /* out: as rx_env_order reports them (0 bins = no re-sort) */
+  int32_t* schedule;                /* [RX_SCHEDULE_W], rx_schedule's layout; dynamics launches so far = 0 */
+  int32_t* perm;                    /* [n_envs] the env order before any re-sort (rx_env_order) */
+  int32_t* dyn_waves;               /* [dyn_cap][4] (track slot or -1 = lane-varying, perm start, 0, env count) */
+  int32_t* ray_waves;               /* [ray_cap][4] as rx_ray_waves */
+  /* optional, NULL = not wanted: */
+  int32_t* slot_n;                  /* [n_tracks] envs per slot (the ray-major decode's stride) */
+  int32_t* pos_slot;                /* [n_envs] lane-varying schedules: the slot at each position, */
+  int32_t* env_pos;                 /* [n_envs] and the position of each env; otherwise left as they are */
+  int32_t* sort_base;               /* [n_tracks] with sort_bins > 0: the first bin of each slot */
+} rx_assign_plan_io;
+int rx_assign_plan(const rx_config* cfg, int32_t n_tracks, const int32_t* wp_off, const int32_t* track_of_env,
+                   rx_assign_plan_io* io);
+
 /* Bind the caller-owned device state (pointers are kept until re-bound).
  * Once both rx_bind_state and rx_assign have run, the engine copies the bound
  * arrays into its working copy (blocking). */

@@ -42,10 +42,15 @@ int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(RX_EHIP, "%s: %s", #call, hipGetErrorString(e_)); \
   } while (0)
 
+// a device allocation that frees itself (on the current device: rx_destroy sets the handle's)
 template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   void release() {
     if (p) (void)hipFree(p);
     p = nullptr;
@@ -76,6 +81,8 @@ int upload(DevBuf<T>& b, const T* host, size_t n) {
 }
 
 }  // namespace
+
+#define RX_WORK_ARRAYS 14  // device arrays of one working rx_state (rx_bind_state)
 
 struct rx_env {
   rx_config cfg{};
@@ -110,20 +117,11 @@ struct rx_env {
   int64_t* draw_cursor = nullptr;
   DevBuf<int32_t> draw_rank, draw_tmp;
   DevBuf<int64_t> draw_base;
-  int32_t n_dyn_waves = 0, n_ray_waves = 0;
-  int32_t dyn_lpe = 1;
-  int32_t ray_lpr = 1;  // lanes per ray task (ray_order 2, not wide): 64 / ray_lpr tasks a ray wave
-  int32_t reward_lpe = 1;  // split step, single-agent: lanes per env in k_step2's REWARD half
-  int32_t argmin_window = 2;
-  int32_t ray_dispatch = RX_RAY_DISPATCH;  // resolved class order of the ray-wave table (rx_config.ray_dispatch)
-  int32_t ray_tail = 0, ray_tail_lpr = 2;  // tail classes cast at ray_tail_lpr lanes per ray (0 = none)
-  int32_t task_sort = 1;                   // ray-task direction sort every task_sort dynamics launches
-  int32_t lane_tracks = 0;                 // lane-varying slots (rx_config.lane_tracks, rx_assign's choice)
+  rx_sched sched;  // the schedule the assignment resolved (rx_assign_plan.h): written whole, after the last upload
   DevBuf<int32_t> pos_slot;                // with lane_tracks: [N] slot of the env at each position
   DevBuf<int32_t> env_pos;                 // with lane_tracks: [N] position of each env, the inverse of perm
                                            // (rx_track_episode_step: the episodic draw rewrites pos_slot)
   DevBuf<uint8_t> policy_frag;  // the bf16 rollout's operand fragments of both trunks (k_policy_frag, rx_rollout_steps)
-  int32_t ray_tail_from = -1;              // first ray wave of the tail (-1 = none)
   DevBuf<double> rel_angles;
   std::vector<double> rel_angles_h;
   // spatial sort (scheduling only)
@@ -133,8 +131,6 @@ struct rx_env {
   bool sort_hist_done = false;           // the REWARD half of the keys' launch also counted the bins
   DevBuf<uint32_t> sort_hist, sort_cursor;  // [sort_bins]
   DevBuf<int32_t> sort_base;             // [n_tracks] first bin of each slot
-  int32_t sort_bins = 0, sort_shift = 0;
-  bool sort_on = false;
   uint64_t dyn_calls = 0;
   // ray-task direction sort (ray_order 2): every RX_TASK_SORT_INTERVAL dynamics
   // launches, and always on the first launch after a block's membership changed
@@ -142,9 +138,8 @@ struct rx_env {
   uint64_t task_calls = 0;
   // ray_order 2: direction-sorted (agent, ray) task ids, rewritten by k_dyn every step
   DevBuf<int32_t> tasks;
-  // split step (k_kin1 + k_step2): cos / sin of the stepped angles; RX_SPLIT=0 disables
+  // split step (k_kin1 + k_step2): cos / sin of the stepped angles
   DevBuf<double> cs_scratch;
-  bool split = true;
   // rx_steps' carrying schedule: rings of snapshots of what the ray waves read -- the stepped
   // pose ([3][N] x, y, angle) and the sorted task ids -- written by a step's KIN part, and a
   // shadow of the obs rows for every ray step of a launch but its newest, which would write
@@ -165,7 +160,7 @@ struct rx_env {
   bool bound = false;
   rx_state st{};
   rx_state work{}, work_tmp{};
-  std::vector<void*> work_mem;
+  DevBuf<uint8_t> work_mem[2 * RX_WORK_ARRAYS];  // the arrays of work and work_tmp
 };
 
 namespace {
@@ -279,46 +274,9 @@ int rx_abi_version(void) { return RX_ABI_VERSION; }
 int rx_create(const rx_config* cfg, rx_env** out) {
   if (!cfg || !out) return fail(RX_EINVAL, "rx_create: null argument");
   *out = nullptr;
-  if (cfg->n_envs <= 0) return fail(RX_EINVAL, "n_envs must be > 0 (got %d)", cfg->n_envs);
-  if (cfg->n_agents != 1 && cfg->n_agents != 2) return fail(RX_EINVAL, "n_agents must be 1 or 2 (got %d)", cfg->n_agents);
-  if (cfg->n_sensors <= 0 || cfg->n_sensors > 256) return fail(RX_EINVAL, "n_sensors out of range (%d)", cfg->n_sensors);
-  if (cfg->max_steps <= 0) return fail(RX_EINVAL, "max_steps must be > 0");
-  if (cfg->ray_order < 0 || cfg->ray_order > 2)
-    return fail(RX_EINVAL, "ray_order must be 0, 1 or 2 (got %d)", cfg->ray_order);
-  if (cfg->cull_super < 0 || cfg->cull_super > 64) return fail(RX_EINVAL, "cull_super out of range (%d)", cfg->cull_super);
-  if (cfg->autoreset < RX_AUTORESET_NEXT_STEP || cfg->autoreset > RX_AUTORESET_DISABLED)
-    return fail(RX_EINVAL, "bad autoreset mode %d", cfg->autoreset);
-  // launch schedule (ABI v17): 0 = auto, -1 = off where there is an off state
-  auto tri = [](int32_t v) { return v == 0 || v == 1 || v == -1; };
-  auto lanes = [](int32_t v, bool wide) { return v == 0 || v == 1 || v == 2 || v == 4 || (wide && v == 64); };
-  if (!tri(cfg->split)) return fail(RX_EINVAL, "split must be 0 (auto), 1 or -1 (got %d)", cfg->split);
-  if (!tri(cfg->seg_filter)) return fail(RX_EINVAL, "seg_filter must be 0 (auto), 1 or -1 (got %d)", cfg->seg_filter);
-  if (!tri(cfg->box_quadrants))
-    return fail(RX_EINVAL, "box_quadrants must be 0 (auto), 1 or -1 (got %d)", cfg->box_quadrants);
-  if (cfg->wide_n < -1) return fail(RX_EINVAL, "wide_n must be >= -1 (got %d)", cfg->wide_n);
-  if (!lanes(cfg->dyn_lpe, true)) return fail(RX_EINVAL, "dyn_lpe must be 0 (auto), 1, 2, 4 or 64 (got %d)", cfg->dyn_lpe);
-  if (!lanes(cfg->ray_lpr, false)) return fail(RX_EINVAL, "ray_lpr must be 0 (auto), 1, 2 or 4 (got %d)", cfg->ray_lpr);
-  if (!lanes(cfg->reward_lpe, false))
-    return fail(RX_EINVAL, "reward_lpe must be 0 (auto), 1, 2 or 4 (got %d)", cfg->reward_lpe);
-  if (cfg->argmin_window < -1 || cfg->argmin_window > 32)
-    return fail(RX_EINVAL, "argmin_window must be 0 (auto), -1 (none) or 1 .. 32 (got %d)", cfg->argmin_window);
-  if (cfg->ray_dispatch < -1 || cfg->ray_dispatch > 3)
-    return fail(RX_EINVAL, "ray_dispatch must be 0 (auto), -1, 1, 2 or 3 (got %d)", cfg->ray_dispatch);
-  if (cfg->ray_tail < -1 || cfg->ray_tail > 16)
-    return fail(RX_EINVAL, "ray_tail must be 0 (auto), -1 (none) or 1 .. 16 (got %d)", cfg->ray_tail);
-  if (cfg->ray_tail_lpr != 0 && cfg->ray_tail_lpr != 2 && cfg->ray_tail_lpr != 4)
-    return fail(RX_EINVAL, "ray_tail_lpr must be 0 (auto), 2 or 4 (got %d)", cfg->ray_tail_lpr);
-  if (cfg->lane_tracks < -1 || cfg->lane_tracks > 1)
-    return fail(RX_EINVAL, "lane_tracks must be 0 (auto), 1 or -1 (got %d)", cfg->lane_tracks);
-  if (cfg->reserved0 != 0)
-    return fail(RX_EINVAL, "reserved0 must be 0 (ABI v23 dropped the kin_sort schedule; got %d)", cfg->reserved0);
-  if (cfg->task_sort < 0 || cfg->task_sort > 16)
-    return fail(RX_EINVAL, "task_sort must be 0 (auto) or 1 .. 16 (got %d)", cfg->task_sort);
-  if (cfg->n_agents == 2 && (cfg->dyn_lpe > 1 || cfg->reward_lpe > 2))
-    return fail(RX_EINVAL, "n_agents = 2: dyn_lpe > 1 is a single-agent schedule, and reward_lpe is 1 or 2 "
-                           "(a lane per car)");
-  if ((long long)cfg->n_envs * cfg->n_agents * cfg->n_sensors > 0x7fffffffLL)
-    return fail(RX_EINVAL, "n_envs * n_agents * n_sensors overflows int32");
+  std::string err;
+  int rc = rx_config_check(cfg, &err);  // the ranges (rx_assign_plan_host.cpp), before any device call
+  if (rc) return fail(rc, "%s", err.c_str());
   int ndev = 0;
   RX_HIP(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail(RX_EINVAL, "device %d not present (%d devices)", cfg->device, ndev);
@@ -344,7 +302,7 @@ int rx_create(const rx_config* cfg, rx_env** out) {
       rel[n - 1] = stop;
     }
     h->rel_angles_h = rel;
-    int rc = upload(h->rel_angles, rel.data(), rel.size());
+    rc = upload(h->rel_angles, rel.data(), rel.size());
     if (rc) {
       delete h;
       return rc;
@@ -366,69 +324,29 @@ int rx_env_order(rx_env* h, int32_t* perm_out, int32_t* sort_bins, int32_t* sort
   RX_HIP(hipSetDevice(h->cfg.device));
   RX_HIP(hipDeviceSynchronize());
   RX_HIP(hipMemcpy(perm_out, h->perm[0].p, (size_t)h->cfg.n_envs * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (sort_bins) *sort_bins = h->sort_on ? h->sort_bins : 0;
-  if (sort_shift) *sort_shift = h->sort_shift;
+  if (sort_bins) *sort_bins = h->sched.sort_on ? h->sched.sort_bins : 0;
+  if (sort_shift) *sort_shift = h->sched.sort_shift;
   return RX_OK;
 }
 
 // the split step applies (k_kin + k_step2): STEP mode, next-step or no autoreset,
 // single-agent envs at one lane per env
 static bool split_step(const rx_env* h, int mode) {
-  return h->split && mode == RX_MODE_STEP && (h->cfg.n_agents == 2 || h->dyn_lpe == 1) &&
+  return h->sched.split && mode == RX_MODE_STEP && (h->cfg.n_agents == 2 || h->sched.dyn_lpe == 1) &&
          h->cfg.autoreset != RX_AUTORESET_SAME_STEP && h->cs_scratch.p;
 }
 
 int rx_schedule(const rx_env* h, int32_t* out) {
   if (!h || !out) return fail(RX_EINVAL, "rx_schedule: null argument");
   if (!h->assigned) return fail(RX_ESTATE, "rx_schedule before rx_assign");
-  const int32_t v[RX_SCHEDULE_W] = {h->split ? 1 : 0, h->dyn_lpe == 64 ? 1 : 0, h->dyn_lpe, h->ray_lpr, h->reward_lpe,
-                                    h->argmin_window, h->cfg.seg_filter >= 0 ? 1 : 0,
-                                    h->cfg.box_quadrants >= 0 ? 1 : 0, h->n_dyn_waves, h->n_ray_waves,
-                                    h->ray_dispatch, h->ray_tail, h->ray_tail_lpr, h->ray_tail_from,
-                                    h->task_sort, h->lane_tracks, (int32_t)h->dyn_calls, 0};
-  std::copy(v, v + RX_SCHEDULE_W, out);
+  rx_sched_row(h->cfg, h->sched, (int32_t)h->dyn_calls, out);
   return RX_OK;
 }
 
 int rx_destroy(rx_env* h) {
   if (!h) return RX_OK;
   (void)hipSetDevice(h->cfg.device);
-  for (auto* b : {&h->wp, &h->nrm, &h->seg, &h->meta, &h->chunk_box, &h->slot_geo, &h->wchunk_box, &h->super_box,
-                  &h->wsuper_box, &h->rel_angles})
-    b->release();
-  for (auto* b : {&h->wp_off, &h->chunk_off, &h->wchunk_off, &h->super_off, &h->wsuper_off, &h->perm[0], &h->perm[1],
-                  &h->slot_n, &h->tasks})
-    b->release();
-  h->cs_scratch.release();
-  for (int b = 0; b < RX_PAIR_RING; ++b) h->snap_pose[b].release();
-  for (int b = 0; b < RX_TASK_RING; ++b) h->snap_tasks[b].release();
-  for (int b = 0; b < RX_SHADOW_ROWS; ++b) h->obs_shadow[b].release();
-  for (int b = 0; b < RX_CROSS_RING; ++b) {
-    h->snap_rows[b].release();
-    h->snap_hint[b].release();
-  }
-  h->policy_frag.release();
-  h->pos_slot.release();
-  h->env_pos.release();
-  h->prof_buf.release();
-  h->resets.release();
-  h->draw_rank.release();
-  h->draw_tmp.release();
-  h->draw_base.release();
-  h->chunk_box_f.release();
-  h->super_box_f.release();
-  h->seg_f.release();
-  h->slot_hdr.release();
-  h->dyn_waves.release();
-  h->ray_waves.release();
-  for (void* m : h->work_mem) (void)hipFree(m);
-  h->work_mem.clear();
-  h->keys_in.release();
-  h->keys_off.release();
-  h->sort_hist.release();
-  h->sort_cursor.release();
-  h->sort_base.release();
-  delete h;
+  delete h;  // every buffer is a DevBuf member: it frees itself
   return RX_OK;
 }
 
@@ -464,230 +382,41 @@ int rx_upload_tracks(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const d
 
 static int sync_state(rx_env* h, int to_user, void* stream = nullptr, bool blocking = true);
 
+// check -> plan -> upload -> commit.  The plan (rx_plan_assignment, host only) is computed into
+// locals; a refusal returns with the handle as it was.  `assigned` is cleared before the first
+// upload and the schedule is written only after the last, so a failed upload leaves a handle that
+// refuses to step, not one with new lane counts beside old wave tables.  upload keeps a large
+// enough buffer at its address (captured graphs and rx_replace_tracks_device rely on it).
 int rx_assign(rx_env* h, const int32_t* track_of_env) {
   if (!h) return fail(RX_EINVAL, "null handle");
   if (h->n_tracks <= 0) return fail(RX_ESTATE, "rx_assign before rx_upload_tracks");
   if (!track_of_env) return fail(RX_EINVAL, "track_of_env is null");
   const int N = h->cfg.n_envs, A = h->cfg.n_agents, R = h->cfg.n_sensors;
-  for (int e = 0; e < N; ++e)
-    if (track_of_env[e] < 0 || track_of_env[e] >= h->n_tracks)
-      return fail(RX_EINVAL, "env %d assigned to track %d (have %d)", e, track_of_env[e], h->n_tracks);
-  // group envs by slot (stable: env order inside a slot is preserved)
-  std::vector<int32_t> perm(N);
-  std::iota(perm.begin(), perm.end(), 0);
-  std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return track_of_env[a] < track_of_env[b]; });
-  std::vector<rx_wave> dyn, ray;
-  std::vector<int> ray_groups;  // end index (in ray) of each 64-env block's waves
-  if (h->cfg.ray_order == 2 && A * R > 16 * A)
-    return fail(RX_EINVAL, "ray_order 2 supports at most 16 sensors (got %d)", R);
-  // launch schedule (rx_config ABI v17 fields; 0 = the measured default for N)
-  const rx_config& c = h->cfg;
-  h->dyn_lpe = (A == 1 && N <= RX_DYN1_SMALL_N) ? RX_DYN1_LPE_SMALL : 1;
-  const int wide_n = c.wide_n == 0 ? RX_WIDE_N : c.wide_n;  // -1: never
-  if (A == 1 && N <= wide_n) h->dyn_lpe = 64;
-  if (A == 1 && c.dyn_lpe != 0) h->dyn_lpe = c.dyn_lpe;
-  h->argmin_window = c.argmin_window == 0 ? 2 : (c.argmin_window < 0 ? 0 : c.argmin_window);
-  {  // the window [prev - H, prev + H] is wrapped into [0, W) by one +-W: needs H <= W of every slot
-    int min_w = 1 << 30;
-    for (int k = 0; k < h->n_tracks; ++k) min_w = std::min(min_w, h->wp_off_h[k + 1] - h->wp_off_h[k]);
-    h->argmin_window = std::min(h->argmin_window, min_w);
-  }
-  // few envs: the culled raycast is a latency chain over too few waves to
-  // fill the chip, so 2 or 4 lanes share one ray and split its leaves
-  h->ray_lpr = 1;
-  if (h->cfg.ray_order == 2 && h->dyn_lpe != 64) {
-    const long long pairs = (long long)N * A, lpr2_n = A == 2 ? RX_RAY2_LPR2_N : RX_RAY_LPR2_N;
-    h->ray_lpr = pairs <= RX_RAY_LPR4_N ? 4 : (pairs <= lpr2_n ? 2 : 1);
-    if (c.ray_lpr != 0) h->ray_lpr = c.ray_lpr;
-  }
-  // few single-agent envs: REWARD (a latency chain of argmins) outlasts the
-  // raycast beside it in k_step2 unless 2 lanes share an env's five points
-  h->reward_lpe = (A == 1 && N <= RX_REWARD_LPE2_N) || (A == 2 && N <= RX_REWARD2_LPE2_N) ? 2 : 1;
-  if (c.reward_lpe != 0) h->reward_lpe = c.reward_lpe;
-  h->split = c.split >= 0;
-  // ray-wave class order and the tail split (ABI v19; scheduling only)
-  h->ray_dispatch = c.ray_dispatch == 0 ? RX_RAY_DISPATCH : (c.ray_dispatch < 0 ? 0 : c.ray_dispatch);
-  h->ray_tail_lpr = c.ray_tail_lpr == 0 ? RX_RAY_TAIL_LPR : c.ray_tail_lpr;
-  // few (env, car) pairs: the ray waves are short and the sort is up to 40 % of
-  // k_kin's wave, so every other launch keeps the previous task order
-  h->task_sort = c.task_sort != 0 ? c.task_sort : ((long long)N * A <= RX_TASK_SORT2_PAIRS ? 2 : 1);
-  h->ray_tail = c.ray_tail == 0 ? RX_RAY_TAIL : (c.ray_tail < 0 ? 0 : c.ray_tail);
-  if (h->cfg.ray_order != 2 || h->ray_lpr != 1 || h->ray_dispatch == 0 || h->dyn_lpe == 64) h->ray_tail = 0;
-  h->ray_tail_from = -1;
-  std::vector<int32_t> slot_n(h->n_tracks, 0);
-  for (int e = 0; e < N; ++e) ++slot_n[track_of_env[e]];
-  // Lane-varying track slots (ABI v23): grouping envs by slot gives every slot
-  // ceil(n_k / 64) dynamics waves; with many distinct slots (gen_tracks(N, seed=None): one env
-  // each) those waves hold a lane or two.  Auto rule: take waves of 64 consecutive positions of
-  // ANY slots (per-lane track loads) when the grouping would need more than twice ceil(N / 64)
-  // waves.  Single-agent envs at one lane per env (the split step or the one-kernel k_dyn1<1>);
-  // it implies one lane per ray and per REWARD env and no ray-task sort or spatial re-sort.
-  {
-    long long grouped = 0;
-    for (int k = 0; k < h->n_tracks; ++k) grouped += (slot_n[k] + 63) / 64;
-    const long long full = (N + 63) / 64;
-    const bool can = A == 1 && h->dyn_lpe == 1;
-    h->lane_tracks = can && c.lane_tracks >= 0 && (c.lane_tracks == 1 || grouped > 2 * full) ? 1 : 0;
-  }
-  if (h->lane_tracks) {
-    h->ray_lpr = 1;
-    h->reward_lpe = 1;
-    h->ray_dispatch = 0;
-    h->ray_tail = 0;
-  }
-  const int tpw = 64 / h->ray_lpr;  // ray tasks per wave
-  int g0 = h->lane_tracks ? N : 0;
-  for (int ps = 0; h->lane_tracks && ps < N; ps += 64) {  // 64 consecutive positions, (env, agent, ray) tasks
-    const int cnt = std::min(64, N - ps), nt = cnt * A * R;
-    dyn.push_back(rx_wave{-1, ps, 0, cnt});
-    for (int j = 0; j < nt; j += 64) ray.push_back(rx_wave{-1, ps, j, std::min(64, nt - j)});
-    ray_groups.push_back((int)ray.size());
-  }
-  while (g0 < N) {
-    const int k = track_of_env[perm[g0]];
-    int g1 = g0;
-    while (g1 < N && track_of_env[perm[g1]] == k) ++g1;
-    const int ng = g1 - g0;
-    const int epw = A == 1 ? 64 / h->dyn_lpe : 64;  // envs per dynamics wave
-    for (int s = 0; s < ng; s += epw) dyn.push_back(rx_wave{k, g0 + s, 0, std::min(epw, ng - s)});
-    if (h->cfg.ray_order == 2) {  // per dynamics wave: its envs' A*R tasks (direction-sorted by k_dyn), tpw a wave
-      for (int s = 0; s < ng; s += epw) {
-        const int cnt = std::min(epw, ng - s), nt = cnt * A * R, ps = g0 + s;
-        for (int j = 0; j < nt; j += tpw) ray.push_back(rx_wave{k, ps, ps * A * R + j, std::min(tpw, nt - j)});
-        ray_groups.push_back((int)ray.size());
-      }
-    } else if (h->cfg.ray_order == 0) {
-      const long long tasks = (long long)ng * A * R;
-      for (long long s = 0; s < tasks; s += 64)
-        ray.push_back(rx_wave{k, g0, (int32_t)s, (int32_t)std::min<long long>(64, tasks - s)});
-    } else {  // ray-major: one (agent, ray) x one 64-env block per wave, grouped by block
-      for (int b = 0; 64 * b < ng; ++b) {
-        for (int qr = 0; qr < A * R; ++qr)
-          ray.push_back(rx_wave{k, g0, qr * ng + 64 * b, std::min(64, ng - 64 * b)});
-        ray_groups.push_back((int)ray.size());
-      }
-    }
-    g0 = g1;
-  }
-  if (h->cfg.ray_order >= 1 || h->lane_tracks) {
-    // XCD-aware placement: workgroups are dealt round-robin over the 8 XCDs
-    // (MI355X_MICROARCH.md, workgroup dispatch), and every wave of one 64-env
-    // block writes into the same obs rows, so the (up to) A*R waves of block g
-    // go to physical indices p = ((g / 8) * maxw + j) * 8 + g % 8 -- one XCD,
-    // one L2 to merge their partial-line writes.  Padding waves have count 0.
-    const size_t n_groups = ray_groups.size();
-    int maxw = 0;
-    for (size_t g = 0; g < n_groups; ++g) maxw = std::max(maxw, ray_groups[g] - (g ? ray_groups[g - 1] : 0));
-    const size_t padded = (n_groups + 7) / 8 * 8;
-    // ray_dispatch (rx_config, ABI v19): 0 = group-octet-major as just described; 1..3 =
-    // class-major, every group's class-j wave in one run, the classes in the order
-    // 1 centre first (|2j - (maxw - 1)| ascending), 2 ascending j, 3 edge classes first
-    // (|2j - (maxw - 1)| descending, the default).  The XCD of a group's waves is g % 8 in
-    // every mode (padded is a multiple of 8).  Dispatch order is scheduling only.
-    const int mode = h->ray_dispatch;
-    std::vector<int> rank(maxw);
-    std::iota(rank.begin(), rank.end(), 0);
-    if (mode == 1 || mode == 3) {
-      std::vector<int> cls(maxw);
-      std::iota(cls.begin(), cls.end(), 0);
-      auto off = [&](int j) { return std::abs(2 * j - (maxw - 1)); };
-      std::stable_sort(cls.begin(), cls.end(), [&](int x, int y) { return mode == 1 ? off(x) < off(y) : off(x) > off(y); });
-      for (int r = 0; r < maxw; ++r) rank[cls[r]] = r;
-    }
-#ifdef RX_RAY_ORDER_LIST
-    {  // A/B builds: an explicit class order for 11-class groups (ray_dispatch >= 1)
-      const int lst[] = RX_RAY_ORDER_LIST;
-      if (mode >= 1 && maxw == (int)(sizeof(lst) / sizeof(lst[0]))) {
-        // the list must be a permutation of 0..maxw-1: a repeated class would give two
-        // ray waves one placed slot (one silently overwritten, its rays never cast)
-        std::vector<bool> seen(maxw, false);
-        for (int r = 0; r < maxw; ++r) {
-          if (lst[r] < 0 || lst[r] >= maxw || seen[lst[r]])
-            return fail(RX_EINVAL, "RX_RAY_ORDER_LIST is not a permutation of 0..%d", maxw - 1);
-          seen[lst[r]] = true;
-          rank[lst[r]] = r;
-        }
-      }
-    }
-#endif
-    // The tail split (ray_tail, class-major modes only): the waves of the last ray_tail
-    // ranks run as the chip drains, where a wave's latency chain -- not the shared VALU --
-    // sets its duration.  Each of their 64-task records becomes m = ray_tail_lpr records of
-    // 64 / m tasks, cast at m lanes per ray (the lanes split each scanned leaf: a shorter
-    // chain, the same result, DESIGN.md §3 "Lanes per ray").  Rank r occupies mult[r]
-    // consecutive runs of `padded` slots; sub-record s of group g's rank-r wave goes to
-    // base[r] + (s * (padded / 8) + g / 8) * 8 + g % 8, so it keeps the group's XCD.  All
-    // tail waves sit at the end of the table: ray_tail_from is the first of them.
-    const int tail = mode == 0 ? 0 : std::min(h->ray_tail, maxw);
-    std::vector<size_t> mult(maxw, 1), base(maxw + 1, 0);
-    for (int r = maxw - tail; r < maxw; ++r) mult[r] = (size_t)h->ray_tail_lpr;
-    for (int r = 0; r < maxw; ++r) base[r + 1] = base[r] + mult[r] * padded;
-    std::vector<rx_wave> placed(base[maxw], rx_wave{0, 0, 0, 0});
-    for (size_t g = 0; g < n_groups; ++g) {
-      const int w0 = g ? ray_groups[g - 1] : 0;
-      for (int j = 0; w0 + j < ray_groups[g]; ++j) {
-        const rx_wave w = ray[w0 + j];
-        if (mode == 0) {
-          placed[((g / 8) * maxw + j) * 8 + g % 8] = w;
-          continue;
-        }
-        const int r = rank[j];
-        const int m = (int)mult[r], per = tpw / m;
-        for (int sub = 0; sub < m; ++sub) {
-          const size_t slot = base[r] + ((size_t)sub * (padded / 8) + g / 8) * 8 + g % 8;
-          placed[slot] = rx_wave{w.track, w.perm_start, w.task_start + sub * per,
-                                 std::max(0, std::min(per, w.count - sub * per))};
-        }
-      }
-    }
-    h->ray_tail = tail;
-    h->ray_tail_from = tail > 0 ? (int32_t)base[maxw - tail] : -1;
-    ray.swap(placed);
-  }
+  rx_assignment plan;
+  std::string err;
+  int rc = rx_plan_assignment(h->cfg, h->n_tracks, h->wp_off_h.data(), track_of_env, &plan, &err);
+  if (rc) return fail(rc, "%s", err.c_str());
+  const rx_sched& sc = plan.sched;
   RX_HIP(hipSetDevice(h->cfg.device));
-  int rc;
-  if ((rc = upload(h->slot_n, slot_n.data(), slot_n.size()))) return rc;
-  if ((rc = upload(h->perm[0], perm.data(), perm.size()))) return rc;
-  if ((rc = upload(h->perm[1], perm.data(), perm.size()))) return rc;
+  h->assigned = false;
+  if ((rc = upload(h->slot_n, plan.slot_n.data(), plan.slot_n.size()))) return rc;
+  if ((rc = upload(h->perm[0], plan.perm.data(), plan.perm.size()))) return rc;
+  if ((rc = upload(h->perm[1], plan.perm.data(), plan.perm.size()))) return rc;
   if (A == 2) {
     std::vector<uint32_t> z(N, 0u);
     if ((rc = upload(h->resets, z.data(), z.size()))) return rc;
   }
-  h->sort_on = false;
-  if (h->lane_tracks) {  // the kernels read each position's slot: the order stays fixed
-    std::vector<int32_t> ps(N);
-    for (int p = 0; p < N; ++p) ps[p] = track_of_env[perm[p]];
-    if ((rc = upload(h->pos_slot, ps.data(), ps.size()))) return rc;
-    for (int p = 0; p < N; ++p) ps[perm[p]] = p;
-    if ((rc = upload(h->env_pos, ps.data(), ps.size()))) return rc;
-  } else if (h->cfg.sort_interval > 0) {
-    // spatial sort bins: slot k owns (W_k >> shift) + 1 consecutive bins from
-    // sort_base[k]; the smallest shift that keeps all bins <= RX_SORT_MAX_BINS.
-    // More slots than that (at most ~1 env per slot): nothing to regroup, no sort.
-    int shift = 0;
-    long long total = 0;
-    for (;; ++shift) {
-      total = 0;
-      for (int k = 0; k < h->n_tracks; ++k) total += ((h->wp_off_h[k + 1] - h->wp_off_h[k]) >> shift) + 1;
-      if (total <= RX_SORT_MAX_BINS || shift >= 30) break;
-    }
-    if (total <= RX_SORT_MAX_BINS) {
-      std::vector<int32_t> base(h->n_tracks);
-      int32_t run = 0;
-      for (int k = 0; k < h->n_tracks; ++k) {
-        base[k] = run;
-        run += ((h->wp_off_h[k + 1] - h->wp_off_h[k]) >> shift) + 1;
-      }
-      std::vector<uint32_t> zk(std::max<size_t>((size_t)N, (size_t)total), 0u);
-      if ((rc = upload(h->sort_base, base.data(), base.size()))) return rc;
-      if ((rc = upload(h->keys_in, zk.data(), (size_t)N))) return rc;
-      if ((rc = upload(h->keys_off, zk.data(), (size_t)N))) return rc;
-      if ((rc = upload(h->sort_hist, zk.data(), (size_t)total))) return rc;
-      if ((rc = upload(h->sort_cursor, zk.data(), (size_t)total))) return rc;
-      h->sort_bins = (int32_t)total;
-      h->sort_shift = shift;
-      h->sort_on = true;
-    }
+  if (sc.lane_tracks) {  // the kernels read each position's slot: the order stays fixed
+    if ((rc = upload(h->pos_slot, plan.pos_slot.data(), plan.pos_slot.size()))) return rc;
+    if ((rc = upload(h->env_pos, plan.env_pos.data(), plan.env_pos.size()))) return rc;
+  } else if (sc.sort_on) {  // the spatial re-sort's bins, keys and counters
+    const size_t total = (size_t)sc.sort_bins;
+    std::vector<uint32_t> zk(std::max<size_t>((size_t)N, total), 0u);
+    if ((rc = upload(h->sort_base, plan.sort_base.data(), plan.sort_base.size()))) return rc;
+    if ((rc = upload(h->keys_in, zk.data(), (size_t)N))) return rc;
+    if ((rc = upload(h->keys_off, zk.data(), (size_t)N))) return rc;
+    if ((rc = upload(h->sort_hist, zk.data(), total))) return rc;
+    if ((rc = upload(h->sort_cursor, zk.data(), total))) return rc;
   }
   if (h->cfg.ray_order == 2) {  // task ids before the first sort: position-major, (agent, ray) minor -- a valid order
     const size_t nt = (size_t)N * A * R;
@@ -710,28 +439,58 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
       if ((rc = upload(h->snap_tasks[b], zi.data(), zi.size()))) return rc;
     for (int b = 0; b < RX_SHADOW_ROWS; ++b)
       if ((rc = upload(h->obs_shadow[b], zf.data(), zf.size()))) return rc;
-    for (int b = 0; b < RX_CROSS_RING && RX_STEPS_CROSS && h->sort_on; ++b) {  // the crossing step's
+    for (int b = 0; b < RX_CROSS_RING && RX_STEPS_CROSS && sc.sort_on; ++b) {  // the crossing step's
       if ((rc = upload(h->snap_rows[b], zi.data(), (size_t)N))) return rc;
       if ((rc = upload(h->snap_hint[b], zd.data(), (size_t)N))) return rc;
     }
   }
-  if ((rc = upload(h->dyn_waves, dyn.data(), dyn.size()))) return rc;
-  if ((rc = upload(h->ray_waves, ray.data(), ray.size()))) return rc;
-  h->ray_waves_h = ray;
-  h->n_dyn_waves = (int32_t)dyn.size();
-  h->n_ray_waves = (int32_t)ray.size();
+  if ((rc = upload(h->dyn_waves, plan.dyn.data(), plan.dyn.size()))) return rc;
+  if ((rc = upload(h->ray_waves, plan.ray.data(), plan.ray.size()))) return rc;
   if (!h->policy_frag.p) {  // allocated here, not in rx_rollout_steps: it may run inside a graph capture
     RX_HIP(hipSetDevice(h->cfg.device));
     if (hipMalloc(&h->policy_frag.p, rx_policy_frag_bytes()) != hipSuccess)
       return fail(RX_ENOMEM, "rx_assign: policy fragment image");
     h->policy_frag.n = rx_policy_frag_bytes();
   }
+  h->ray_waves_h.swap(plan.ray);
+  h->sched = sc;
   h->assigned = true;
   h->tasks_stale = true;
   h->sort_pending = false;
   h->sort_hist_done = false;  // the histogram was re-uploaded as zeros above (or sorting is off)
   if (h->bound && h->st.track) RX_HIP(hipMemcpy(h->st.track, track_of_env, N * sizeof(int32_t), hipMemcpyHostToDevice));
   if (h->bound) return sync_state(h, 0);  // the new wave order: re-read the caller's arrays
+  return RX_OK;
+}
+
+int rx_assign_plan(const rx_config* cfg, int32_t n_tracks, const int32_t* wp_off, const int32_t* track_of_env,
+                   rx_assign_plan_io* io) {
+  if (!cfg || !wp_off || !track_of_env || !io) return fail(RX_EINVAL, "rx_assign_plan: null argument");
+  if (n_tracks <= 0) return fail(RX_EINVAL, "rx_assign_plan: n_tracks must be > 0 (got %d)", n_tracks);
+  for (int k = 0; k < n_tracks; ++k)
+    if (wp_off[k + 1] - wp_off[k] < 2)
+      return fail(RX_EINVAL, "track %d has %d waypoints (need >= 2)", k, wp_off[k + 1] - wp_off[k]);
+  rx_assignment plan;
+  std::string err;
+  const int rc = rx_plan_assignment(*cfg, n_tracks, wp_off, track_of_env, &plan, &err);
+  if (rc) return fail(rc, "%s", err.c_str());
+  const rx_sched& sc = plan.sched;
+  const bool room = io->schedule && io->perm && io->dyn_waves && io->ray_waves && io->dyn_cap >= sc.n_dyn_waves &&
+                    io->ray_cap >= sc.n_ray_waves;
+  io->n_dyn_waves = sc.n_dyn_waves;
+  io->n_ray_waves = sc.n_ray_waves;
+  if (!room) return RX_OK;  // the sizes only
+  rx_sched_row(*cfg, sc, 0, io->schedule);
+  std::copy(plan.perm.begin(), plan.perm.end(), io->perm);
+  io->sort_bins = sc.sort_bins;
+  io->sort_shift = sc.sort_shift;
+  static_assert(sizeof(rx_wave) == 4 * sizeof(int32_t), "wave records are int32 [4]");
+  if (!plan.dyn.empty()) memcpy(io->dyn_waves, plan.dyn.data(), plan.dyn.size() * sizeof(rx_wave));
+  if (!plan.ray.empty()) memcpy(io->ray_waves, plan.ray.data(), plan.ray.size() * sizeof(rx_wave));
+  if (io->slot_n) std::copy(plan.slot_n.begin(), plan.slot_n.end(), io->slot_n);
+  if (io->pos_slot) std::copy(plan.pos_slot.begin(), plan.pos_slot.end(), io->pos_slot);
+  if (io->env_pos) std::copy(plan.env_pos.begin(), plan.env_pos.end(), io->env_pos);
+  if (io->sort_base) std::copy(plan.sort_base.begin(), plan.sort_base.end(), io->sort_base);
   return RX_OK;
 }
 
@@ -758,13 +517,17 @@ int rx_bind_state(rx_env* h, const rx_state* st) {
   h->st = *st;
   if (!h->work.x) {  // working copy + shadow, same shapes as the caller's arrays
     const size_t N = (size_t)h->cfg.n_envs, NA = N * (size_t)h->cfg.n_agents;
+    int used = 0;  // RX_WORK_ARRAYS arrays per state
     for (rx_state* w : {&h->work, &h->work_tmp}) {
       auto alloc = [&](auto** ptr, size_t bytes) -> int {
-        void* m = nullptr;
-        if (hipMalloc(&m, std::max<size_t>(bytes, 16)) != hipSuccess) return fail(RX_ENOMEM, "working state alloc");
-        RX_HIP(hipMemset(m, 0, std::max<size_t>(bytes, 16)));
-        h->work_mem.push_back(m);
-        *ptr = reinterpret_cast<std::remove_reference_t<decltype(*ptr)>>(m);
+        DevBuf<uint8_t>& m = h->work_mem[used++];
+        if (hipMalloc(&m.p, std::max<size_t>(bytes, 16)) != hipSuccess) {
+          m.p = nullptr;
+          return fail(RX_ENOMEM, "working state alloc");
+        }
+        m.n = std::max<size_t>(bytes, 16);
+        RX_HIP(hipMemset(m.p, 0, m.n));
+        *ptr = reinterpret_cast<std::remove_reference_t<decltype(*ptr)>>(m.p);
         return RX_OK;
       };
       int rc;
@@ -805,7 +568,7 @@ int rx_set_speed_weight(rx_env* h, double w) {
 static constexpr int kProfMax = 512;  // launches per record
 static int prof_stride(const rx_env* h) {
   const int wide = h->cfg.n_envs * h->cfg.n_agents * h->cfg.n_sensors;  // k_rays_wide: one wave per ray
-  return std::max(h->reward_lpe * ((h->n_dyn_waves + 7) / 8 * 8) + h->n_ray_waves, wide) + 8;
+  return std::max(h->sched.reward_lpe * ((h->sched.n_dyn_waves + 7) / 8 * 8) + h->sched.n_ray_waves, wide) + 8;
 }
 static void prof_arm(rx_env* h, rx_kargs& a, int kind) {
   a.prof_ts = nullptr;
@@ -830,8 +593,8 @@ static void make_kargs(rx_env* h, const rx_io* io, int mode, const uint8_t* mask
   a.perm = h->perm[0].p;
   a.rel_angles = h->rel_angles.p;
   a.reset_mask = mask;
-  a.n_dyn_waves = h->n_dyn_waves;
-  a.n_ray_waves = h->n_ray_waves;
+  a.n_dyn_waves = h->sched.n_dyn_waves;
+  a.n_ray_waves = h->sched.n_ray_waves;
   a.n_sensors = h->cfg.n_sensors;
   a.D = h->D;
   a.max_steps = h->cfg.max_steps;
@@ -843,26 +606,26 @@ static void make_kargs(rx_env* h, const rx_io* io, int mode, const uint8_t* mask
   a.seed = h->cfg.seed;
   a.reset_count = h->resets.p;
   a.ray_order = h->cfg.ray_order;
-  a.dyn_lpe = h->dyn_lpe;
-  a.ray_lpr = h->ray_lpr;
-  a.ray_tail_from = h->ray_tail_from;
-  a.ray_tail_lpr = h->ray_tail_lpr;
-  a.reward_lpe = h->reward_lpe;
-  a.argmin_window = h->argmin_window;
+  a.dyn_lpe = h->sched.dyn_lpe;
+  a.ray_lpr = h->sched.ray_lpr;
+  a.ray_tail_from = h->sched.ray_tail_from;
+  a.ray_tail_lpr = h->sched.ray_tail_lpr;
+  a.reward_lpe = h->sched.reward_lpe;
+  a.argmin_window = h->sched.argmin_window;
   a.slot_nenv = h->slot_n.p;
-  a.wide = h->dyn_lpe == 64;
+  a.wide = h->sched.dyn_lpe == 64;
   a.n_wide_tasks = h->cfg.n_envs * h->cfg.n_agents * h->cfg.n_sensors;
   a.tasks = h->tasks.p;
-  a.tasks_out = (h->cfg.ray_order == 2 && !a.wide && !h->lane_tracks) ? h->tasks.p : nullptr;
-  a.lane_tracks = h->lane_tracks;
-  a.pos_slot = h->lane_tracks ? h->pos_slot.p : nullptr;
+  a.tasks_out = (h->cfg.ray_order == 2 && !a.wide && !h->sched.lane_tracks) ? h->tasks.p : nullptr;
+  a.lane_tracks = h->sched.lane_tracks;
+  a.pos_slot = h->sched.lane_tracks ? h->pos_slot.p : nullptr;
   a.cs_scratch = h->cs_scratch.p;
   a.ray_x = a.st.x;  // the ray inputs: the working state (rx_steps' carrying launches: a snapshot)
   a.ray_y = a.st.y;
   a.ray_angle = a.st.angle;
   a.ray_hint = a.st.progress;  // (a crossing step of rx_steps: the hint snapshot)
   a.sort_base = h->sort_base.p;
-  a.sort_shift = h->sort_shift;
+  a.sort_shift = h->sched.sort_shift;
   a.box_quadrants = h->cfg.box_quadrants >= 0;
   a.seg_filter = h->cfg.seg_filter >= 0;
 #ifdef RX_AB_NO_EPSTATS  // A/B build only (tools/build_rev.py): drop the episode-statistics atomics
@@ -876,7 +639,7 @@ static void make_kargs(rx_env* h, const rx_io* io, int mode, const uint8_t* mask
 // part may reuse the previous one's while the blocks hold the same envs.  Does the next KIN
 // part sort its ray tasks?  (Asked only where tasks_out is non-null.)
 static bool task_sort_due(const rx_env* h) {
-  return h->tasks_stale || (h->task_calls % (uint64_t)h->task_sort) == 0;
+  return h->tasks_stale || (h->task_calls % (uint64_t)h->sched.task_sort) == 0;
 }
 // ... and the same for the KIN part being armed now, which takes its turn
 static bool take_task_sort_turn(rx_env* h) {
@@ -887,7 +650,7 @@ static bool take_task_sort_turn(rx_env* h) {
 }
 // Spatial re-sort, every sort_interval dynamics launches (dyn_calls counts them only while
 // the re-sort is on): is it due `ahead` dynamics launches from now?
-static bool resort_on(const rx_env* h) { return h->cfg.sort_interval > 0 && h->sort_on; }
+static bool resort_on(const rx_env* h) { return h->cfg.sort_interval > 0 && h->sched.sort_on; }
 static bool resort_due(const rx_env* h, int32_t ahead) {
   return resort_on(h) && ((h->dyn_calls + ahead) % h->cfg.sort_interval) == 0;
 }
@@ -899,7 +662,7 @@ static bool resort_due(const rx_env* h, int32_t ahead) {
 // in between): clear it, so the fused count, or k_sort_hist, starts from zero.
 static int arm_sort_keys(rx_env* h, rx_kargs& a, bool hist, hipStream_t s) {
   if (h->sort_hist_done) {
-    RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sort_bins * sizeof(uint32_t), s));
+    RX_HIP(hipMemsetAsync(h->sort_hist.p, 0, (size_t)h->sched.sort_bins * sizeof(uint32_t), s));
     h->sort_hist_done = false;
   }
   a.sort_keys = h->keys_in.p;
@@ -918,7 +681,7 @@ static int sort_envs_now(rx_env* h, hipStream_t s) {
   h->tasks_stale = true;  // the re-sort moves envs between blocks
   rx_state work = h->work, tmp = h->work_tmp;
   const int rc = rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, h->cfg.n_agents, h->sort_hist.p,
-                              h->sort_cursor.p, h->sort_bins, h->perm[0].p, h->perm[1].p, &work, &tmp, s, hist_done);
+                              h->sort_cursor.p, h->sched.sort_bins, h->perm[0].p, h->perm[1].p, &work, &tmp, s, hist_done);
   if (rc != 0) return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
   return RX_OK;
 }
@@ -1324,9 +1087,9 @@ int32_t rx_steps_plan(rx_plan_args* in, rx_plan_launch* out, int32_t cap) {
 // by rx_step_phases (its keys belong to a step whose rays are not cast yet), and needs
 // rx_assign's snapshot rings and shadow obs rows.  Otherwise rx_steps is K x rx_step.
 static bool steps_carried(const rx_env* h, const rx_io* io) {
-  if (!RX_STEPS_CARRY || !split_step(h, RX_MODE_STEP) || h->cfg.n_agents != 1 || h->reward_lpe != 1) return false;
+  if (!RX_STEPS_CARRY || !split_step(h, RX_MODE_STEP) || h->cfg.n_agents != 1 || h->sched.reward_lpe != 1) return false;
   if (h->prof || io->counters || h->sort_pending) return false;
-  const bool ranks = h->cfg.ray_order == 2 && !h->lane_tracks;
+  const bool ranks = h->cfg.ray_order == 2 && !h->sched.lane_tracks;
   for (int b = 0; b < RX_PAIR_RING; ++b)
     if (!h->snap_pose[b].p) return false;
   for (int b = 0; b < RX_TASK_RING; ++b)
@@ -1353,7 +1116,7 @@ static int steps_pair(rx_env* h, const rx_io* io, const rx_io_strides& st, int32
                      h->snap_hint[RX_CROSS_RING - 1].p;
   const int32_t si = resort_on(h) ? h->cfg.sort_interval : 0;
   rx_plan_args pa{K, 0, si, si ? (int32_t)(h->dyn_calls % (uint64_t)si) : 0,
-                  ranks ? h->task_sort : 0, ranks ? (int32_t)(h->task_calls % (uint64_t)h->task_sort) : 0,
+                  ranks ? h->sched.task_sort : 0, ranks ? (int32_t)(h->task_calls % (uint64_t)h->sched.task_sort) : 0,
                   h->tasks_stale ? 1 : 0, cross ? 1 : 0, -1, 0, 0};  // depth and lag: the planner's choice for K
   std::vector<rx_plan_launch> plan((size_t)3 * K + 8);  // (at most two launches a step and the drains)
   const int32_t n_launch = rx_steps_plan(&pa, plan.data(), (int32_t)plan.size());
@@ -1451,7 +1214,7 @@ static int max_waypoints(const rx_env* h) {
 }
 
 int rx_rollout_supported(const rx_env* h) {
-  return h && h->assigned && h->bound && h->cfg.n_agents == 1 && h->dyn_lpe == 64 && (h->D == 15 || h->D == 19) &&
+  return h && h->assigned && h->bound && h->cfg.n_agents == 1 && h->sched.dyn_lpe == 64 && (h->D == 15 || h->D == 19) &&
          max_waypoints(h) <= RX_ROLLOUT_MAX_W;
 }
 
@@ -1517,7 +1280,7 @@ int rx_rollout(rx_env* h, const rx_io* io, const rx_rollout_io* r, void* stream)
                 RX_ROLLOUT_MAX_W);
   int rc;
   if ((rc = rollout_dims("rx_rollout", h, r)) != 0 || (rc = rollout_bufs("rx_rollout", r)) != 0) return rc;
-  if (h->n_dyn_waves != h->cfg.n_envs) return fail(RX_ESTATE, "rx_rollout: expected one env per dynamics wave");
+  if (h->sched.n_dyn_waves != h->cfg.n_envs) return fail(RX_ESTATE, "rx_rollout: expected one env per dynamics wave");
   rx_kargs a{};
   make_kargs(h, io, RX_MODE_STEP, nullptr, a);
   a.sort_keys = nullptr;
@@ -2676,7 +2439,7 @@ static int track_episode_handle(const char* fn, const rx_env* h, const rx_track_
   if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
   if (!h->assigned || !h->bound || h->cfg.n_agents != 1)
     return fail(RX_EINVAL, "%s: the handle must be an assigned, bound single-agent handle", fn);
-  if (!h->lane_tracks)
+  if (!h->sched.lane_tracks)
     return fail(RX_EINVAL, "%s: the handle's schedule is not lane-varying: set rx_config.lane_tracks = 1 (it needs "
                            "one lane per env: with at most %d envs set dyn_lpe = 1 as well)", fn, RX_WIDE_N);
   if (h->cfg.autoreset != RX_AUTORESET_NEXT_STEP)

@@ -5,20 +5,10 @@
 #include <stdint.h>
 
 #include "rx.h"
+#include "rx_assign_plan.h"  // rx_wave and the schedule thresholds (no HIP: the host-only planner shares them)
 
 #define RX_MODE_STEP 0
 #define RX_MODE_RESET 1
-
-// One wavefront's work item: 64 consecutive tasks of ONE track slot.
-//  dyn waves: lane -> env perm[perm_start + lane], lane < count
-//  ray waves: lane -> task task_start + lane (task = env_local*A*R + agent*R + ray),
-//             env = perm[perm_start + env_local]
-struct rx_wave {
-  int32_t track;
-  int32_t perm_start;
-  int32_t task_start;
-  int32_t count;
-};
 
 // Every per-slot scalar the lane-varying kernels read, in ONE 128-byte record (one
 // cache line per env instead of one per table: the slot's waypoint range, its culling
@@ -63,76 +53,6 @@ struct rx_track_view {
 #ifndef RX_WP_SUPER
 #define RX_WP_SUPER 4  // leaves per waypoint super-chunk
 #endif
-
-// lanes per env in k_dyn1 (a dynamics wave holds 64 / lpe envs): 4 when there
-// are few envs (latency-bound: more lanes per env shorten the chain), 1 when
-// the chip is fuller.  One lane per env also selects the split step (k_kin1 +
-// k_step2: the REWARD half beside the raycast), which beats k_dyn1<4> + k_rays
-// from 4,096 envs on (41.4 vs 52.8 us at 4,096, 42.7 vs 54.3 at 8,192; equal
-// at 2,048, where the wide kernels run anyway: tools/gpu_lpe_ab.sh)
-#define RX_DYN1_LPE_SMALL 4
-#define RX_DYN1_SMALL_N 2048
-// Lanes per ray task (ray_order 2): 4 (16 tasks a ray wave) up to
-// RX_RAY_LPR4_N (env, agent) pairs, 2 up to RX_RAY_LPR2_N, 1 above: with few
-// envs the raycast is a latency chain over too few waves to fill the chip
-// ("Lanes per ray"; crossovers measured on MI355X)
-#ifndef RX_RAY_LPR4_N
-#define RX_RAY_LPR4_N 8192
-#endif
-#ifndef RX_RAY_LPR2_N
-#define RX_RAY_LPR2_N 16384
-#endif
-// k_step2<1>'s REWARD half at 2 lanes per env up to this many envs (it is the
-// launch's critical path there once the raycast runs at 4 lanes per ray;
-// from 8,192 envs on it only slows the raycast beside it)
-#ifndef RX_REWARD_LPE2_N
-#define RX_REWARD_LPE2_N 4096
-#endif
-// two-car envs: k_step2<2>'s REWARD half with a lane per car (one closest-waypoint
-// pass per wave instead of two) up to this many envs.  Same-session A/B
-// (profiles/r04/ab_two_car_*.jsonl): 4,096 envs 67.2 -> 79.2 M env-steps/s,
-// 8,192 128.1 -> 134.7 M (with one lane per ray), 16,384 213.2 -> 220.3 M,
-// 65,536 389 -> 387 M (off there)
-#ifndef RX_REWARD2_LPE2_N
-#define RX_REWARD2_LPE2_N 16384
-#endif
-// two-car envs: 2 lanes per ray only up to this many (env, car) pairs (the
-// single-agent RX_RAY_LPR2_N band is empty for them: with the REWARD half at a
-// lane per car, 8,192 envs run 134.7 M at 1 lane per ray vs 128.6 M at 2)
-#ifndef RX_RAY2_LPR2_N
-#define RX_RAY2_LPR2_N 8192
-#endif
-// Ray-wave dispatch order (rx_assign's placement of the ray-wave table, ray_order 2).
-// Class j of a 64-env group = its j-th wave of direction-sorted tasks (the cars of a
-// group head alike, so class j ~ sensor ray j: the edge classes look sideways, the
-// centre ones down the track and cost ~1.3x).  0 = group-octet-major (round 2),
-// 1 = class-major centre classes first, 2 = class-major ascending j, 3 = class-major
-// EDGE classes first, the centre ones last (default: 65,536 envs 752 -> 826-833 M
-// env-steps/s, 4,096 envs +3 %, same session, DESIGN.md §3 "Ray-wave dispatch order").
-#ifndef RX_RAY_DISPATCH
-#define RX_RAY_DISPATCH 3
-#endif
-// rx_config.ray_tail / ray_tail_lpr automatic values: the last RX_RAY_TAIL classes of the
-// dispatch order cast at RX_RAY_TAIL_LPR lanes per ray (0 = no tail split)
-#ifndef RX_RAY_TAIL
-#define RX_RAY_TAIL 0
-#endif
-#ifndef RX_RAY_TAIL_LPR
-#define RX_RAY_TAIL_LPR 2
-#endif
-// rx_config.task_sort automatic value: the ray-task direction sort every other
-// dynamics launch up to this many (env, car) pairs, every launch above.  Same-session
-// A/B (profiles/r04/ab_task_sort.txt): 4,096 single-agent envs 129.8 / 128.9 ->
-// 132.3 / 132.7 M env-steps/s (k_kin1 6.2 -> 3.6 us), 8,192 two-car envs 135.1 / 136.7
-// -> 137.2 / 138.8 M; 65,536 envs 833 -> 804-810 M (every 4th / 8th: 761 / 715 M) and
-// 65,536 two-car envs -0.5 %: the stale order costs more ray work than the sort
-#ifndef RX_TASK_SORT2_PAIRS
-#define RX_TASK_SORT2_PAIRS 16384
-#endif
-// at most this many single-agent envs: one env per dynamics wave and one ray
-// per raycast wave (k_rays_wide), brute force over the lanes -- the kernels
-// are latency chains there, and 64 lanes shorten them
-#define RX_WIDE_N 2048
 
 struct rx_kargs {
   rx_track_view tr;
@@ -503,7 +423,7 @@ extern "C" int rx_launch_adam_apply(const rx_adam_config* cfg, float* p, float* 
                                     const double* lr, const uint8_t* stop, float* ws, int nb, hipStream_t s);
 // spatial re-sort (rx_sort.hip): counting sort of the perm positions by the
 // bin keys the REWARD half wrote; hist must be zero on entry and is left zero
-#define RX_SORT_MAX_BINS 65536
+// (at most RX_SORT_MAX_BINS bins, rx_assign_plan.h)
 // and moves the working state rows with their envs (perm, work -> perm_tmp,
 // tmp -> back); rx_state_sync: working copy <-> the caller's arrays
 extern "C" int rx_sort_envs(const uint32_t* keys, uint32_t* off, int n, int A, uint32_t* hist, uint32_t* cursor, int nbins,

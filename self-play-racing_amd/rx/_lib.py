@@ -9,6 +9,7 @@ device is absent, calls fail loudly.
 import ctypes
 import os
 
+import numpy as np
 import torch  # noqa: F401  (must precede librx: shared HIP runtime, see above)
 
 from . import _build
@@ -45,7 +46,7 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_track_episode_host", "rx_track_episode_step", "rx_track_episodic_rollout_steps",
            "rx_track_learn_tally_slots", "rx_track_learn_tally_slots_host", "rx_track_learn_episode",
            "rx_track_learn_episode_host", "rx_track_learn_episode_step", "rx_track_learn_episodic_rollout_steps",
-           "rx_steps_plan", "rx_patch_tracks", "rx_patch_tracks_host", "rx_replace_tracks_device")
+           "rx_steps_plan", "rx_patch_tracks", "rx_patch_tracks_host", "rx_replace_tracks_device", "rx_assign_plan")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -140,6 +141,43 @@ def steps_plan_default(n_steps):
     if load().rx_steps_plan(ctypes.byref(a), None, 0) < 0:
         raise RxError("rx_steps_plan: bad arguments")
     return a.depth, bool(a.rank_in_kin)
+
+
+# rx_assign_plan (additive to ABI v25): the assignment rx_assign would build, host only
+ASSIGN_PLAN_PTRS = ("schedule", "perm", "dyn_waves", "ray_waves", "slot_n", "pos_slot", "env_pos", "sort_base")
+
+
+class RxAssignPlanIO(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("dyn_cap", "ray_cap", "n_dyn_waves", "n_ray_waves", "sort_bins",
+                                              "sort_shift")] + [(k, _P) for k in ASSIGN_PLAN_PTRS]
+
+
+def assign_plan(cfg, wp_off, track_of_env):
+    """rx_assign_plan for an RxConfig, wp_off int32 [n_tracks + 1] and track_of_env int32 [n_envs]: a dict of
+    schedule (by SCHEDULE_KEYS), perm, sort_bins, sort_shift, dyn_waves / ray_waves int32 [n][4], slot_n, and
+    pos_slot / env_pos (lane-varying schedules, else None) and sort_base (with sort_bins > 0, else None).
+    A refusal raises RxError with the library's text."""
+    L = load()
+    wp_off = np.ascontiguousarray(wp_off, np.int32)
+    toe = np.ascontiguousarray(track_of_env, np.int32)
+    n_tracks, N = len(wp_off) - 1, cfg.n_envs
+    io = RxAssignPlanIO()
+    check(L.rx_assign_plan(ctypes.byref(cfg), n_tracks, ptr(wp_off), ptr(toe), ctypes.byref(io)), "rx_assign_plan")
+    out = dict(schedule=np.zeros(SCHEDULE_W, np.int32), perm=np.zeros(N, np.int32),
+               dyn_waves=np.zeros((io.n_dyn_waves, 4), np.int32), ray_waves=np.zeros((io.n_ray_waves, 4), np.int32),
+               slot_n=np.zeros(n_tracks, np.int32), pos_slot=np.zeros(N, np.int32), env_pos=np.zeros(N, np.int32),
+               sort_base=np.zeros(n_tracks, np.int32))
+    io.dyn_cap, io.ray_cap = io.n_dyn_waves, io.n_ray_waves
+    for k in ASSIGN_PLAN_PTRS:
+        setattr(io, k, out[k].ctypes.data)
+    check(L.rx_assign_plan(ctypes.byref(cfg), n_tracks, ptr(wp_off), ptr(toe), ctypes.byref(io)), "rx_assign_plan")
+    out["schedule"] = {k: int(v) for k, v in zip(SCHEDULE_KEYS, out["schedule"])}
+    out["sort_bins"], out["sort_shift"] = io.sort_bins, io.sort_shift
+    if not out["schedule"]["lane_tracks"]:
+        out["pos_slot"] = out["env_pos"] = None
+    if io.sort_bins == 0:
+        out["sort_base"] = None
+    return out
 
 
 class RxAdamConfig(ctypes.Structure):
@@ -311,6 +349,7 @@ def load(build_if_missing=True):
     L.rx_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.c_int32, ctypes.POINTER(RxIOStrides), _P]
     L.rx_steps_plan.argtypes = [ctypes.POINTER(RxPlanArgs), ctypes.POINTER(RxPlanLaunch), ctypes.c_int32]
     L.rx_steps_plan.restype = ctypes.c_int32
+    L.rx_assign_plan.argtypes = [ctypes.POINTER(RxConfig), ctypes.c_int32, _P, _P, ctypes.POINTER(RxAssignPlanIO)]
     gae_args = [ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P]
     L.rx_gae.argtypes = gae_args
     L.rx_gae_scan.argtypes = gae_args

@@ -205,6 +205,7 @@ class RacingVectorEnv:
             cfg = _lib.RxConfig(N, A, R, self.max_steps, _AUTORESET[autoreset], dev.index or 0, int(seed) & (2**64 - 1),
                                 float(half_cone), self.speed_weight, int(cull_chunk), self.sort_interval,
                                 int(ray_order), int(cull_super), *[int(sched.get(k, 0)) for k in _lib.SCHED_FIELDS])
+            self._cfg = cfg
             h = _lib._P()
             _lib.check(self.L.rx_create(cfg, h), "rx_create")
             self._h = h
@@ -474,6 +475,12 @@ class RacingVectorEnv:
         return {"track": t[:, 0], "perm_start": t[:, 1], "task_start": t[:, 2], "count": t[:, 3],
                 "cls": np.where(t[:, 3] > 0, off // (64 // max(1, sch["ray_lpr"])), -1),
                 "sub": np.where(t[:, 3] > 0, (off % 64) // per, -1)}
+
+    def assign_plan(self, track_of_env=None):
+        """What rx_assign builds for this env's config and track table (rx_assign_plan: host only, the
+        handle is not touched; _lib.assign_plan's dict), for ``track_of_env`` or the current slots."""
+        toe = self.track_of_env if track_of_env is None else track_of_env
+        return _lib.assign_plan(self._cfg, self.tracks.arrays()["wp_off"], toe)
 
     def enable_counters(self, on=True):
         """Per-wave culling counters (rx_io.counters): chunk tests / scans."""
