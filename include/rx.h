@@ -1438,6 +1438,75 @@ int rx_track_evolve_plan_host(const rx_track_evolve_io* ev, uint32_t generation,
 int rx_track_evolve(const rx_track_evolve_io* ev, uint32_t generation, void* stream);
 int rx_track_evolve_host(const rx_track_evolve_io* ev, uint32_t generation, void* stream);
 
+/* ABI v25, additive: TRACK EVOLUTION IN PLACE -- the same fresh tracks and edited
+ * children for a pool whose slots keep their point counts (the episodic trainers'
+ * partial resample, rx.track_evolve_episodic): no offset moves, so the pool buffer,
+ * the resident track table and the captured rollout graphs all stay.  An edited
+ * child must have its slot's point count, so the parent is drawn among the slots of
+ * that point count only: the rank table is regrouped by point count on the device.
+ * Since the host knows every spawned slot's P beforehand, nothing is downloaded
+ * between the three calls.  Rules: csrc/rx_track_evolve.h, DESIGN.md §4.
+ *
+ * rx_track_evolve_classes(): with P_k = cp_off[k+1] - cp_off[k] and w_k = cdf_score[k] -
+ * cdf_score[k-1] (w_0 = cdf_score[0]):
+ *   order[n_tracks]      the slots sorted by (P_k, k) ascending (a stable counting sort);
+ *                        a slot with P_k outside [1, 64] belongs to no class, weighs 0
+ *                        and follows the last class in slot order;
+ *   cdf_class[n_tracks]  the inclusive integer scan of w[order[i]], through the classes
+ *                        without restarting;
+ *   class_end[65]        class_end[p] = the number of slots with 1 <= P <= p, class_end[0] = 0.
+ * Reads cp_off, cdf_score; writes order, cdf_class, class_end.  It does not look at the
+ * spawn set (n_spawn only has to be in range; slots may be null).
+ *
+ * rx_track_evolve_inplace(generation, edit_frac): for j < n_spawn, k = slots[j], c = P_k:
+ *   lo = class_end[c-1], hi = class_end[c], base = lo ? cdf_class[lo-1] : 0,
+ *   F = cdf_class[hi-1] - base;  draw 0: an EDIT when u < edit_frac and F > 0, else FRESH;
+ *   EDIT:  t = base + mulhi(h, F), parent = order[i] for the smallest i in [lo, hi) with
+ *          t < cdf_class[i] (the slot itself and slots being replaced included: the OLD
+ *          points are read); the child is rx_track_evolve's edit of it;
+ *   FRESH: draw 1 is consumed and discarded; rx_track_evolve's fresh track of P_k points.
+ *   plan[j] = (kind, parent or -1, P_k, edits applied); the track goes to
+ *   cp_out[out_off[j] .. out_off[j+1]) and width_out[j], a compact staging buffer.
+ * A slot whose span in out_off is not P_k, or whose P_k lies outside [1, 64], is not
+ * written at all: width_out[j] = NaN (a bad track to rx_build_tracks), plan[j] =
+ * (FRESH, -1, P_k, 0).  Reads slots, cp_off, cp, width, order, cdf_class, class_end, out_off;
+ * writes plan, cp_out, width_out.  The pool is not written.
+ *
+ * rx_track_evolve_commit(): the staging rows copied over the spawned slots' spans of cp
+ * and over width[slots[j]]; every other byte of the pool stays.  A slot inplace did
+ * not write takes the NaN width and keeps its points.  Reads slots, cp_off, out_off,
+ * cp_out, width_out; writes cp, width.  To be queued after rx_track_evolve_inplace on
+ * the same stream.
+ *
+ * Pointers, twins, waits and allocation as above.  With n_spawn == 0 inplace and
+ * commit do nothing.  Checked before any HIP call (RX_EINVAL, the message names the
+ * field): a null io, n_tracks <= 0, n_spawn outside 0..n_tracks, null pointers among
+ * the ones the entry point reads or writes, edit_frac outside [0, 1] or NaN. */
+typedef struct rx_track_evolve_inplace_io {
+  int32_t n_tracks;            /* slots of the pool, > 0 */
+  int32_t n_spawn;             /* slots to replace, 0..n_tracks */
+  const int32_t* slots;        /* [n_spawn] ascending, distinct */
+  const int32_t* cp_off;       /* [n_tracks + 1] offsets in points; they never change */
+  double* cp;                  /* [cp_off[n_tracks]][2] the pool: read by inplace, written by commit */
+  double* width;               /* [n_tracks] likewise */
+  const int64_t* cdf_score;    /* [n_tracks] rx_track_learn_tables' rank table (classes only) */
+  int32_t* order;              /* [n_tracks] slots by (P, slot) */
+  int64_t* cdf_class;          /* [n_tracks] the rank weights scanned in that order */
+  int32_t* class_end;          /* [65] slots with 1 <= P <= p */
+  int32_t* plan;               /* [n_spawn][4] = (kind, parent or -1, P, edits applied) */
+  const int32_t* out_off;      /* [n_spawn + 1] staging offsets in points */
+  double* cp_out;              /* [out_off[n_spawn]][2] staging */
+  double* width_out;           /* [n_spawn] staging */
+  uint64_t seed;
+} rx_track_evolve_inplace_io;
+int rx_track_evolve_classes(const rx_track_evolve_inplace_io* ev, void* stream);
+int rx_track_evolve_classes_host(const rx_track_evolve_inplace_io* ev, void* stream);
+int rx_track_evolve_inplace(const rx_track_evolve_inplace_io* ev, uint32_t generation, double edit_frac, void* stream);
+int rx_track_evolve_inplace_host(const rx_track_evolve_inplace_io* ev, uint32_t generation, double edit_frac,
+                                 void* stream);
+int rx_track_evolve_commit(const rx_track_evolve_inplace_io* ev, void* stream);
+int rx_track_evolve_commit_host(const rx_track_evolve_inplace_io* ev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2808,4 +2808,84 @@ int rx_track_evolve_host(const rx_track_evolve_io* ev, uint32_t generation, void
   return RX_OK;
 }
 
+// ABI v25, additive: track evolution in place.  which: 0 classes, 1 inplace, 2 commit.
+static int evolve_inplace_args(const char* fn, const rx_track_evolve_inplace_io* ev, int which, double edit_frac) {
+  if (!ev) return fail(RX_EINVAL, "%s: null track evolve inplace io", fn);
+  if (ev->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, ev->n_tracks);
+  if (ev->n_spawn < 0 || ev->n_spawn > ev->n_tracks)
+    return fail(RX_EINVAL, "%s: n_spawn=%d outside 0..n_tracks=%d", fn, ev->n_spawn, ev->n_tracks);
+  if (which == 1 && !(edit_frac >= 0.0 && edit_frac <= 1.0))
+    return fail(RX_EINVAL, "%s: edit_frac=%g outside [0, 1]", fn, edit_frac);
+  if (which != 0 && ev->n_spawn == 0) return RX_OK;  // nothing is read
+  if (which != 0 && !ev->slots) return evolve_null(fn, "slots");
+  if (!ev->cp_off) return evolve_null(fn, "cp_off");
+  if (which != 0) {
+    if (!ev->cp) return evolve_null(fn, "cp");
+    if (!ev->width) return evolve_null(fn, "width");
+  }
+  if (which == 0 && !ev->cdf_score) return evolve_null(fn, "cdf_score");
+  if (which != 2) {
+    if (!ev->order) return evolve_null(fn, "order");
+    if (!ev->cdf_class) return evolve_null(fn, "cdf_class");
+    if (!ev->class_end) return evolve_null(fn, "class_end");
+  }
+  if (which == 1 && !ev->plan) return evolve_null(fn, "plan");
+  if (which != 0) {
+    if (!ev->out_off) return evolve_null(fn, "out_off");
+    if (!ev->cp_out) return evolve_null(fn, "cp_out");
+    if (!ev->width_out) return evolve_null(fn, "width_out");
+  }
+  return RX_OK;
+}
+
+int rx_track_evolve_classes(const rx_track_evolve_inplace_io* ev, void* stream) {
+  int rc = evolve_inplace_args("rx_track_evolve_classes", ev, 0, 0.0);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_evolve_classes(ev, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_evolve_classes: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_evolve_classes_host(const rx_track_evolve_inplace_io* ev, void* /*stream*/) {
+  const int rc = evolve_inplace_args("rx_track_evolve_classes_host", ev, 0, 0.0);
+  if (rc) return rc;
+  rx_host_track_evolve_classes(ev);
+  return RX_OK;
+}
+
+int rx_track_evolve_inplace(const rx_track_evolve_inplace_io* ev, uint32_t generation, double edit_frac, void* stream) {
+  int rc = evolve_inplace_args("rx_track_evolve_inplace", ev, 1, edit_frac);
+  if (rc) return rc;
+  if (ev->n_spawn == 0) return RX_OK;
+  if ((rc = rx_launch_track_evolve_inplace(ev, generation, edit_frac, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_evolve_inplace: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_evolve_inplace_host(const rx_track_evolve_inplace_io* ev, uint32_t generation, double edit_frac,
+                                 void* /*stream*/) {
+  const int rc = evolve_inplace_args("rx_track_evolve_inplace_host", ev, 1, edit_frac);
+  if (rc) return rc;
+  if (ev->n_spawn == 0) return RX_OK;
+  rx_host_track_evolve_inplace(ev, generation, edit_frac);
+  return RX_OK;
+}
+
+int rx_track_evolve_commit(const rx_track_evolve_inplace_io* ev, void* stream) {
+  int rc = evolve_inplace_args("rx_track_evolve_commit", ev, 2, 0.0);
+  if (rc) return rc;
+  if (ev->n_spawn == 0) return RX_OK;
+  if ((rc = rx_launch_track_evolve_commit(ev, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_evolve_commit: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_evolve_commit_host(const rx_track_evolve_inplace_io* ev, void* /*stream*/) {
+  const int rc = evolve_inplace_args("rx_track_evolve_commit_host", ev, 2, 0.0);
+  if (rc) return rc;
+  if (ev->n_spawn == 0) return RX_OK;
+  rx_host_track_evolve_commit(ev);
+  return RX_OK;
+}
+
 }  // extern "C"

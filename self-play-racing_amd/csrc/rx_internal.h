@@ -408,6 +408,15 @@ extern "C" int rx_launch_track_evolve(const rx_track_evolve_io* ev, uint32_t gen
 // rx_track_evolve_host.cpp: the same two as host loops (plain C++, no HIP call)
 extern "C" void rx_host_track_evolve_plan(const rx_track_evolve_io* ev, uint32_t generation, double edit_frac);
 extern "C" void rx_host_track_evolve(const rx_track_evolve_io* ev, uint32_t generation);
+// the in-place form (rx_track_evolve.hip; rx_track_evolve_host.cpp)
+extern "C" int rx_launch_track_evolve_classes(const rx_track_evolve_inplace_io* ev, hipStream_t s);
+extern "C" int rx_launch_track_evolve_inplace(const rx_track_evolve_inplace_io* ev, uint32_t generation,
+                                              double edit_frac, hipStream_t s);
+extern "C" int rx_launch_track_evolve_commit(const rx_track_evolve_inplace_io* ev, hipStream_t s);
+extern "C" void rx_host_track_evolve_classes(const rx_track_evolve_inplace_io* ev);
+extern "C" void rx_host_track_evolve_inplace(const rx_track_evolve_inplace_io* ev, uint32_t generation,
+                                             double edit_frac);
+extern "C" void rx_host_track_evolve_commit(const rx_track_evolve_inplace_io* ev);
 extern "C" int rx_launch_adv_stats(const rx_ppo_batch* b, int n_mb, float* stats, double* moments, hipStream_t s);
 extern "C" int rx_adv_chunks(int mb);
 extern "C" int rx_launch_adv_stats_ws(const rx_ppo_batch* b, int n_mb, double* ws, float* stats, double* moments,

@@ -51,6 +51,34 @@
 //    offsets do not follow the plan) is not written at all; its width becomes NaN,
 //    which rx_build_tracks marks as a bad track.  The kernel never writes outside
 //    [cp_off_new[k], cp_off_new[k + 1]).
+//
+// Rules of the IN-PLACE form (rx_track_evolve_classes / _inplace / _commit; DESIGN.md §4
+// "Track evolution in place"): a spawned slot keeps its point count, so no offset moves.
+//  * The class table.  P_k = cp_off[k + 1] - cp_off[k]; w_k = cdf_score[k] - cdf_score[k - 1]
+//    (w_0 = cdf_score[0]).  order[n_tracks] holds the slots sorted by (P_k, k) ascending: a
+//    stable counting sort by point count.  A slot whose P_k lies outside [1, RX_TRACK_MAX_P]
+//    belongs to no class: it weighs 0 and follows the last class, in slot order.
+//    cdf_class[i] is the inclusive integer scan of w[order[i]], through the classes without
+//    restarting; class_end[p] = the number of slots with 1 <= P <= p (class_end[0] = 0), for
+//    p <= RX_TRACK_MAX_P.  All integers: the table is unique whatever order it is built in.
+//  * The stream of spawned slot k at generation g is rx_te_stream, the draws keep their places.
+//  * draw 0, the kind: with c = P_k, lo = class_end[c - 1], hi = class_end[c],
+//    base = lo ? cdf_class[lo - 1] : 0 and F = cdf_class[hi - 1] - base: EDIT when
+//    u < edit_frac and F > 0, else FRESH.
+//  * draw 1, EDIT: t = base + mulhi(h, F); parent = order[i] for the smallest i in [lo, hi)
+//    with t < cdf_class[i].  The parent has the slot's point count; it may be the slot itself
+//    or another slot that is being replaced: parents are read from the pool as it stood.
+//    The child is rx_te_edit.  FRESH: the draw is consumed and discarded (the point count is
+//    the slot's own) and the track is rx_te_fresh(h0, P_k): bit for bit the track
+//    rx_track_evolve writes for the same (seed, g, k) whenever that path draws the same P.
+//  * The plan row is (kind, parent or -1, P_k, edits applied).  The track goes into a compact
+//    staging buffer, cp_out[out_off[j] .. out_off[j + 1]) and width_out[j], never into the pool.
+//    A slot whose staging span is not P_k, or whose P_k lies outside [1, RX_TRACK_MAX_P], or
+//    whose slot index lies outside the pool, is not written at all: width_out[j] becomes NaN
+//    and its plan row is (FRESH, -1, P_k, 0).  Nothing is written outside the slot's span.
+//  * The commit copies the staging rows over the spawned slots' spans of cp and width; every
+//    other byte of the pool stays.  A slot that was not written (the same three conditions)
+//    takes the NaN width and keeps its points.
 #pragma once
 
 #include <stdint.h>
@@ -59,6 +87,7 @@
 #include "rx_curriculum.h"  // rx_tc_mulhi64, rx_tc_search
 #include "rx_league.h"      // rx_lg_splitmix64
 #include "rx_math.h"        // rx_sincos, rx_clip, RX_SQRT
+#include "rx_spline.h"      // RX_TRACK_MAX_P
 
 #define RX_TRACK_EVOLVE_W 4          // plan row: kind, parent, P, edits applied
 #define RX_TRACK_EVOLVE_FRESH 0
@@ -255,5 +284,106 @@ RX_FN void rx_te_slot(const rx_track_evolve_io* ev, uint32_t g, int32_t k) {
     }
     ev->width_new[k] = rx_te_fresh(h0, span, out);
     row[3] = 0;
+  }
+}
+
+// ---- in place: the class table, the staging buffer, the commit ------------------------------------------
+
+#define RX_TRACK_EVOLVE_BINS (RX_TRACK_MAX_P + 2)  // bin P for 1 <= P <= RX_TRACK_MAX_P, the last bin for no class
+
+// the bin of a point count: P itself, or the bin behind the last class
+RX_FN int32_t rx_te_bin(int32_t P) { return P >= 1 && P <= RX_TRACK_MAX_P ? P : RX_TRACK_MAX_P + 1; }
+
+RX_FN int32_t rx_te_points(const int32_t* cp_off, int32_t k) { return cp_off[k + 1] - cp_off[k]; }
+
+// w_k of the rank table, 0 for a slot of no class
+RX_FN uint64_t rx_te_class_weight(const int64_t* cdf_score, int32_t k, int32_t bin) {
+  if (bin > RX_TRACK_MAX_P) return 0;
+  return (uint64_t)cdf_score[k] - (k ? (uint64_t)cdf_score[k - 1] : 0ull);
+}
+
+// whether spawned slot j has a place to be written to: its slot in the pool, a point count
+// of a class, a staging span of that many points
+RX_FN int rx_te_inplace_ok(const rx_track_evolve_inplace_io* ev, int32_t j, int32_t* k_out, int32_t* P_out) {
+  const int32_t k = ev->slots[j];
+  *k_out = k;
+  *P_out = 0;
+  if (k < 0 || k >= ev->n_tracks) return 0;
+  const int32_t P = rx_te_points(ev->cp_off, k);
+  *P_out = P;
+  return P >= 1 && P <= RX_TRACK_MAX_P && ev->out_off[j + 1] - ev->out_off[j] == P;
+}
+
+// spawned slot j: its plan row and its track in the staging buffer
+RX_FN void rx_te_inplace_slot(const rx_track_evolve_inplace_io* ev, uint32_t g, double edit_frac, int32_t j) {
+  int32_t* row = ev->plan + (size_t)j * RX_TRACK_EVOLVE_W;
+  int32_t k, P;
+  row[0] = RX_TRACK_EVOLVE_FRESH;
+  row[1] = -1;
+  row[3] = 0;
+  if (!rx_te_inplace_ok(ev, j, &k, &P)) {
+    row[2] = P;
+    ev->width_out[j] = rx_te_nan();
+    return;
+  }
+  row[2] = P;
+  double* out = ev->cp_out + 2 * (size_t)ev->out_off[j];
+  const uint64_t h0 = rx_te_stream(ev->seed, g, (uint32_t)k);
+  const int32_t lo = ev->class_end[P - 1], hi = ev->class_end[P];
+  uint64_t base = 0, F = 0;
+  if (lo >= 0 && lo < hi && hi <= ev->n_tracks) {  // (a table that was built for this pool always has k itself in here)
+    base = lo ? (uint64_t)ev->cdf_class[lo - 1] : 0ull;
+    F = (uint64_t)ev->cdf_class[hi - 1] - base;
+  }
+  if (rx_te_kind(h0, edit_frac, F) == RX_TRACK_EVOLVE_EDIT) {
+    const uint64_t t = base + rx_tc_mulhi64(rx_lg_splitmix64(h0), F);
+    const int32_t parent = ev->order[lo + rx_tc_search(ev->cdf_class + lo, hi - lo, t)];
+    if (parent < 0 || parent >= ev->n_tracks || rx_te_points(ev->cp_off, parent) != P) {  // not this pool's table
+      ev->width_out[j] = rx_te_nan();
+      return;
+    }
+    double w;
+    row[0] = RX_TRACK_EVOLVE_EDIT;
+    row[1] = parent;
+    row[3] = rx_te_edit(h0, P, ev->cp + 2 * (size_t)ev->cp_off[parent], ev->width[parent], out, &w);
+    ev->width_out[j] = w;
+  } else {
+    ev->width_out[j] = rx_te_fresh(h0, P, out);
+  }
+}
+
+// the commit of spawned slot j (whose slot is k), one point at a time
+RX_FN void rx_te_commit_point(const rx_track_evolve_inplace_io* ev, int32_t j, int32_t k, int32_t i) {
+  const size_t src = 2 * ((size_t)ev->out_off[j] + (size_t)i), dst = 2 * ((size_t)ev->cp_off[k] + (size_t)i);
+  ev->cp[dst] = ev->cp_out[src];
+  ev->cp[dst + 1] = ev->cp_out[src + 1];
+}
+
+RX_FN void rx_te_commit_slot(const rx_track_evolve_inplace_io* ev, int32_t j) {
+  int32_t k, P;
+  const int ok = rx_te_inplace_ok(ev, j, &k, &P);
+  if (k < 0 || k >= ev->n_tracks) return;
+  if (ok)
+    for (int32_t i = 0; i < P; ++i) rx_te_commit_point(ev, j, k, i);
+  ev->width[k] = ev->width_out[j];
+}
+
+// the class table, one slot after the other (the host twin; the kernel gives the same integers)
+RX_FN void rx_te_classes_serial(const rx_track_evolve_inplace_io* ev) {
+  int32_t start[RX_TRACK_EVOLVE_BINS + 1];
+  for (int32_t b = 0; b <= RX_TRACK_EVOLVE_BINS; ++b) start[b] = 0;
+  for (int32_t k = 0; k < ev->n_tracks; ++k) start[rx_te_bin(rx_te_points(ev->cp_off, k)) + 1] += 1;
+  for (int32_t b = 1; b <= RX_TRACK_EVOLVE_BINS; ++b) start[b] += start[b - 1];  // start[b]: the slots of bins < b
+  for (int32_t p = 0; p <= RX_TRACK_MAX_P; ++p) ev->class_end[p] = start[p + 1];
+  for (int32_t k = 0; k < ev->n_tracks; ++k) {
+    const int32_t b = rx_te_bin(rx_te_points(ev->cp_off, k));
+    const int32_t pos = start[b]++;
+    ev->order[pos] = k;
+    ev->cdf_class[pos] = (int64_t)rx_te_class_weight(ev->cdf_score, k, b);
+  }
+  uint64_t run = 0;
+  for (int32_t i = 0; i < ev->n_tracks; ++i) {
+    run += (uint64_t)ev->cdf_class[i];
+    ev->cdf_class[i] = (int64_t)run;
   }
 }

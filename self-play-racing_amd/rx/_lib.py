@@ -42,7 +42,9 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_track_draw", "rx_track_draw_host", "rx_track_rollout_steps", "rx_track_learn_tally",
            "rx_track_learn_tally_host", "rx_track_learn_fold", "rx_track_learn_fold_host", "rx_track_learn_tables",
            "rx_track_learn_tables_host", "rx_track_learn_draw", "rx_track_learn_draw_host", "rx_track_evolve_plan",
-           "rx_track_evolve_plan_host", "rx_track_evolve", "rx_track_evolve_host", "rx_track_episode",
+           "rx_track_evolve_plan_host", "rx_track_evolve", "rx_track_evolve_host", "rx_track_evolve_classes",
+           "rx_track_evolve_classes_host", "rx_track_evolve_inplace", "rx_track_evolve_inplace_host",
+           "rx_track_evolve_commit", "rx_track_evolve_commit_host", "rx_track_episode",
            "rx_track_episode_host", "rx_track_episode_step", "rx_track_episodic_rollout_steps",
            "rx_track_learn_tally_slots", "rx_track_learn_tally_slots_host", "rx_track_learn_episode",
            "rx_track_learn_episode_host", "rx_track_learn_episode_step", "rx_track_learn_episodic_rollout_steps",
@@ -283,6 +285,17 @@ class RxTrackEvolveIO(ctypes.Structure):
                [("seed", ctypes.c_uint64)]
 
 
+# track evolution in place (ABI v25, additive): the rank table by point count, a staging buffer, a commit
+RX_TRACK_MAX_P = 64
+TRACK_EVOLVE_INPLACE_FIELDS = ("slots", "cp_off", "cp", "width", "cdf_score", "order", "cdf_class", "class_end", "plan",
+                               "out_off", "cp_out", "width_out")
+
+
+class RxTrackEvolveInplaceIO(ctypes.Structure):
+    _fields_ = [("n_tracks", ctypes.c_int32), ("n_spawn", ctypes.c_int32)] + \
+               [(k, _P) for k in TRACK_EVOLVE_INPLACE_FIELDS] + [("seed", ctypes.c_uint64)]
+
+
 # rendering (ABI v25, additive): pixel classes / trail bits, size limits, edge record width (include/rx.h)
 RX_PX_BACKGROUND, RX_PX_TRACK, RX_PX_BORDER, RX_PX_START, RX_PX_TRAIL0, RX_PX_TRAIL1 = 0, 1, 2, 3, 0x10, 0x20
 RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX, RX_RASTER_EDGE_W = 16, 2048, 6
@@ -442,6 +455,10 @@ def load(build_if_missing=True):
         ev = ctypes.POINTER(RxTrackEvolveIO)
         getattr(L, "rx_track_evolve_plan" + sfx).argtypes = [ev, ctypes.c_uint32, ctypes.c_double, _P]
         getattr(L, "rx_track_evolve" + sfx).argtypes = [ev, ctypes.c_uint32, _P]
+        evi = ctypes.POINTER(RxTrackEvolveInplaceIO)
+        getattr(L, "rx_track_evolve_classes" + sfx).argtypes = [evi, _P]
+        getattr(L, "rx_track_evolve_inplace" + sfx).argtypes = [evi, ctypes.c_uint32, ctypes.c_double, _P]
+        getattr(L, "rx_track_evolve_commit" + sfx).argtypes = [evi, _P]
         getattr(L, "rx_league_weights" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int32, ctypes.c_int32,
                                                          ctypes.c_double, ctypes.c_double, _P]
         getattr(L, "rx_league_draw" + sfx).argtypes = [ctypes.POINTER(RxLeagueIO), ctypes.c_int64, _P, _P, _P]

@@ -183,20 +183,57 @@ class DeviceTrackTable:
         source.slots = np.ascontiguousarray(slots, dtype=np.int32)
         return source
 
+    def replacement_from_device(self, slots, out_off, cp_d, width_d):
+        """``replacement`` for new tracks that already live in device memory: row j of
+        ``out_off`` (host int32 [n + 1], in points), ``cp_d`` (float64 [out_off[n], 2]) and
+        ``width_d`` (float64 [n]) goes into ``slots[j]``; the slots must be ascending.  The same
+        checks from the host offsets (ValueError naming the slot whose span is not its point
+        count), then ``build_from_device``: one rx_build_tracks launch, no upload, no download."""
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        out_off = np.ascontiguousarray(out_off, dtype=np.int32).reshape(-1)
+        n = len(self)
+        if len(slots) == 0 or len(out_off) != len(slots) + 1:
+            raise ValueError("replace: need at least one slot, and one row of offsets per slot and one more")
+        if slots.min() < 0 or slots.max() >= n or np.any(np.diff(slots) <= 0):
+            raise ValueError(f"replace: the slots must be distinct, ascending and lie in [0, {n})")
+        for k, have in zip(slots, np.diff(out_off)):
+            want = int(self.wp_off[k + 1] - self.wp_off[k])
+            if int(have) * self.factor != want:
+                raise ValueError(f"replace: slot {k} has {want} waypoints ({want / self.factor:g} control points x "
+                                 f"{self.factor}), its new track {int(have)} control points: a replaced slot keeps its "
+                                 "point count")
+        source = DeviceTrackTable.build_from_device(out_off, cp_d, width_d, factor=self.factor)
+        source.slots = np.ascontiguousarray(slots, dtype=np.int32)
+        return source
+
     def apply(self, source):
         """The second half of ``replace``: ``source``'s rows written over its slots'
         rows of this table (rx_patch_tracks: one launch on torch's current stream, no
-        wait, no download), and the control points and widths this table knows."""
+        wait, no download), and the control points and widths this table knows.  A
+        source whose control points live in device memory (``replacement_from_device``)
+        is not downloaded for that: this table then knows no control points until
+        ``point_at`` names the buffer that holds the pool."""
         p, keep = self.patch(source)
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().rx_patch_tracks(len(self), _lib.ptr(self.wp_off), _lib.ptr(self.wp),
                                                    _lib.ptr(self.nrm), _lib.ptr(self.seg), _lib.ptr(self.meta), 0, 0,
                                                    None, ctypes.byref(p), _lib.stream_ptr()), "rx_patch_tracks")
         del keep
-        if self.control_points is not None:  # (a build_from_device table downloads them here)
+        if source._cp_dev is not None:
+            self._control_points = self._widths = self._cp_dev = None
+        elif self.control_points is not None:  # (a build_from_device table downloads them here)
             for k, c, w in zip(source.slots, source.control_points, source.widths):
                 self._control_points[k], self._widths[k] = c, w
         self._track_set = None
+
+    def point_at(self, cp_off, cp_d, width_d):
+        """The control points of this table's slots are the device buffer (``cp_off`` host
+        int32 [n + 1], ``cp_d`` float64 [cp_off[n], 2], ``width_d`` float64 [n]) from now on:
+        ``control_points`` / ``widths`` download it when asked, as after ``build_from_device``."""
+        if len(cp_off) != len(self) + 1:
+            raise ValueError(f"point_at: {len(cp_off) - 1} slots of control points for a table of {len(self)}")
+        self._control_points = self._widths = self._track_set = None
+        self._cp_dev = (np.ascontiguousarray(cp_off, dtype=np.int32), cp_d, width_d)
 
     def replace(self, slots, control_points, widths):
         """New tracks in the given slots of this table, in place.  A slot keeps its

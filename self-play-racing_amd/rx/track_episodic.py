@@ -116,6 +116,20 @@ class EpisodicCurriculumPPO(CurriculumPPO):
         """The partial path's hook between the tallies' reset and the new scores: what else a
         subclass keeps per slot starts again here."""
 
+    def _before_retire(self, generation, retired):
+        """The partial path's hook before the retired slots' tallies are reset: what a
+        subclass reads of the slots as they stand (their ranks, say) is read here."""
+
+    def _replace_retired(self, generation, retired):
+        """The partial path's replacement itself -> ``replace_tracks``' (obs, mask).  Here:
+        fresh host tracks of the slots' own point counts (``spawn_same_points``),
+        ``RacingVectorEnv.replace_tracks``, and the host copy of the pool."""
+        cps, widths = spawn_same_points(self.config["seed"], generation, [len(self._cps[k]) for k in retired])
+        obs, mask = self.envs.replace_tracks(retired, cps, widths)
+        for k, cp, w in zip(retired, cps, widths):
+            self._cps[k], self._widths[k] = cp, w
+        return obs, mask
+
     def _resample_partial(self, retired):
         """``retired`` (ascending) replaced in place: fresh tracks of the slots' own point
         counts (``spawn_same_points``, generation g), their tallies start again, the envs
@@ -123,13 +137,11 @@ class EpisodicCurriculumPPO(CurriculumPPO):
         ``reassign_tracks``, no draw: an env leaves a replaced slot when its episode ends."""
         cur, envs = self.curriculum, self.envs
         g = envs.track_generation + 1
-        cps, widths = spawn_same_points(self.config["seed"], g, [len(self._cps[k]) for k in retired])
+        self._before_retire(g, retired)
         cur.reset_slots(retired)
         self._after_retire(retired)
         cur.scores()  # a fresh slot weighs what an unseen one does
-        obs, mask = envs.replace_tracks(retired, cps, widths)
-        for k, cp, w in zip(retired, cps, widths):
-            self._cps[k], self._widths[k] = cp, w
+        obs, mask = self._replace_retired(g, retired)
         if self._carry is None:
             next_obs, next_done = obs.clone(), torch.zeros(self.num_local_envs, device=self.device)
         else:  # the carried rows, the reset envs' replaced: their reset observations, not done

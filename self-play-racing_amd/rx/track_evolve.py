@@ -9,8 +9,10 @@ track of the generator's distribution, or -- ACCEL (Parker-Holder et al. 2022) -
 small edit of a track the replay scores still rank high, so the pool moves to the
 learner's frontier instead of being redrawn at random.
 
-``TrackEvolver``           the device control-point buffer (cp, width, cp_off) and
-                           the two calls (rx_track_evolve_plan / rx_track_evolve);
+``TrackEvolver``           the device control-point buffer (cp, width, cp_off), the
+                           two calls (rx_track_evolve_plan / rx_track_evolve) and the
+                           in-place form (rx_track_evolve_classes / _inplace / _commit;
+                           its trainer is rx.track_evolve_episodic);
 ``EvolvingCurriculumPPO``  ``ReplayCurriculumPPO`` whose retired slots are filled by
                            the evolver.
 
@@ -19,6 +21,7 @@ on the host (rx_build_tracks wants them there anyway), and hands the new buffer 
 ``DeviceTrackTable.build_from_device``: no control point crosses PCIe in either
 direction.  The rules are csrc/rx_track_evolve.h; DESIGN.md §4.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -48,7 +51,8 @@ class TrackEvolver:
     [n_tracks + 1] (in points) are device tensors, initialised from the env's slots;
     ``cp_off_host`` is the host copy of the offsets.  ``spawn`` writes the next pool
     into new tensors and swaps them in (the point counts change, so the buffer is
-    not edited in place)."""
+    not edited in place); ``classes`` / ``spawn_in_place`` / ``commit`` are the form for slots
+    that keep their point counts: the same tensors, written in place."""
 
     def __init__(self, venv, seed, edit_frac=0.5, factor=30):
         if venv.n_agents != 1:
@@ -78,6 +82,7 @@ class TrackEvolver:
         self.edit_frac = check_edit_frac(edit_frac)
         self.L = _lib.load()
         self.seed, self.factor, self.device = int(seed) & (2**64 - 1), factor, device
+        self._classes = None  # (order, cdf_class, class_end) of the last classes() call
 
     def load(self, control_points, widths):
         """Replace the whole pool by host tracks (one upload)."""
@@ -90,6 +95,7 @@ class TrackEvolver:
         self.cp = torch.from_numpy(np.ascontiguousarray(np.concatenate(cps))).to(self.device)
         self.width = torch.from_numpy(np.ascontiguousarray(ws, dtype=np.float64)).to(self.device)
         self.cp_off = torch.from_numpy(self.cp_off_host).to(self.device)
+        self._classes = None
 
     def table(self):
         """The ``DeviceTrackTable`` of the pool as it stands (one rx_build_tracks launch)."""
@@ -131,7 +137,77 @@ class TrackEvolver:
             _lib.check(self.L.rx_track_evolve(ctypes.byref(ev), g, s), "rx_track_evolve")
             plan = plan_d.cpu().numpy()
         self.cp, self.width, self.cp_off, self.cp_off_host = cp_new, width_new, off_new_d, off_new
+        self._classes = None  # the class table was the old pool's
         return self.table(), plan
+
+    # ------------------------------------------------------------ in place: a slot keeps its point count
+    def _inplace_io(self, ns=0, slots=None, cdf_score=None, plan=None, out_off=None, cp_out=None, width_out=None):
+        q = _lib.ptr
+        order, cdf_class, class_end = self._classes or (None, None, None)
+        return _lib.RxTrackEvolveInplaceIO(self.n_tracks, ns, q(slots), q(self.cp_off), q(self.cp), q(self.width),
+                                           q(cdf_score), q(order), q(cdf_class), q(class_end), q(plan), q(out_off),
+                                           q(cp_out), q(width_out), self.seed)
+
+    def classes(self, cdf_score, stream=None):
+        """rx_track_evolve_classes: the rank table ``cdf_score`` (device int64 [n_tracks], as
+        rx_track_learn_tables left it) regrouped by point count, for the parent draws of
+        ``spawn_in_place``.  One launch, no download and no wait.  -> the device tensors
+        (order int32 [n_tracks], cdf_class int64 [n_tracks], class_end int32 [65]), which the
+        evolver keeps and the next call overwrites."""
+        n, dev = self.n_tracks, self.cp.device
+        if cdf_score.dtype != torch.int64 or tuple(cdf_score.shape) != (n,) or cdf_score.device != dev \
+                or not cdf_score.is_contiguous():
+            raise ValueError(f"rx_track_evolve_classes: cdf_score must be a contiguous int64 [{n}] on the env's device")
+        with torch.cuda.device(dev):
+            if self._classes is None or len(self._classes[0]) != n:
+                self._classes = (torch.empty(n, dtype=torch.int32, device=dev),
+                                 torch.empty(n, dtype=torch.int64, device=dev),
+                                 torch.empty(_lib.RX_TRACK_MAX_P + 1, dtype=torch.int32, device=dev))
+            ev = self._inplace_io(cdf_score=cdf_score)
+            _lib.check(self.L.rx_track_evolve_classes(ctypes.byref(ev), _lib.stream_ptr(stream)),
+                       "rx_track_evolve_classes")
+        return self._classes
+
+    def spawn_in_place(self, slots, generation, stream=None):
+        """New tracks for ``slots`` at ``generation``, each of its slot's own point count, by the
+        class table ``classes`` left: rx_track_evolve_inplace into a compact staging buffer.  The
+        pool is not written (``commit`` does that) and nothing is downloaded or waited for: the
+        host knows every slot's point count, so it forms the staging offsets itself.
+        -> ``PendingSpawn``: ``slots`` (ascending, host int32), ``out_off`` (host int32
+        [n_spawn + 1], in points), and the device tensors ``cp_out`` float64 [out_off[-1], 2],
+        ``width_out`` float64 [n_spawn] and ``plan`` int32 [n_spawn, 4] = (kind, parent or -1,
+        P, edits applied)."""
+        n = self.n_tracks
+        if self._classes is None:
+            raise RuntimeError("spawn_in_place needs the class table: call classes(cdf_score) first")
+        slots = np.unique(np.asarray(slots, dtype=np.int64).reshape(-1))
+        if slots.size and (slots[0] < 0 or slots[-1] >= n):
+            raise ValueError(f"slots must lie in [0, {n})")
+        g, ns, dev = int(generation) & 0xFFFFFFFF, len(slots), self.cp.device
+        out_off = np.concatenate([[0], np.cumsum(np.diff(self.cp_off_host)[slots])]).astype(np.int32)
+        slots = slots.astype(np.int32)
+        with torch.cuda.device(dev):
+            slots_d, out_off_d = torch.from_numpy(slots).to(dev), torch.from_numpy(out_off).to(dev)
+            cp_out = torch.empty((int(out_off[-1]), 2), dtype=torch.float64, device=dev)
+            width_out = torch.empty(ns, dtype=torch.float64, device=dev)
+            plan = torch.zeros((ns, _lib.RX_TRACK_EVOLVE_W), dtype=torch.int32, device=dev)
+            ev = self._inplace_io(ns, slots_d, None, plan, out_off_d, cp_out, width_out)
+            _lib.check(self.L.rx_track_evolve_inplace(ctypes.byref(ev), g, self.edit_frac, _lib.stream_ptr(stream)),
+                       "rx_track_evolve_inplace")
+        return PendingSpawn(slots, out_off, cp_out, width_out, plan, g, slots_d, out_off_d)
+
+    def commit(self, pending, stream=None):
+        """rx_track_evolve_commit: ``pending``'s staging rows over its slots' spans of the pool;
+        every other byte of ``cp`` and ``width`` stays.  One launch, no wait."""
+        p = pending
+        with torch.cuda.device(self.cp.device):
+            ev = self._inplace_io(len(p.slots), p.slots_d, None, None, p.out_off_d, p.cp_out, p.width_out)
+            _lib.check(self.L.rx_track_evolve_commit(ctypes.byref(ev), _lib.stream_ptr(stream)),
+                       "rx_track_evolve_commit")
+
+
+PendingSpawn = collections.namedtuple("PendingSpawn",
+                                      "slots out_off cp_out width_out plan generation slots_d out_off_d")
 
 
 class EvolvingCurriculumPPO(ReplayCurriculumPPO):
@@ -192,4 +268,4 @@ class EvolvingCurriculumPPO(ReplayCurriculumPPO):
         return tab
 
 
-__all__ = ["TrackEvolver", "EvolvingCurriculumPPO", "check_edit_frac", "KINDS"]
+__all__ = ["TrackEvolver", "PendingSpawn", "EvolvingCurriculumPPO", "check_edit_frac", "KINDS"]

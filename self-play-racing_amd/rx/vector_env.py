@@ -339,24 +339,43 @@ class RacingVectorEnv:
         for bit.  A track librx refuses (RxError naming the slot) leaves the env as
         it was.  Returns (obs, mask): the env's obs rows, the reset envs' replaced by
         their reset observations, and the uint8 [N] device mask of the reset envs."""
-        from .track_device import DeviceTrackTable
-        table = self._table
-        if table is None:
-            table = DeviceTrackTable.from_arrays(self.tracks.arrays(), self.device)
+        table = self._resident_table()
         with torch.cuda.device(self.device):
-            source = table.replacement(slots, control_points, widths)
-            p, keep = table.patch(source)
-            # the handle first: it sees the source's meta rows and refuses a bad track before anything is written
-            _lib.check(self.L.rx_replace_tracks_device(self._h, ctypes.byref(p), _lib.stream_ptr()),
-                       "rx_replace_tracks_device")
-            del keep
-            table.apply(source)
-            flag = torch.zeros(len(table), dtype=torch.uint8, device=self.device)
-            flag[torch.from_numpy(source.slots.astype(np.int64)).to(self.device)] = 1
-            mask = flag[self._st["track"].long()]
-            self._table, self._tracks = table, None
-            self.track_generation += 1
-            obs = self.reset_device(mask)
+            return self._replace_from_source(table, table.replacement(slots, control_points, widths))
+
+    def replace_tracks_device(self, slots, out_off, cp_d, width_d):
+        """``replace_tracks`` for new tracks that already live in device memory: row j of
+        the compact buffer (``out_off`` host int32 [n + 1] in points, ``cp_d`` float64
+        [out_off[n], 2], ``width_d`` float64 [n]; ``TrackEvolver.spawn_in_place``) goes into
+        ``slots[j]`` (ascending).  ``DeviceTrackTable.replacement_from_device`` builds the
+        source without an upload; from there on it is ``replace_tracks``: the handle
+        refuses a bad track (a NaN width among them) before anything is written, the
+        same masked reset, the same (obs, mask).  The resident table then knows no
+        control points until ``DeviceTrackTable.point_at``."""
+        table = self._resident_table()
+        with torch.cuda.device(self.device):
+            return self._replace_from_source(table, table.replacement_from_device(slots, out_off, cp_d, width_d))
+
+    def _resident_table(self):
+        from .track_device import DeviceTrackTable
+        if self._table is not None:
+            return self._table
+        return DeviceTrackTable.from_arrays(self.tracks.arrays(), self.device)
+
+    def _replace_from_source(self, table, source):
+        """``replace_tracks`` from the built source table on (torch's current device is the env's)."""
+        p, keep = table.patch(source)
+        # the handle first: it sees the source's meta rows and refuses a bad track before anything is written
+        _lib.check(self.L.rx_replace_tracks_device(self._h, ctypes.byref(p), _lib.stream_ptr()),
+                   "rx_replace_tracks_device")
+        del keep
+        table.apply(source)
+        flag = torch.zeros(len(table), dtype=torch.uint8, device=self.device)
+        flag[torch.from_numpy(source.slots.astype(np.int64)).to(self.device)] = 1
+        mask = flag[self._st["track"].long()]
+        self._table, self._tracks = table, None
+        self.track_generation += 1
+        obs = self.reset_device(mask)
         if self._track_ids_stale:  # the device moved envs between slots: the mask knows, the host does not
             hit = mask.bool().cpu().numpy()
         else:

@@ -6,6 +6,7 @@
     python tools/curriculum_train.py --evolve --envs 4096 --steps 128 --updates 60 --tracks 512
     python tools/curriculum_train.py --episodic --envs 4096 --steps 128 --updates 60 --tracks 512
     python tools/curriculum_train.py --episodic --replay value_l1 --envs 4096 --steps 128 --updates 60 --tracks 512
+    python tools/curriculum_train.py --episodic --partial --evolve --envs 4096 --steps 128 --updates 60 --tracks 512
 
 ``CurriculumPPO`` on a pool of ``--tracks`` distinct tracks (env i starts on slot
 i % tracks): every finished episode is tallied against its slot on the device;
@@ -30,8 +31,13 @@ with nothing to retire resets nobody; with ``--replay`` as well it is
 ``rx.track_replay_episodic.EpisodicReplayCurriculumPPO``, whose ended envs draw
 from the value-loss scores (prioritised level replay per episode).  ``--episodic
 --partial`` (``episodic_partial``) also replaces the retired slots in place, so a
-resample that retires slots resets only the envs on them.  ``--episodic
---evolve`` is refused.  Every curriculum run also reports the
+resample that retires slots resets only the envs on them.  ``--episodic --partial
+--evolve`` (``--evolve-edit`` as above) is
+``rx.track_evolve_episodic.EpisodicEvolvingCurriculumPPO``: those retired slots are
+filled on the device, by fresh tracks and by edited children of high-ranked tracks
+of the slot's own point count.  ``--episodic --evolve`` without ``--partial`` is
+refused: only the partial path keeps a slot's point count, and the global path
+of ``--evolve`` rebuilds the table the episodic draws run on.  Every curriculum run also reports the
 episodes tallied per update, the slots that reached ``--min-episodes`` and, per
 update, the share of the envs on the fullest slot (with replay scores also on the
 slot ranked first).
@@ -86,6 +92,8 @@ def run(kind, args, evaluator):
         if replay:
             from rx.track_replay_episodic import EpisodicReplayCurriculumPPO as cls
         cfg["episodic_partial"] = bool(args.partial)
+        if evolve:  # (only with --partial: main() refuses the rest)
+            from rx.track_evolve_episodic import EpisodicEvolvingCurriculumPPO as cls
     t = cls(lambda i: RacingEnv(num_sensors=11, track_pool=pool, track_id=i % n, track_width=widths[i % n]), cfg,
             device="cuda")
     info, curve, tallied, top_share, rank1_share = {"steps": [], "rewards": []}, [], [], [], []
@@ -158,8 +166,10 @@ def main():
     ap.add_argument("--no-uniform", action="store_true", help="skip the uniform PPO run")
     ap.add_argument("--out", default="bench_out/curriculum_train.json")
     args = ap.parse_args()
-    if args.episodic and args.evolve:
-        sys.exit("--episodic moves envs between the slots of a fixed table: not with --evolve (DESIGN.md §8)")
+    if args.episodic and args.evolve and not args.partial:
+        sys.exit("--episodic moves envs between the slots of a fixed table, and --evolve on the global path gives a "
+                 "retired slot a new point count and rebuilds that table: pass --partial as well, which evolves the "
+                 "retired slots in place at their own point count (DESIGN.md §4)")
     if args.partial and not args.episodic:
         sys.exit("--partial replaces retired slots under the episodic trainers: pass --episodic as well")
     if not torch.cuda.is_available():
