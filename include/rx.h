@@ -1181,7 +1181,7 @@ int rx_league_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, 
  * assigned, bound single-agent handle. */
 typedef struct rx_track_io {
   int32_t n_tracks;        /* track slots, > 0 */
-  int32_t score;           /* 0 = fail, 1 = potential (scores only) */
+  int32_t score;           /* 0 = fail, 1 = potential (scores only); rx_track_duel_scores: also 2 = lose, 3 = contested */
   const int32_t* track;    /* [N] the slot of env e, env order: rx_state.track (tally only) */
   int64_t* tally;          /* [n_tracks][4] */
   int64_t* cdf;            /* [n_tracks] */
@@ -1199,6 +1199,71 @@ int rx_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double 
 int rx_track_draw_host(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, void* stream);
 int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
                            int32_t precision, void* stream);
+
+/* ABI v25, additive: the TRACK CURRICULUM FOR SELF-PLAY -- the per-slot tallies of
+ * TWO-CAR episodes, so a self-play or league run can answer "on which tracks does the
+ * learner lose" and be redrawn over its slots (rx.track_selfplay).  rx_track_io and its
+ * entry points above are unchanged; the two-car columns live in rx_track_duel_io.  The
+ * arithmetic is csrc/rx_track_duel.h, shared by the kernels (csrc/rx_curriculum.hip)
+ * and the *_host twins; DESIGN.md §4.
+ *
+ * rx_track_tally2 over n two-car envs: a = td->agent is the learner's car, o = 1 - a;
+ * `info` is f64 [n][2][RX_INFO_W], the terminal step's rx_io.info.  Every env e with
+ * done[e] != 0 and 0 <= track[e] < n_tracks is tallied (an env outside that range is
+ * not counted), with pa = info[e][a][RX_INFO_PROGRESS], po = info[e][o][RX_INFO_PROGRESS]
+ * and la = info[e][a][RX_INFO_PLACEMENT]:
+ *   tally[track[e]] (rx_track_io.tally, the single-agent columns for the learner's car):
+ *     episodes += 1;  finishes += (pa == 1.0);
+ *     crashes += (terminated[e] != 0 and pa != 1.0 and po != 1.0): both cars left the
+ *       track, the only way a two-car episode terminates without a finish (a lost race
+ *       is not a crash);
+ *     progress_q += (int64)(pa * 1048576.0)
+ *   duel[track[e]], int64 [n_tracks][RX_TRACK_DUEL_W = 4]:
+ *     wins += (la == 1.0);  opp_finishes += (po == 1.0);
+ *     opp_progress_q += (int64)(po * 1048576.0);  timeouts += (terminated[e] == 0)
+ * Placement 1 is always awarded when an episode ends, so losses = episodes - wins and
+ * are not stored.  The kernel is rx_track_tally's: a wave whose envs all run leaves
+ * after one ballot, the envs that ended are folded per slot inside the wave and one lane
+ * per slot issues at most 8 int64 atomic adds; integer sums, any order of arrival.
+ *
+ * rx_track_duel_scores: rx_track_scores with rx_track_io.score in 0..3 (rx_track_scores
+ * itself keeps accepting 0 and 1):
+ *   0 "fail", 1 "potential":  rx_track_scores' arithmetic on (episodes, finishes), the same bits
+ *   2 "lose":       p_k = (wins + prior) / (episodes + 2 * prior);  q_k = 1 - p_k
+ *   3 "contested":  the same p_k;  q_k = 4 * p_k * (1 - p_k)
+ * f_k, W_k and the exact integer cdf as in rx_track_scores; p[k] receives the p_k used.
+ * rx_track_draw reads cdf only and serves these tables unchanged.
+ *
+ * rx_track_duel_rollout_steps: with lg == NULL rx_selfplay_rollout_steps' contract and
+ * outputs bit for bit; with lg rx_league_rollout_steps', opp_id, draw_count and the
+ * league tally included (the fold of the league draw into the next policy launch stays).
+ * In both cases ONE rx_track_tally2 follows every step's rx_step on `stream`, before the
+ * next step's policy launch, reading that step's done row, io->terminated and io->info
+ * (both required, also with lg == NULL).  No host wait and no allocation: a stream
+ * capture records it.
+ *
+ * All pointers are DEVICE pointers; the *_host twins take HOST pointers, ignore `stream`,
+ * make no HIP call and give the same bits.  Checked before any HIP call (RX_EINVAL, the
+ * message names the field): null pointers, n_tracks <= 0, score outside 0..3 (scores),
+ * agent not 0 or 1, n <= 0, power, prior and precision as above, a handle that is not an
+ * assigned, bound two-car handle with obs_dim 19, td->agent != sp->agent, lg->agent !=
+ * td->agent. */
+#define RX_TRACK_DUEL_W 4
+typedef struct rx_track_duel_io {
+  int32_t agent;  /* the learner's car, 0 or 1 */
+  int64_t* duel;  /* [n_tracks][RX_TRACK_DUEL_W]: wins, opp_finishes, opp_progress_q, timeouts */
+} rx_track_duel_io;
+int rx_track_tally2(const rx_track_io* tc, const rx_track_duel_io* td, int64_t n, const float* done,
+                    const uint8_t* terminated, const double* info, void* stream);
+int rx_track_tally2_host(const rx_track_io* tc, const rx_track_duel_io* td, int64_t n, const float* done,
+                         const uint8_t* terminated, const double* info, void* stream);
+int rx_track_duel_scores(const rx_track_io* tc, const rx_track_duel_io* td, int32_t power, double prior,
+                         void* stream);
+int rx_track_duel_scores_host(const rx_track_io* tc, const rx_track_duel_io* td, int32_t power, double prior,
+                              void* stream);
+int rx_track_duel_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
+                                const rx_league_io* lg, const rx_track_io* tc, const rx_track_duel_io* td,
+                                int32_t precision, void* stream);
 
 /* ABI v25, additive: EPISODIC TRACK DRAWS -- an env takes a new track slot when its own
  * episode ends, as prioritised level replay does, instead of every env being reset at a

@@ -1348,8 +1348,13 @@ static int rollout_loop(const char* fn, rx_env* h, const rx_io* io, const rx_rol
 #ifndef RX_LEAGUE_FOLD
 #define RX_LEAGUE_FOLD 1
 #endif
+// With tc and td, rx_track_duel_rollout_steps: one k_track_tally2 after every step, which reads the
+// done row the step just wrote and the env's terminated / info rows before the next step overwrites
+// them (one stream); with lg the next step's folded draw reads the same info rows, and neither
+// writes them.  The policy and env launches are the same either way.
 static int two_car_rollout_loop(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
-                                const rx_league_io* lg, int32_t precision, void* stream) {
+                                const rx_league_io* lg, int32_t precision, void* stream,
+                                const rx_track_io* tc = nullptr, const rx_track_duel_io* td = nullptr) {
   const int64_t N = h->cfg.n_envs, D = h->D;
   const int q = sp->agent, o = 1 - q;
   hipStream_t hs = (hipStream_t)stream;
@@ -1382,6 +1387,9 @@ static int two_car_rollout_loop(rx_env* h, const rx_io* io, const rx_rollout_io*
     s.reward = sp->env_reward;
     s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;  // dones['__all__'] (wrappers.py:51)
     if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
+    // the envs that ended: count the episode against their track slot
+    if (tc && (rc = rx_launch_track_tally2(tc, td, N, s.done_f32, io->terminated, io->info, hs)) != 0)
+      return fail(RX_EHIP, "track tally launch failed: %s", hipGetErrorString((hipError_t)rc));
     // the envs that ended: count the result against their opponent, draw the next one
     if (lg && (last || !RX_LEAGUE_FOLD) && (rc = rx_launch_league_draw(lg, N, s.done_f32, io->info, hs)) != 0)
       return fail(RX_EHIP, "league draw launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -2415,6 +2423,102 @@ int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, c
     return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
                 !io->terminated ? "terminated" : "info");
   return rollout_loop(fn, h, io, r, tc, precision, stream);
+}
+
+// ABI v25, additive: the track curriculum for self-play (csrc/rx_track_duel.h).  The checks of the
+// three entry points and their host twins, before any HIP call.
+static int track_duel_io(const char* fn, const rx_track_duel_io* td) {
+  if (!td) return fail(RX_EINVAL, "%s: null track duel io", fn);
+  if (td->agent != 0 && td->agent != 1) return fail(RX_EINVAL, "%s: agent=%d must be 0 or 1", fn, td->agent);
+  if (!td->duel) return fail(RX_EINVAL, "%s: null duel", fn);
+  return RX_OK;
+}
+
+static int track_tally2_args(const char* fn, const rx_track_io* tc, const rx_track_duel_io* td, int64_t n,
+                             const float* done, const uint8_t* terminated, const double* info) {
+  int rc = track_args(fn, tc, 0);
+  if (rc || (rc = track_duel_io(fn, td)) != 0) return rc;
+  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
+  if (!done || !terminated || !info)
+    return fail(RX_EINVAL, "%s: null %s", fn, !done ? "done" : !terminated ? "terminated" : "info");
+  return RX_OK;
+}
+
+static int track_duel_scores_args(const char* fn, const rx_track_io* tc, const rx_track_duel_io* td, int32_t power,
+                                  double prior) {
+  if (!tc) return fail(RX_EINVAL, "%s: null track io", fn);
+  if (tc->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, tc->n_tracks);
+  if (!tc->tally || !tc->cdf || !tc->p)
+    return fail(RX_EINVAL, "%s: null %s", fn, !tc->tally ? "tally" : !tc->cdf ? "cdf" : "p");
+  if (tc->score < 0 || tc->score > 3) return fail(RX_EINVAL, "%s: score=%d outside 0..3", fn, tc->score);
+  const int rc = track_duel_io(fn, td);
+  if (rc) return rc;
+  if (power < 0 || power > 4) return fail(RX_EINVAL, "%s: power=%d outside 0..4", fn, power);
+  if (!(prior > 0.0)) return fail(RX_EINVAL, "%s: prior=%g must be > 0", fn, prior);
+  return RX_OK;
+}
+
+int rx_track_tally2(const rx_track_io* tc, const rx_track_duel_io* td, int64_t n, const float* done,
+                    const uint8_t* terminated, const double* info, void* stream) {
+  int rc = track_tally2_args("rx_track_tally2", tc, td, n, done, terminated, info);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_tally2(tc, td, n, done, terminated, info, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_tally2: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_tally2_host(const rx_track_io* tc, const rx_track_duel_io* td, int64_t n, const float* done,
+                         const uint8_t* terminated, const double* info, void* /*stream*/) {
+  const int rc = track_tally2_args("rx_track_tally2_host", tc, td, n, done, terminated, info);
+  if (rc) return rc;
+  rx_host_track_tally2(tc, td, n, done, terminated, info);
+  return RX_OK;
+}
+
+int rx_track_duel_scores(const rx_track_io* tc, const rx_track_duel_io* td, int32_t power, double prior,
+                         void* stream) {
+  int rc = track_duel_scores_args("rx_track_duel_scores", tc, td, power, prior);
+  if (rc) return rc;
+  if ((rc = rx_launch_track_duel_scores(tc, td, power, prior, (hipStream_t)stream)) != 0)
+    return fail(RX_EHIP, "rx_track_duel_scores: launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+int rx_track_duel_scores_host(const rx_track_io* tc, const rx_track_duel_io* td, int32_t power, double prior,
+                              void* /*stream*/) {
+  const int rc = track_duel_scores_args("rx_track_duel_scores_host", tc, td, power, prior);
+  if (rc) return rc;
+  rx_host_track_duel_scores(tc, td, power, prior);
+  return RX_OK;
+}
+
+// the two-car rollout loop with the tally (two_car_rollout_loop); lg: the league's opponents, or null
+int rx_track_duel_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
+                                const rx_league_io* lg, const rx_track_io* tc, const rx_track_duel_io* td,
+                                int32_t precision, void* stream) {
+  const char* fn = "rx_track_duel_rollout_steps";
+  // the track and league ios first: their refusals need no handle (tests/test_track_selfplay_cpu.py)
+  int rc = track_args(fn, tc, 0);
+  if (rc || (rc = track_duel_io(fn, td)) != 0) return rc;
+  if (lg && (rc = league_args(fn, lg, 2)) != 0) return rc;
+  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
+  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
+  if (!io || !r || !sp) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : !r ? "rollout io" : "self-play io");
+  if (!h->assigned || !h->bound || h->cfg.n_agents != 2 || h->D != 19)
+    return fail(RX_EINVAL, "%s: the handle must be an assigned, bound two-car handle with obs_dim 19", fn);
+  if ((rc = rollout_dims(fn, h, r)) != 0) return rc;
+  if (sp->agent != 0 && sp->agent != 1) return fail(RX_EINVAL, "%s: agent=%d must be 0 or 1", fn, sp->agent);
+  if (td->agent != sp->agent)
+    return fail(RX_EINVAL, "%s: agent %d of the track duel io != agent %d of the self-play io", fn, td->agent,
+                sp->agent);
+  if (lg && lg->agent != td->agent)
+    return fail(RX_EINVAL, "%s: agent %d of the league io != agent %d of the track duel io", fn, lg->agent, td->agent);
+  if ((rc = rollout_bufs(fn, r)) != 0 || (rc = selfplay_bufs(fn, sp, lg != nullptr)) != 0) return rc;
+  if (!lg && (rc = precision_arg(fn, "opp_precision", sp->opp_precision)) != 0) return rc;
+  if (!io->terminated || !io->info)
+    return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
+                !io->terminated ? "terminated" : "info");
+  return two_car_rollout_loop(h, io, r, sp, lg, precision, stream, tc, td);
 }
 
 // ABI v25, additive: episodic track draws (rx_track_episode, csrc/rx_curriculum.h).  The checks that

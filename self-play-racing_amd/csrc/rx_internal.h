@@ -374,6 +374,14 @@ extern "C" int rx_launch_track_episode(const rx_track_io* tc, const rx_track_epi
                                        hipStream_t s);
 extern "C" void rx_host_track_episode(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n,
                                       const float* done, const uint8_t* terminated, const double* info);
+// the two-car tally and the scores over its win columns (rx_track_duel.h), on the device and as host loops
+extern "C" int rx_launch_track_tally2(const rx_track_io* tc, const rx_track_duel_io* td, int64_t n, const float* done,
+                                      const uint8_t* terminated, const double* info, hipStream_t s);
+extern "C" int rx_launch_track_duel_scores(const rx_track_io* tc, const rx_track_duel_io* td, int power, double prior,
+                                           hipStream_t s);
+extern "C" void rx_host_track_tally2(const rx_track_io* tc, const rx_track_duel_io* td, int64_t n, const float* done,
+                                     const uint8_t* terminated, const double* info);
+extern "C" void rx_host_track_duel_scores(const rx_track_io* tc, const rx_track_duel_io* td, int power, double prior);
 // rx_track_replay.hip: advantages -> per-slot (samples, mag_q); the score fold; rank + the two integer tables;
 // the three-way env -> slot draw (arguments checked by rx_api.cpp)
 extern "C" int rx_launch_track_learn_tally(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,

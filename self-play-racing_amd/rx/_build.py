@@ -25,7 +25,7 @@ SOURCES = ["rx_kernels.hip", "rx_sort.hip", "rx_optim.hip", "rx_ppo.hip", "rx_tr
 HOST_ONLY = {"rx_raster_host.cpp", "rx_league_host.cpp", "rx_curriculum_host.cpp", "rx_track_replay_host.cpp",
              "rx_track_evolve_host.cpp", "rx_assign_plan_host.cpp"}
 HEADERS = ["rx_internal.h", "rx_math.h", "rx_sincos_table.h", "rx_policy.h", "rx_policy_mfma.h", "rx_spline.h",
-           "rx_raster.h", "rx_league.h", "rx_cull.h", "rx_curriculum.h", "rx_track_replay.h", "rx_track_evolve.h",
+           "rx_raster.h", "rx_league.h", "rx_cull.h", "rx_curriculum.h", "rx_track_duel.h", "rx_track_replay.h", "rx_track_evolve.h",
            "rx_assign_plan.h"]
 
 ARCH = os.environ.get("RX_OFFLOAD_ARCH", "gfx950")

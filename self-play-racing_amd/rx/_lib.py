@@ -48,6 +48,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_track_episode_host", "rx_track_episode_step", "rx_track_episodic_rollout_steps",
            "rx_track_learn_tally_slots", "rx_track_learn_tally_slots_host", "rx_track_learn_episode",
            "rx_track_learn_episode_host", "rx_track_learn_episode_step", "rx_track_learn_episodic_rollout_steps",
+           "rx_track_tally2", "rx_track_tally2_host", "rx_track_duel_scores", "rx_track_duel_scores_host",
+           "rx_track_duel_rollout_steps",
            "rx_steps_plan", "rx_patch_tracks", "rx_patch_tracks_host", "rx_replace_tracks_device", "rx_assign_plan")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
@@ -256,6 +258,15 @@ class RxTrackIO(ctypes.Structure):
                 ("p", _P), ("track_of_env", _P), ("seed", ctypes.c_uint64)]
 
 
+# the track curriculum for self-play (ABI v25, additive): two-car tallies and the win scores (include/rx.h)
+RX_TRACK_DUEL_W = 4
+TRACK_DUEL_SCORES = {"fail": 0, "potential": 1, "lose": 2, "contested": 3}
+
+
+class RxTrackDuelIO(ctypes.Structure):
+    _fields_ = [("agent", ctypes.c_int32), ("duel", _P)]
+
+
 # episodic track draws (ABI v25, additive): an env takes a new slot when its episode ends (include/rx.h)
 RX_TRACK_EPISODE_SALT = 0x9C3B5E2D7F1A8046  # csrc/rx_curriculum.h
 
@@ -435,7 +446,15 @@ def load(build_if_missing=True):
                                                         ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackLearnIO),
                                                         ctypes.POINTER(RxTrackEpisodeIO), ctypes.c_double, _P,
                                                         ctypes.c_int32, _P]
+    L.rx_track_duel_rollout_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxRolloutIO),
+                                              ctypes.POINTER(RxSelfplayIO), ctypes.POINTER(RxLeagueIO),
+                                              ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackDuelIO), ctypes.c_int32,
+                                              _P]
     for sfx in ("", "_host"):
+        td = ctypes.POINTER(RxTrackDuelIO)
+        getattr(L, "rx_track_tally2" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), td, ctypes.c_int64, _P, _P, _P, _P]
+        getattr(L, "rx_track_duel_scores" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), td, ctypes.c_int32,
+                                                             ctypes.c_double, _P]
         getattr(L, "rx_track_episode" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.POINTER(RxTrackEpisodeIO),
                                                          ctypes.c_int64, _P, _P, _P, _P]
         getattr(L, "rx_track_tally" + sfx).argtypes = [ctypes.POINTER(RxTrackIO), ctypes.c_int64, _P, _P, _P, _P]

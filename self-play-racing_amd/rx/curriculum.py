@@ -53,6 +53,26 @@ def check_rules(power, mix, prior, score):
     return int(power), float(mix), float(prior), _score_id(score)
 
 
+def host_fresh_tracks(seed, generation, n):
+    """``n`` fresh host tracks for the slots a resample at ``generation`` retires ->
+    (control points, widths): ``gen_tracks(seed=None)`` and one ``randint(6, 10)`` width
+    each from ``RandomState(seed + 7919 * generation)``, so np.random does not move."""
+    from .track import gen_tracks
+    rng = np.random.RandomState((seed + 7919 * generation) % 2 ** 32)
+    cps = gen_tracks(n, seed=None, rng=rng)
+    return cps, [int(rng.randint(6, 10)) for _ in range(n)]
+
+
+def mastered_slots(episodes, p, refresh, mastery, min_episodes):
+    """Up to floor(refresh * n_tracks) slots with at least ``min_episodes`` episodes and p
+    at least ``mastery``, highest p first, ties by slot (host arrays of one scores call)."""
+    budget = int(math.floor(refresh * len(p)))
+    if budget <= 0:
+        return np.zeros(0, dtype=np.int64)
+    ok = np.nonzero((episodes >= min_episodes) & (p >= mastery))[0]
+    return ok[np.lexsort((ok, -p[ok]))][:budget].astype(np.int64)
+
+
 class TrackCurriculum:
     """The tallies of ``venv``'s track slots and the draw of its envs over them.
 
@@ -268,13 +288,10 @@ class CurriculumPPO(PPO):
         """Up to floor(refresh * n_tracks) slots with enough episodes and p at least the
         mastery, highest p first, ties by slot (from the scores just computed)."""
         cur = self.curriculum
-        budget = int(math.floor(self.refresh * cur.n_tracks))
-        if budget <= 0:
+        if int(math.floor(self.refresh * cur.n_tracks)) <= 0:
             return np.zeros(0, dtype=np.int64)
-        episodes = cur.tally[:, 0].cpu().numpy()
-        p = cur.p.cpu().numpy()
-        ok = np.nonzero((episodes >= self.min_episodes) & (p >= self.mastery))[0]
-        return ok[np.lexsort((ok, -p[ok]))][:budget].astype(np.int64)
+        return mastered_slots(cur.tally[:, 0].cpu().numpy(), cur.p.cpu().numpy(), self.refresh, self.mastery,
+                              self.min_episodes)
 
     def _draw_tracks(self, generation, retired):
         """The slot of every env for ``generation`` (device int32 [N]); ``retired``: the slots
@@ -294,10 +311,7 @@ class CurriculumPPO(PPO):
         pool.  The one place a subclass changes where new tracks come from; here the
         host draw: ``gen_tracks(seed=None)`` and one ``randint(6, 10)`` width each
         from ``RandomState(seed + 7919 * generation)``."""
-        from .track import gen_tracks
-        rng = np.random.RandomState((self.config["seed"] + 7919 * generation) % 2 ** 32)
-        new_cps = gen_tracks(len(retired), seed=None, rng=rng)
-        new_widths = [int(rng.randint(6, 10)) for _ in range(len(retired))]
+        new_cps, new_widths = host_fresh_tracks(self.config["seed"], generation, len(retired))
         return self._replace_tracks(generation, retired, new_cps, new_widths)
 
     def resample_tracks(self, control_points=None, widths=None):
@@ -347,12 +361,21 @@ def format_track_table(table, limit=None):
     order = np.lexsort((np.arange(len(table["p"])), table["p"]))
     if limit is not None:
         order = order[:limit]
-    lines = [f"{'slot':>6} {'episodes':>9} {'finishes':>9} {'crashes':>9} {'progress':>9} {'p':>7} {'prob':>9}"]
+    duel = "wins" in table  # a two-car table (rx.track_selfplay): the win columns follow
+    head = f"{'slot':>6} {'episodes':>9} {'finishes':>9} {'crashes':>9} {'progress':>9} {'p':>7} {'prob':>9}"
+    if duel:
+        head += f" {'wins':>9} {'win rate':>9} {'opp fin':>9} {'opp prog':>9} {'timeouts':>9}"
+    lines = [head]
+    num = lambda x: "-" if np.isnan(x) else f"{x:.3f}"  # noqa: E731
     for k in order:
-        mp = table["mean_progress"][k]
-        lines.append(f"{k:>6} {table['episodes'][k]:>9} {table['finishes'][k]:>9} {table['crashes'][k]:>9} "
-                     f"{'-' if np.isnan(mp) else f'{mp:.3f}':>9} {table['p'][k]:>7.3f} {table['prob'][k]:>9.2e}")
+        line = (f"{k:>6} {table['episodes'][k]:>9} {table['finishes'][k]:>9} {table['crashes'][k]:>9} "
+                f"{num(table['mean_progress'][k]):>9} {table['p'][k]:>7.3f} {table['prob'][k]:>9.2e}")
+        if duel:
+            line += (f" {table['wins'][k]:>9} {num(table['win_rate'][k]):>9} {table['opp_finishes'][k]:>9} "
+                     f"{num(table['opp_mean_progress'][k]):>9} {table['timeouts'][k]:>9}")
+        lines.append(line)
     return "\n".join(lines)
 
 
-__all__ = ["TrackCurriculum", "CurriculumStepRollout", "CurriculumPPO", "format_track_table", "check_rules"]
+__all__ = ["TrackCurriculum", "CurriculumStepRollout", "CurriculumPPO", "format_track_table", "check_rules",
+           "host_fresh_tracks", "mastered_slots"]

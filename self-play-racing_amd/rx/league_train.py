@@ -253,7 +253,7 @@ class LeagueSelfPlayPPO(SelfPlayPPO):
         else:
             self.envs.weights(n_live, self.pfsp_power, self.pfsp_mix, self.pfsp_prior)
             self.envs.draw_all()
-        self.envs.reset_device()
+        self._rebuild_envs()
 
     def collect_rollout(self, *bufs):
         # SelfPlayPPO's one captured graph per opponent kind; here the kind is random vs bank

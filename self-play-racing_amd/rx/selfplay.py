@@ -177,6 +177,11 @@ class SelfPlayPPO(PPO):
             from . import ppo_fused
             fused = self.config.get("fused_policy", True)
             self.envs.set_opponent(self._opp_static, self._opp_flat if fused else None, ppo_fused.precision(self.config))
+        self._rebuild_envs()
+
+    def _rebuild_envs(self):
+        """The env rebuild that ends ``update_opponent``: every env is reset (rx.track_selfplay
+        redraws the envs over the track slots here instead, at its boundaries)."""
         self.envs.reset_device()
 
     def _step_rollout(self, obs):

@@ -2,6 +2,7 @@
 
     python tools/league_train.py --envs 8192 --steps 128 --updates 40
     python tools/league_train.py --envs 64 --steps 32 --updates 6 --snapshot-freq 1 --pool-size 3
+    python tools/league_train.py --curriculum --track-resample-every 2 --tracks 64 --envs 8192 --steps 128 --updates 12
 
 SelfPlayPPO's loop with the opponent pool in a device bank: per env an opponent
 drawn from the pool, weighted towards the snapshots the learner still loses to
@@ -9,6 +10,11 @@ drawn from the pool, weighted towards the snapshots the learner still loses to
 counted on the device.  The learner's head-to-head record against the pool is
 printed at the end and written to ``--out`` as JSON; ``--save`` also writes a
 checkpoint that tools/league.py reads.
+
+``--curriculum`` trains rx.track_selfplay.LeagueCurriculumPPO instead: every finished
+episode is also counted against its track slot, every ``--track-resample-every`` updates
+the envs are redrawn over the ``--tracks`` slots towards the tracks the learner still loses
+on (``--curriculum-score``), and the per-track table is printed beside the head-to-head one.
 """
 import argparse
 import json
@@ -38,7 +44,15 @@ def main():
     ap.add_argument("--resume", default=None, help="a checkpoint of an earlier run")
     ap.add_argument("--save", default=None, help="write a checkpoint here at the end")
     ap.add_argument("--out", default="bench_out/league_train.json")
+    ap.add_argument("--curriculum", action="store_true", help="tally per track slot and resample (rx.track_selfplay)")
+    ap.add_argument("--track-resample-every", type=int, default=0, metavar="K",
+                    help="with --curriculum: redraw the envs over the slots every K updates (0: tally only)")
+    ap.add_argument("--tracks", type=int, default=0, metavar="N",
+                    help="distinct tracks in the pool, env i on track i %% N (default: one per env)")
+    ap.add_argument("--curriculum-score", default="lose", choices=("fail", "potential", "lose", "contested"))
     args = ap.parse_args()
+    if not args.curriculum and args.track_resample_every:
+        ap.error("--track-resample-every needs --curriculum")
     from rx.configs import self_play_config
     from rx.envs import MultiRacingEnv
     from rx.league_train import LeagueSelfPlayPPO, format_head_to_head
@@ -51,20 +65,39 @@ def main():
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
-    pool = gen_tracks(args.envs, seed=args.seed)
-    widths = [np.random.randint(6, 10) for _ in range(args.envs)]
-    t = LeagueSelfPlayPPO(lambda i: MultiRacingEnv(2, 11, pool, i, widths), cfg, device="cuda")
+    n_tracks = args.tracks if args.tracks > 0 else args.envs
+    if args.tracks > 0:  # N distinct tracks (the seeded pool below repeats after a few)
+        rng = np.random.RandomState(args.seed)
+        pool = gen_tracks(n_tracks, seed=None, rng=rng)
+        widths = [int(rng.randint(6, 10)) for _ in range(n_tracks)]
+    else:
+        pool = gen_tracks(n_tracks, seed=args.seed)
+        widths = [np.random.randint(6, 10) for _ in range(n_tracks)]
+    cls = LeagueSelfPlayPPO
+    if args.curriculum:
+        from rx.track_selfplay import LeagueCurriculumPPO, format_track_table
+        cls = LeagueCurriculumPPO
+        cfg.update(track_resample_every=args.track_resample_every, curriculum_score=args.curriculum_score)
+    t = cls(lambda i: MultiRacingEnv(2, 11, pool, i % n_tracks, widths), cfg, device="cuda")
     update = gstep = -1
     info = None
     for update, num_updates, gstep, ep, info in t.train_iter(resume_from=args.resume):
         t._log(update, num_updates, gstep, ep, info, extra=f" | Pool Size: {len(t.opponent_pool)}")
     rows = t.head_to_head()
     print(format_head_to_head(rows))
+    tracks = None
+    if args.curriculum:
+        table = t.track_table()
+        print(format_track_table(table, limit=32))
+        tracks = {k: [None if isinstance(x, float) and np.isnan(x) else x for x in v.tolist()]
+                  for k, v in table.items()}
+        tracks["generation"], tracks["retired"] = t.envs.venv.track_generation, t.retired
     if args.save and update >= 0:
         print("checkpoint:", t.save_checkpoint(update, gstep, info, path=args.save))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
-        json.dump({"config": json.loads(json.dumps(cfg)), "updates": update + 1, "head_to_head": rows}, f, indent=1)
+        json.dump({"config": json.loads(json.dumps(cfg)), "updates": update + 1, "head_to_head": rows,
+                   **({"tracks": tracks} if tracks is not None else {})}, f, indent=1)
     print("->", args.out)
     t.envs.close()
 
