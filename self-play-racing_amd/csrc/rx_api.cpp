@@ -1,30 +1,20 @@
-// rx_api.cpp -- C ABI (include/rx.h): handle lifetime, argument validation,
-// track-table upload, env->wavefront grouping, launches.
+// rx_api.cpp -- C ABI (include/rx.h): what owns or mutates the handle.  The error state, handle
+// lifetime, track-table upload, env->wavefront grouping, state binding, the step's launches
+// and rx_steps.  The other entry points: rx_api_loops.cpp (rollout, eval and match loops),
+// rx_api_train.cpp (GAE, Adam, PPO, policies), rx_api_tracks.cpp (track and culling tables,
+// rasteriser), rx_api_curriculum.cpp (league and track curriculum); rx_handle.h joins them.
 //
 // Everything that allocates or copies synchronously (rx_upload_tracks,
 // rx_assign) happens outside the step path; rx_reset / rx_step / rx_gae only
 // enqueue kernels on the caller's stream, so they can be graph-captured.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <numeric>
 #include <type_traits>
-#include <string>
-#include <vector>
 
-#include "rx.h"
-#include "rx_cull.h"
-#include "rx_internal.h"
-#include "rx_spline.h"
+#include "rx_handle.h"
 
-namespace {
-
-thread_local std::string g_err;
+static thread_local std::string g_err;
 
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -36,199 +26,15 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define RX_HIP(call)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess) return fail(RX_EHIP, "%s: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
-
-// a device allocation that frees itself (on the current device: rx_destroy sets the handle's)
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-
-// room for n elements: the buffer is kept when it is large enough (its address then stays)
-template <class T>
-int reserve(DevBuf<T>& b, size_t n) {
-  if (n > b.n) {
-    b.release();
-    if (hipMalloc(&b.p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
-      b.p = nullptr;
-      return fail(RX_ENOMEM, "hipMalloc(%zu bytes) failed", n * sizeof(T));
-    }
-    b.n = n;
-  }
-  return RX_OK;
-}
-
-template <class T>
-int upload(DevBuf<T>& b, const T* host, size_t n) {
-  const int rc = reserve(b, n);
-  if (rc != RX_OK) return rc;
-  if (n) RX_HIP(hipMemcpy(b.p, host, n * sizeof(T), hipMemcpyHostToDevice));
-  return RX_OK;
-}
-
-}  // namespace
-
-#define RX_WORK_ARRAYS 14  // device arrays of one working rx_state (rx_bind_state)
-
-struct rx_env {
-  rx_config cfg{};
-  int D = 0;
-  // track table
-  int32_t n_tracks = 0;
-  std::vector<int32_t> wp_off_h;
-  DevBuf<int32_t> wp_off;
-  DevBuf<double> wp, nrm, seg, meta;
-  // raycast culling tables (derived from the track table)
-  DevBuf<int32_t> chunk_off;
-  DevBuf<double> chunk_box, slot_geo, wchunk_box;
-  DevBuf<int32_t> wchunk_off;
-  DevBuf<int32_t> super_off;  // two-level culling: super-chunk boxes per slot
-  DevBuf<double> super_box;
-  DevBuf<int32_t> wsuper_off;  // two-level closest-waypoint culling
-  DevBuf<double> wsuper_box;
-  DevBuf<float> chunk_box_f, super_box_f;  // outward-rounded float32 copies (raycast box tests) + 4 quadrant blocks
-  int32_t n_chunk_boxes = 0, n_super_boxes = 0;
-  DevBuf<float> seg_f;  // [2*Wtot][4] float32 (start.x, start.y, v2.x, v2.y): the raycast's segment pre-filter
-  DevBuf<rx_slot_hdr> slot_hdr;  // [n] per-slot headers (lane-varying kernels)
-  // assignment
-  bool assigned = false;
-  DevBuf<int32_t> perm[2];  // the env order (perm[0]: env id at each position) and the re-sort's shadow
-  DevBuf<rx_wave> dyn_waves, ray_waves;
-  std::vector<rx_wave> ray_waves_h;  // host copy of the ray-wave table (rx_ray_waves)
-  DevBuf<int32_t> slot_n;   // envs per slot (ray-major decode)
-  DevBuf<uint32_t> resets;  // per-env reset count: keys the 2-car start-slot draw (graph-replay safe)
-  // rx_set_start_draws: the caller's MT19937 outputs and cursor; ranks of the resetting envs
-  const uint32_t* draws = nullptr;
-  int64_t n_draws = 0;
-  int64_t* draw_cursor = nullptr;
-  DevBuf<int32_t> draw_rank, draw_tmp;
-  DevBuf<int64_t> draw_base;
-  rx_sched sched;  // the schedule the assignment resolved (rx_assign_plan.h): written whole, after the last upload
-  DevBuf<int32_t> pos_slot;                // with lane_tracks: [N] slot of the env at each position
-  DevBuf<int32_t> env_pos;                 // with lane_tracks: [N] position of each env, the inverse of perm
-                                           // (rx_track_episode_step: the episodic draw rewrites pos_slot)
-  DevBuf<uint8_t> policy_frag;  // the bf16 rollout's operand fragments of both trunks (k_policy_frag, rx_rollout_steps)
-  DevBuf<double> rel_angles;
-  std::vector<double> rel_angles_h;
-  // spatial sort (scheduling only)
-  DevBuf<uint32_t> keys_in;              // [N] bin per perm position (REWARD half)
-  DevBuf<uint32_t> keys_off;             // [N] the position's rank within its bin (the count's atomic)
-  bool sort_pending = false;             // keys written, the re-sort runs after this step's raycast
-  bool sort_hist_done = false;           // the REWARD half of the keys' launch also counted the bins
-  DevBuf<uint32_t> sort_hist, sort_cursor;  // [sort_bins]
-  DevBuf<int32_t> sort_base;             // [n_tracks] first bin of each slot
-  uint64_t dyn_calls = 0;
-  // ray-task direction sort (ray_order 2): every RX_TASK_SORT_INTERVAL dynamics
-  // launches, and always on the first launch after a block's membership changed
-  bool tasks_stale = true;
-  uint64_t task_calls = 0;
-  // ray_order 2: direction-sorted (agent, ray) task ids, rewritten by k_dyn every step
-  DevBuf<int32_t> tasks;
-  // split step (k_kin1 + k_step2): cos / sin of the stepped angles
-  DevBuf<double> cs_scratch;
-  // rx_steps' carrying schedule: rings of snapshots of what the ray waves read -- the stepped
-  // pose ([3][N] x, y, angle) and the sorted task ids -- written by a step's KIN part, and a
-  // shadow of the obs rows for every ray step of a launch but its newest, which would write
-  // the same rows (stride-0 outputs); the task rows are written by the RANK workgroups of the
-  // deep launch (rx_internal.h)
-  DevBuf<double> snap_pose[RX_PAIR_RING];
-  DevBuf<int32_t> snap_tasks[RX_TASK_RING];
-  DevBuf<float> obs_shadow[RX_SHADOW_ROWS];
-  DevBuf<int32_t> snap_rows[RX_CROSS_RING];  // the crossing step's row ids and visiting-order hint (pre-sort)
-  DevBuf<double> snap_hint[RX_CROSS_RING];
-  // rx_profile: per recorded launch, [RX_PROF_SLOTS] wave start + [RX_PROF_SLOTS] wave end stamps
-  bool prof = false;
-  DevBuf<unsigned long long> prof_buf;
-  std::vector<int> prof_kinds;
-  // state: the caller's arrays (env order, rx_bind_state) and the engine's
-  // working copy in wave order (position p = env perm[p]; the kernels read and
-  // write it coalesced) plus the shadow the re-sort moves rows into
-  bool bound = false;
-  rx_state st{};
-  rx_state work{}, work_tmp{};
-  DevBuf<uint8_t> work_mem[2 * RX_WORK_ARRAYS];  // the arrays of work and work_tmp
-};
-
-namespace {
-// ---- culling tables (csrc/rx_cull.h) ------------------------------------------
-// What the host can check of a culling-table build, and the offsets: off receives
-// wp_off and the chunk / super / wchunk / wsuper offset arrays back to back
-// (n + 1 entries each), tot the four box totals.  sizes_only: the offsets alone are
-// checked (rx_cull_table_sizes; rx_upload_tracks_device, whose arrays are the handle's).
-int cull_check(const char* fn, int32_t n, const int32_t* wp_off, const void* wp, const void* seg, const void* meta,
-               int32_t G, int32_t SG, const rx_cull_tables* out, bool sizes_only, std::vector<int32_t>* off,
-               int64_t tot[4]) {
-  if (n <= 0) return fail(RX_EINVAL, "%s: n_tracks must be > 0 (got %d)", fn, n);
-  if (!wp_off) return fail(RX_EINVAL, "%s: wp_off is null", fn);
-  if (!sizes_only) {
-    if (!wp) return fail(RX_EINVAL, "%s: wp is null", fn);
-    if (!seg) return fail(RX_EINVAL, "%s: seg is null", fn);
-    if (!meta) return fail(RX_EINVAL, "%s: meta is null", fn);
-    if (!out) return fail(RX_EINVAL, "%s: out is null", fn);
-    const struct {
-      const void* p;
-      const char* name;
-      bool need;
-    } fields[] = {{out->seg_f, "seg_f", true},
-                  {out->slot_hdr, "slot_hdr", true},
-                  {out->chunk_off, "chunk_off", G > 0},
-                  {out->wchunk_off, "wchunk_off", G > 0},
-                  {out->wsuper_off, "wsuper_off", G > 0},
-                  {out->chunk_box, "chunk_box", G > 0},
-                  {out->wchunk_box, "wchunk_box", G > 0},
-                  {out->wsuper_box, "wsuper_box", G > 0},
-                  {out->slot_geo, "slot_geo", G > 0},
-                  {out->chunk_box_f, "chunk_box_f", G > 0},
-                  {out->super_off, "super_off", G > 0 && SG > 0},
-                  {out->super_box, "super_box", G > 0 && SG > 0},
-                  {out->super_box_f, "super_box_f", G > 0 && SG > 0}};
-    for (const auto& f : fields)
-      if (f.need && !f.p) return fail(RX_EINVAL, "%s: out->%s is null", fn, f.name);
-  }
-  if (SG < 0 || SG > RX_CULL_MAX_SUPER)
-    return fail(RX_EINVAL, "%s: cull_super must be 0 .. %d (got %d)", fn, RX_CULL_MAX_SUPER, SG);
-  if (wp_off[0] != 0) return fail(RX_EINVAL, "%s: wp_off[0] must be 0 (got %d)", fn, wp_off[0]);
-  const size_t n1 = (size_t)n + 1;
-  if (off) off->assign(5 * n1, 0);
-  int64_t run[4] = {0, 0, 0, 0};
-  for (int32_t k = 0; k < n; ++k) {
-    const int64_t W = (int64_t)wp_off[k + 1] - wp_off[k];
-    if (W < 2) return fail(RX_EINVAL, "%s: track %d has W = %lld waypoints (need >= 2)", fn, k, (long long)W);
-    if (W > RX_CULL_MAX_W)
-      return fail(RX_EINVAL, "%s: track %d has W = %lld waypoints (at most %d)", fn, k, (long long)W, RX_CULL_MAX_W);
-    const rx_cull_counts c = rx_cull_slot_counts((int32_t)W, G, SG);
-    const int32_t add[4] = {c.leaf, c.super, c.wchunk, c.wsuper};
-    for (int a = 0; a < 4; ++a) {
-      run[a] += add[a];
-      if (run[a] > INT32_MAX)
-        return fail(RX_EINVAL, "%s: track %d: the box count overflows the int32 offsets", fn, k);
-      if (off) (*off)[(a + 1) * n1 + k + 1] = (int32_t)run[a];
-    }
-    if (off) (*off)[k + 1] = wp_off[k + 1];
-  }
-  for (int a = 0; a < 4; ++a) tot[a] = run[a];
-  return RX_OK;
+int launched(const char* fn, int rc) {
+  return rc ? fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc)) : RX_OK;
 }
 
 // Culling tables for every slot (rx_cull.h through the host twin): chunks of G
 // consecutive boundary segments per side, their end-point boxes, per slot the
 // bounding circle of all boundary points and the longest segment (kernel margins,
 // DESIGN.md §3), the float32 copies and the per-slot headers.
-int build_chunks(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* seg,
+static int build_chunks(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* seg,
                  const double* meta) {
   const int G = h->cfg.cull_chunk, SG = h->cfg.cull_super;  // SG: leaves per super-chunk (0 = one level)
   int64_t tot[4];
@@ -264,9 +70,6 @@ int build_chunks(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const doubl
   }
   return upload(h->slot_hdr, hd.data(), hd.size());
 }
-}  // namespace
-
-extern "C" {
 
 const char* rx_last_error(void) { return g_err.c_str(); }
 int rx_abi_version(void) { return RX_ABI_VERSION; }
@@ -578,7 +381,7 @@ static void prof_arm(rx_env* h, rx_kargs& a, int kind) {
   h->prof_kinds.push_back(kind);
 }
 
-static void make_kargs(rx_env* h, const rx_io* io, int mode, const uint8_t* mask, rx_kargs& a) {
+void make_kargs(rx_env* h, const rx_io* io, int mode, const uint8_t* mask, rx_kargs& a) {
   a.tr = rx_track_view{h->wp_off.p,    h->wp.p,        h->nrm.p,      h->seg.p,        h->meta.p,
                        h->chunk_off.p, h->chunk_box.p, h->slot_geo.p, h->wchunk_off.p, h->wchunk_box.p,
                        h->super_off.p, h->super_box.p, h->wsuper_off.p, h->wsuper_box.p,
@@ -686,7 +489,7 @@ static int sort_envs_now(rx_env* h, hipStream_t s) {
   return RX_OK;
 }
 
-static int launch(rx_env* h, const rx_io* io, int mode, const uint8_t* mask, void* stream, int phases = 3) {
+int launch(rx_env* h, const rx_io* io, int mode, const uint8_t* mask, void* stream, int phases) {
   if (phases < 1 || phases > 3) return fail(RX_EINVAL, "phases must be 1, 2 or 3 (got %d)", phases);
   if (!h) return fail(RX_EINVAL, "null handle");
   if (!io) return fail(RX_EINVAL, "io is null");
@@ -1205,503 +1008,8 @@ int rx_steps(rx_env* h, const rx_io* io, int32_t n_steps, const rx_io_strides* s
   return RX_OK;
 }
 
-// rx_rollout: the persistent small-N rollout (k_rollout) on a handle in the
-// one-env-per-wave configuration; the per-step io pointers are set in-kernel.
-static int max_waypoints(const rx_env* h) {
-  int m = 0;
-  for (int k = 0; k < h->n_tracks; ++k) m = std::max(m, h->wp_off_h[k + 1] - h->wp_off_h[k]);
-  return m;
-}
-
-int rx_rollout_supported(const rx_env* h) {
-  return h && h->assigned && h->bound && h->cfg.n_agents == 1 && h->sched.dyn_lpe == 64 && (h->D == 15 || h->D == 19) &&
-         max_waypoints(h) <= RX_ROLLOUT_MAX_W;
-}
-
-// ---- the step loops: the argument checks of their entry points, each written once.
-// fn is the entry point's name; every check returns before any HIP call.
-static int precision_arg(const char* fn, const char* field, int32_t precision) {
-  if (precision != RX_PREC_FP32 && precision != RX_PREC_BF16)
-    return fail(RX_EINVAL, "%s: %s=%d (RX_PREC_FP32 or RX_PREC_BF16)", fn, field, precision);
-  return RX_OK;
-}
-
-static int rollout_dims(const char* fn, const rx_env* h, const rx_rollout_io* r) {
-  if (r->T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, r->T);
-  if (r->obs_dim != h->D) return fail(RX_EINVAL, "%s: obs_dim %d != the handle's %d", fn, r->obs_dim, h->D);
-  return RX_OK;
-}
-
-static int rollout_bufs(const char* fn, const rx_rollout_io* r) {
-  const char* null = !r->params ? "params" : !r->log_std ? "log_std" : !r->eps ? "eps" : !r->obs ? "obs"
-                     : !r->actions ? "actions" : !r->logprobs ? "logprobs" : !r->values ? "values"
-                     : !r->rewards ? "rewards" : !r->dones ? "dones" : !r->next_obs ? "next_obs"
-                     : !r->next_done ? "next_done" : nullptr;
-  return null ? fail(RX_EINVAL, "%s: null rollout buffer %s", fn, null) : RX_OK;
-}
-
-// bank: the opponents' parameters come from a league io, so opp_params / opp_log_std are not read
-static int selfplay_bufs(const char* fn, const rx_selfplay_io* sp, bool bank) {
-  const char* null = !bank && !sp->opp_params ? "opp_params" : !bank && !sp->opp_log_std ? "opp_log_std"
-                     : !sp->opp_eps ? "opp_eps" : !sp->env_actions ? "env_actions" : !sp->env_obs ? "env_obs"
-                     : !sp->env_reward ? "env_reward" : !sp->sink ? "sink" : nullptr;
-  return null ? fail(RX_EINVAL, "%s: null self-play buffer %s", fn, null) : RX_OK;
-}
-
-// the evaluation record, and the io rows k_eval_acc reads
-static int record_args(const char* fn, const rx_io* io, const double* acc, const uint8_t* active,
-                       const int32_t* n_active) {
-  if (!acc || !active || !n_active)
-    return fail(RX_EINVAL, "%s: null %s", fn, !acc ? "acc" : !active ? "active" : "n_active");
-  if (!io->obs || !io->reward64 || !io->info || !io->done_f32)
-    return fail(RX_EINVAL, "%s: null io->%s", fn,
-                !io->obs ? "obs" : !io->reward64 ? "reward64" : !io->info ? "info" : "done_f32");
-  return RX_OK;
-}
-
-// bf16 with parameters that are fixed for the whole call: their operand fragments are built once
-// (k_policy_frag) and every step's policy launch reads them -- the same bf16 values rx_policy_act
-// converts per use.  *frag stays null for fp32.
-static int policy_fragments(const char* fn, rx_env* h, int32_t obs_dim, const float* params, int32_t precision,
-                            hipStream_t s, const void** frag) {
-  *frag = nullptr;
-  if (precision != RX_PREC_BF16) return RX_OK;
-  if (rx_launch_policy_frag(obs_dim, params, h->policy_frag.p, s))
-    return fail(RX_EHIP, "%s: fragment launch failed", fn);
-  *frag = h->policy_frag.p;
-  return RX_OK;
-}
-
-int rx_rollout(rx_env* h, const rx_io* io, const rx_rollout_io* r, void* stream) {
-  if (!h || !io || !r) return fail(RX_EINVAL, "rx_rollout: null argument");
-  if (!rx_rollout_supported(h))
-    return fail(RX_ESTATE, "rx_rollout: needs an assigned, bound single-agent handle in the small-N (one env per "
-                           "wave) configuration with 15 or 19 observation columns and <= %d waypoints per slot",
-                RX_ROLLOUT_MAX_W);
-  int rc;
-  if ((rc = rollout_dims("rx_rollout", h, r)) != 0 || (rc = rollout_bufs("rx_rollout", r)) != 0) return rc;
-  if (h->sched.n_dyn_waves != h->cfg.n_envs) return fail(RX_ESTATE, "rx_rollout: expected one env per dynamics wave");
-  rx_kargs a{};
-  make_kargs(h, io, RX_MODE_STEP, nullptr, a);
-  a.sort_keys = nullptr;
-  a.tasks_out = nullptr;
-  a.prof_ts = nullptr;
-  if ((rc = rx_launch_rollout(&a, r, max_waypoints(h), (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "k_rollout launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-// The single-agent rollout loop: per step rx_policy_act on obs[t], then rx_step of actions[t] writing
-// obs[t + 1], rewards[t] and dones[t + 1] (next_obs / next_done after the last).  tc == null is
-// rx_rollout_steps; with tc, rx_track_rollout_steps: one k_track_tally after every step, which reads
-// the done row the step just wrote and the env's terminated / info rows before the next step
-// overwrites them (one stream).  The policy and env launches are the same either way.
-// With ep as well, rx_track_episodic_rollout_steps: k_track_episode in the tally's place, so an env
-// that ended in step t is reset by step t + 1 from the slot it just drew; slots: [T][N] or null.
-// With lt too, rx_track_learn_episodic_rollout_steps: k_track_learn_episode in that launch's place.
-static int rollout_loop(const char* fn, rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
-                        int32_t precision, void* stream, const rx_track_episode_io* ep = nullptr,
-                        int32_t* slots = nullptr, const rx_track_learn_io* lt = nullptr, double stale_mix = 0.0) {
-  const int64_t N = h->cfg.n_envs, D = h->D;
-  hipStream_t hs = (hipStream_t)stream;
-  const void* frag;
-  int rc = policy_fragments(fn, h, r->obs_dim, r->params, precision, hs, &frag);
-  if (rc) return rc;
-  for (int32_t t = 0; t < r->T; ++t) {
-    const bool last = t + 1 == r->T;
-    const rx_policy_io pio{r->obs_dim, N, r->obs + t * N * D, r->eps + t * N * 2, r->params, r->log_std,
-                           r->actions + t * N * 2, r->logprobs + t * N, r->values + t * N, 0, 0, precision,
-                           nullptr, 0};
-    if ((rc = rx_launch_policy_act(&pio, hs, frag)) != 0)
-      return fail(RX_EHIP, "%s: policy launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-    rx_io s = *io;
-    s.actions = r->actions + t * N * 2;
-    s.obs = last ? r->next_obs : r->obs + (t + 1) * N * D;
-    s.reward = r->rewards + t * N;
-    s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;
-    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
-    if (ep) {
-      rx_track_episode_io e = *ep;
-      e.slot_out = slots ? slots + t * N : nullptr;
-      rc = lt ? rx_launch_track_learn_episode(tc, lt, &e, stale_mix, N, s.done_f32, io->terminated, io->info, hs)
-              : rx_launch_track_episode(tc, &e, N, s.done_f32, io->terminated, io->info, hs);
-      if (rc != 0) return fail(RX_EHIP, "%s: episode launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-    } else if (tc && (rc = rx_launch_track_tally(tc, N, s.done_f32, io->terminated, io->info, hs)) != 0)
-      return fail(RX_EHIP, "%s: tally launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-  }
-  return RX_OK;
-}
-
-// The two-car rollout loop: per step ONE launch for both policies, then rx_step on the env's own
-// buffers; one agent-row copy after the last step.  The opponent's actor runs on its rows of the
-// env's observation buffer (wrappers.py:36-39), actions into its slot of the env's action buffer;
-// the learning agent on obs[t] -- the caller's rows at t = 0 (they may predate an env rebuild),
-// afterwards its rows of the env's buffer, which the launch also copies into obs[t] together with
-// the agent's reward of step t - 1 -- actions into the rollout row and its env slot.
-// lg == null is rx_selfplay_rollout_steps (k_selfplay_act, one frozen opponent).  With lg,
-// rx_league_rollout_steps (k_league_act): env e's opponent is bank member lg->opp_id[e], the
-// opponent's params / log_std are the bank bases, and the tally and redraw of step t's done flags
-// is folded into step t + 1's launch (its opponent waves are the only readers of the ids), so one
-// k_league_draw per rollout remains, for the last step.  RX_LEAGUE_FOLD=0 (an A/B build,
-// tools/bench_league_train.py) launches k_league_draw after every step instead: the same bits,
-// one more launch per step.
-#ifndef RX_LEAGUE_FOLD
-#define RX_LEAGUE_FOLD 1
-#endif
-// With tc and td, rx_track_duel_rollout_steps: one k_track_tally2 after every step, which reads the
-// done row the step just wrote and the env's terminated / info rows before the next step overwrites
-// them (one stream); with lg the next step's folded draw reads the same info rows, and neither
-// writes them.  The policy and env launches are the same either way.
-static int two_car_rollout_loop(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
-                                const rx_league_io* lg, int32_t precision, void* stream,
-                                const rx_track_io* tc = nullptr, const rx_track_duel_io* td = nullptr) {
-  const int64_t N = h->cfg.n_envs, D = h->D;
-  const int q = sp->agent, o = 1 - q;
-  hipStream_t hs = (hipStream_t)stream;
-  int rc;
-  for (int32_t t = 0; t < r->T; ++t) {
-    const bool last = t + 1 == r->T;
-    const rx_policy_io opp{(int32_t)D, N, sp->env_obs + o * D, sp->opp_eps + t * N * 2,
-                           lg ? lg->params : sp->opp_params, lg ? lg->log_std : sp->opp_log_std,
-                           sp->env_actions + 2 * o, nullptr, sp->sink, 2 * D, 4,
-                           lg ? lg->opp_precision : sp->opp_precision, nullptr, 0};
-    const rx_policy_io pio{(int32_t)D, N, t == 0 ? r->obs : sp->env_obs + q * D, r->eps + t * N * 2, r->params,
-                           r->log_std, r->actions + t * N * 2, r->logprobs + t * N, r->values + t * N,
-                           t == 0 ? 0 : 2 * D, 0, precision, sp->env_actions + 2 * q, 4};
-    float* obs_out = t == 0 ? nullptr : r->obs + t * N * D;
-    float* rew_out = t == 0 ? nullptr : r->rewards + (t - 1) * N;
-    if (lg) {
-      // io->info still holds step t - 1's rows here: rx_step writes it after this launch
-      const bool fold = RX_LEAGUE_FOLD && t > 0;
-      rc = rx_launch_league_act(&pio, &opp, lg, fold ? r->dones + t * N : nullptr, fold ? io->info : nullptr,
-                                obs_out, sp->env_reward, rew_out, hs);
-    } else {
-      rc = rx_launch_selfplay_act(&pio, &opp, obs_out, sp->env_reward, rew_out, q, hs);
-    }
-    if (rc)
-      return fail(RX_EHIP, "%s policy launch failed: %s", lg ? "league" : "self-play",
-                  hipGetErrorString((hipError_t)rc));
-    rx_io s = *io;
-    s.actions = sp->env_actions;
-    s.obs = sp->env_obs;
-    s.reward = sp->env_reward;
-    s.done_f32 = last ? r->next_done : r->dones + (t + 1) * N;  // dones['__all__'] (wrappers.py:51)
-    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
-    // the envs that ended: count the episode against their track slot
-    if (tc && (rc = rx_launch_track_tally2(tc, td, N, s.done_f32, io->terminated, io->info, hs)) != 0)
-      return fail(RX_EHIP, "track tally launch failed: %s", hipGetErrorString((hipError_t)rc));
-    // the envs that ended: count the result against their opponent, draw the next one
-    if (lg && (last || !RX_LEAGUE_FOLD) && (rc = rx_launch_league_draw(lg, N, s.done_f32, io->info, hs)) != 0)
-      return fail(RX_EHIP, "league draw launch failed: %s", hipGetErrorString((hipError_t)rc));
-  }
-  // the last step's agent rows: next_obs and rewards[T - 1]
-  rc = rx_launch_agent_rows((int)N, (int)D, q, sp->env_obs, sp->env_reward, r->next_obs, r->rewards + (r->T - 1) * N,
-                            hs);
-  if (rc) return fail(RX_EHIP, "agent-row copy launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-// The accumulating loop of an evaluation: per step the policy launch (if any), rx_step of actions[t]
-// in place, k_eval_acc.  ev.params == null is open loop (the caller's actions); with m the policy
-// launch is the bank's (car q of env e on policy m->seat[e][q]), else rx_policy_act over all N * A
-// rows -- both cars of a two-car env are rows of the same launch: one policy drives them
-// (utils/metrics.py:94-101).  ev holds the fields rx_eval_io and rx_match_io share.
-static int record_loop(const char* fn, rx_env* h, const rx_io* io, const rx_eval_io& ev, const rx_match_io* m,
-                       int32_t n_steps, void* stream) {
-  const int64_t N = h->cfg.n_envs, A = h->cfg.n_agents, NA = N * A;
-  hipStream_t hs = (hipStream_t)stream;
-  const void* frag = nullptr;
-  int rc;
-  if (ev.params && !m && (rc = policy_fragments(fn, h, ev.obs_dim, ev.params, ev.precision, hs, &frag)) != 0)
-    return rc;
-  for (int32_t t = 0; t < n_steps; ++t) {
-    float* act = ev.actions + (int64_t)t * NA * 2;
-    if (ev.params) {
-      const rx_policy_io pio{ev.obs_dim, NA, io->obs, ev.eps + (int64_t)t * NA * 2, ev.params, ev.log_std, act,
-                             ev.logp_sink, ev.value_sink, 0, 0, ev.precision, nullptr, 0};
-      if (m) {
-        const rx_policy_bank_io b{pio, m->n_policies, (int32_t)A, m->params_stride, m->seat};
-        rc = rx_launch_policy_act_bank(&b, hs);
-      } else {
-        rc = rx_launch_policy_act(&pio, hs, frag);
-      }
-      if (rc) return fail(RX_EHIP, "%s: policy launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-    }
-    rx_io s = *io;
-    s.actions = act;
-    if ((rc = launch(h, &s, RX_MODE_STEP, nullptr, stream)) != 0) return rc;
-    // after launch(): its re-sort (if any) has been enqueued, so perm and the working rows agree
-    if ((rc = rx_launch_eval_acc((int)N, (int)A, h->perm[0].p, &h->work, io, ev.acc, ev.active, ev.n_active,
-                                 hs)) != 0)
-      return fail(RX_EHIP, "k_eval_acc launch failed: %s", hipGetErrorString((hipError_t)rc));
-  }
-  return RX_OK;
-}
-
-int rx_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, int32_t precision, void* stream) {
-  const char* fn = "rx_rollout_steps";
-  if (!h || !io || !r) return fail(RX_EINVAL, "%s: null argument", fn);
-  if (!h->assigned || !h->bound) return fail(RX_ESTATE, "%s: needs an assigned, bound handle", fn);
-  if (h->cfg.n_agents != 1) return fail(RX_EINVAL, "%s: single-agent handles only", fn);
-  int rc;
-  if ((rc = rollout_dims(fn, h, r)) != 0 || (rc = rollout_bufs(fn, r)) != 0 ||
-      (rc = precision_arg(fn, "precision", precision)) != 0)
-    return rc;
-  return rollout_loop(fn, h, io, r, nullptr, precision, stream);
-}
-
-int rx_selfplay_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
-                              int32_t precision, void* stream) {
-  const char* fn = "rx_selfplay_rollout_steps";
-  if (!h || !io || !r || !sp) return fail(RX_EINVAL, "%s: null argument", fn);
-  if (!h->assigned || !h->bound) return fail(RX_ESTATE, "%s: needs an assigned, bound handle", fn);
-  if (h->cfg.n_agents != 2) return fail(RX_EINVAL, "%s: two-car handles only", fn);
-  int rc = rollout_dims(fn, h, r);
-  if (rc) return rc;
-  if (sp->agent != 0 && sp->agent != 1) return fail(RX_EINVAL, "%s: agent=%d must be 0 or 1", fn, sp->agent);
-  if ((rc = rollout_bufs(fn, r)) != 0 || (rc = selfplay_bufs(fn, sp, false)) != 0) return rc;
-  if (h->D != 19) return fail(RX_EINVAL, "%s: obs_dim %d (19)", fn, h->D);
-  if ((rc = precision_arg(fn, "precision", precision)) != 0 ||
-      (rc = precision_arg(fn, "opp_precision", sp->opp_precision)) != 0)
-    return rc;
-  return two_car_rollout_loop(h, io, r, sp, nullptr, precision, stream);
-}
-
-// ABI v25: an evaluation's step loop (policy or open-loop actions, rx_step, k_eval_acc
-// per step) enqueued by one call; every argument is checked before the first HIP call.
-int rx_eval_steps(rx_env* h, const rx_io* io, const rx_eval_io* ev, int32_t n_steps, void* stream) {
-  if (!h) return fail(RX_EINVAL, "rx_eval_steps: null handle");
-  if (!io) return fail(RX_EINVAL, "rx_eval_steps: null io");
-  if (!ev) return fail(RX_EINVAL, "rx_eval_steps: null ev");
-  if (n_steps <= 0) return fail(RX_EINVAL, "rx_eval_steps: n_steps=%d must be > 0", n_steps);
-  if (!ev->actions) return fail(RX_EINVAL, "rx_eval_steps: null actions");
-  int rc = record_args("rx_eval_steps", io, ev->acc, ev->active, ev->n_active);
-  if (rc) return rc;
-  if (ev->params) {  // policy mode
-    if (ev->obs_dim != 15 && ev->obs_dim != 19)
-      return fail(RX_EINVAL, "rx_eval_steps: obs_dim=%d has no policy kernel (15 or 19)", ev->obs_dim);
-    if ((rc = precision_arg("rx_eval_steps", "precision", ev->precision)) != 0) return rc;
-    if (!ev->log_std || !ev->eps || !ev->logp_sink || !ev->value_sink)
-      return fail(RX_EINVAL, "rx_eval_steps: null %s (policy mode)",
-                  !ev->log_std ? "log_std" : !ev->eps ? "eps" : !ev->logp_sink ? "logp_sink" : "value_sink");
-  }
-  // from here on the handle is read
-  if (ev->obs_dim != h->D) return fail(RX_EINVAL, "rx_eval_steps: obs_dim %d != the handle's %d", ev->obs_dim, h->D);
-  if (h->n_tracks <= 0 || !h->assigned || !h->bound)
-    return fail(RX_ESTATE, "rx_eval_steps: needs an assigned, bound handle");
-  return record_loop("rx_eval_steps", h, io, *ev, nullptr, n_steps, stream);
-}
-
-// ABI v25, additive: rx_eval_steps' policy mode with a seating -- per step one bank launch
-// (car q of env e on policy seat[e][q]), rx_step, k_eval_acc.
-int rx_match_steps(rx_env* h, const rx_io* io, const rx_match_io* m, int32_t n_steps, void* stream) {
-  if (!h) return fail(RX_EINVAL, "rx_match_steps: null handle");
-  if (!io) return fail(RX_EINVAL, "rx_match_steps: null io");
-  if (!m) return fail(RX_EINVAL, "rx_match_steps: null match io");
-  if (n_steps <= 0) return fail(RX_EINVAL, "rx_match_steps: n_steps=%d must be > 0", n_steps);
-  if (m->obs_dim != 15 && m->obs_dim != 19)
-    return fail(RX_EINVAL, "rx_match_steps: obs_dim=%d has no policy kernel (15 or 19)", m->obs_dim);
-  int rc = precision_arg("rx_match_steps", "precision", m->precision);
-  if (rc) return rc;
-  if (m->n_policies <= 0) return fail(RX_EINVAL, "rx_match_steps: n_policies=%d must be > 0", m->n_policies);
-  if (m->params_stride < rx_ppo_n_params(m->obs_dim))
-    return fail(RX_EINVAL, "rx_match_steps: params_stride=%lld < the %d parameters of obs_dim %d",
-                (long long)m->params_stride, rx_ppo_n_params(m->obs_dim), m->obs_dim);
-  if (!m->params || !m->log_std || !m->eps || !m->seat || !m->actions || !m->logp_sink || !m->value_sink)
-    return fail(RX_EINVAL, "rx_match_steps: null %s",
-                !m->params ? "params" : !m->log_std ? "log_std" : !m->eps ? "eps" : !m->seat ? "seat"
-                : !m->actions ? "actions" : !m->logp_sink ? "logp_sink" : "value_sink");
-  if ((rc = record_args("rx_match_steps", io, m->acc, m->active, m->n_active)) != 0) return rc;
-  // from here on the handle is read
-  if (m->obs_dim != h->D) return fail(RX_EINVAL, "rx_match_steps: obs_dim %d != the handle's %d", m->obs_dim, h->D);
-  if (h->n_tracks <= 0 || !h->assigned || !h->bound)
-    return fail(RX_ESTATE, "rx_match_steps: needs an assigned, bound handle");
-  if (h->cfg.n_agents != 1 && h->cfg.n_agents != 2)
-    return fail(RX_EINVAL, "rx_match_steps: n_agents=%d (1 or 2)", h->cfg.n_agents);
-  const rx_eval_io ev{m->obs_dim, m->precision, m->params, m->log_std, m->eps, m->actions, m->logp_sink,
-                      m->value_sink, m->acc, m->active, m->n_active};
-  return record_loop("rx_match_steps", h, io, ev, m, n_steps, stream);
-}
-
-static int gae(int32_t T, int32_t N, const float* r, const float* v, const float* d, const float* nv, const float* nd,
-               double gamma, double lam, float* adv, float* ret, int scan, void* stream) {
-  if (T <= 0 || N <= 0) return fail(RX_EINVAL, "rx_gae: T=%d N=%d must be > 0", T, N);
-  if (!r || !v || !d || !nv || !nd || !adv || !ret) return fail(RX_EINVAL, "rx_gae: null buffer");
-  if ((long long)T * N > 0x7fffffffffffLL) return fail(RX_EINVAL, "rx_gae: T*N too large");
-  // agent/ppo.py:149,151: c["gamma"] * nnt is float32(gamma) * nnt; the Python
-  // double product gamma*lambda is rounded to float32 once.
-  const float g = (float)gamma;
-  const float gl = (float)(gamma * lam);
-  const int rc = rx_launch_gae(T, N, r, v, d, nv, nd, g, gl, adv, ret, scan, (hipStream_t)stream);
-  if (rc != 0) return fail(RX_EHIP, "gae launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_gae(int32_t T, int32_t N, const float* r, const float* v, const float* d, const float* nv, const float* nd,
-           double gamma, double lam, float* adv, float* ret, void* stream) {
-  return gae(T, N, r, v, d, nv, nd, gamma, lam, adv, ret, 0, stream);
-}
-
-int rx_gae_scan(int32_t T, int32_t N, const float* r, const float* v, const float* d, const float* nv,
-                const float* nd, double gamma, double lam, float* adv, float* ret, void* stream) {
-  return gae(T, N, r, v, d, nv, nd, gamma, lam, adv, ret, 1, stream);
-}
-
-// ---- track table builders (ABI v24) ------------------------------------------
-// What the host can check from the offsets alone; fills wp_off.
-static int tracks_shape(const char* fn, int32_t n, int32_t factor, const int32_t* cp_off, const void* cp,
-                        const void* width, int32_t* wp_off, const void* wp, const void* nrm, const void* seg,
-                        const void* meta) {
-  if (n <= 0) return fail(RX_EINVAL, "%s: n_tracks must be > 0 (got %d)", fn, n);
-  if (!cp_off || !cp || !width || !wp_off || !wp || !nrm || !seg || !meta) return fail(RX_EINVAL, "%s: null buffer", fn);
-  if (factor < 1) return fail(RX_EINVAL, "%s: factor must be >= 1 (got %d)", fn, factor);
-  if (cp_off[0] != 0) return fail(RX_EINVAL, "%s: cp_off[0] must be 0", fn);
-  const int max_w = 64 * RX_WP_CHUNK * RX_WP_SUPER;  // rx_upload_tracks' limit
-  for (int32_t k = 0; k < n; ++k) {
-    const int64_t P = (int64_t)cp_off[k + 1] - cp_off[k];
-    if (P < 3 || P > RX_TRACK_MAX_P)
-      return fail(RX_EINVAL, "%s: track %d has P = %lld control points (3 .. %d)", fn, k, (long long)P, RX_TRACK_MAX_P);
-    if (P * factor > max_w)
-      return fail(RX_EINVAL, "%s: track %d has W = P * factor = %lld waypoints (at most %d)", fn, k,
-                  (long long)(P * factor), max_w);
-  }
-  if ((int64_t)cp_off[n] * factor > INT32_MAX)
-    return fail(RX_EINVAL, "%s: W summed over the tracks = %lld overflows wp_off (int32)", fn,
-                (long long)cp_off[n] * factor);
-  for (int32_t k = 0; k <= n; ++k) wp_off[k] = cp_off[k] * factor;
-  return RX_OK;
-}
-
-int rx_build_tracks(int32_t n, int32_t factor, const int32_t* cp_off, const double* cp, const double* width,
-                    int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta, void* stream) {
-  const int rc = tracks_shape("rx_build_tracks", n, factor, cp_off, cp, width, wp_off, wp, nrm, seg, meta);
-  if (rc != RX_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  int32_t* off_dev = nullptr;
-  const size_t bytes = ((size_t)n + 1) * sizeof(int32_t);
-  if (hipMallocAsync((void**)&off_dev, bytes, s) != hipSuccess || !off_dev)
-    return fail(RX_ENOMEM, "rx_build_tracks: hipMallocAsync(%zu bytes) failed", bytes);
-  hipError_t e = hipMemcpyAsync(off_dev, cp_off, bytes, hipMemcpyHostToDevice, s);
-  int lrc = 0;
-  if (e == hipSuccess) lrc = rx_launch_build_tracks(n, factor, off_dev, cp, width, wp, nrm, seg, meta, s);
-  const hipError_t ef = hipFreeAsync(off_dev, s);
-  if (e != hipSuccess) return fail(RX_EHIP, "rx_build_tracks: offset copy failed: %s", hipGetErrorString(e));
-  if (lrc != 0) return fail(RX_EHIP, "rx_build_tracks: launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  if (ef != hipSuccess) return fail(RX_EHIP, "rx_build_tracks: hipFreeAsync failed: %s", hipGetErrorString(ef));
-  return RX_OK;
-}
-
-int rx_build_tracks_host(int32_t n, int32_t factor, const int32_t* cp_off, const double* cp, const double* width,
-                         int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta, void* /*stream*/) {
-  const int rc = tracks_shape("rx_build_tracks_host", n, factor, cp_off, cp, width, wp_off, wp, nrm, seg, meta);
-  if (rc != RX_OK) return rc;
-  for (int32_t k = 0; k < n; ++k) {  // the data, before anything is written
-    const int P = cp_off[k + 1] - cp_off[k];
-    int at = 0;
-    switch (rx_track_check(P, cp + 2 * (size_t)cp_off[k], width[k], &at)) {
-      case RX_TRACK_BAD_COORD:
-        return fail(RX_EINVAL, "rx_build_tracks_host: track %d: cp[%d] has a non-finite coordinate", k, at);
-      case RX_TRACK_BAD_CHORD:
-        return fail(RX_EINVAL, "rx_build_tracks_host: track %d: chord %d (cp[%d] to cp[%d]) has zero or non-finite "
-                               "length", k, at, at, (at + 1) % P);
-      case RX_TRACK_BAD_WIDTH:
-        return fail(RX_EINVAL, "rx_build_tracks_host: track %d: width %g is negative or NaN", k, width[k]);
-      default:
-        break;
-    }
-  }
-  rx_spline_ws ws;
-  for (int32_t k = 0; k < n; ++k) {  // the kernel's steps (rx_track.hip), one lane at a time
-    const int P = cp_off[k + 1] - cp_off[k], W = P * factor;
-    const double* c = cp + 2 * (size_t)cp_off[k];
-    const size_t base = (size_t)wp_off[k];
-    for (int i = 0; i < P; ++i) rx_spline_load(i, c, &ws);
-    rx_spline_knots(P, W, &ws);
-    rx_spline_solve(P, 0, &ws);
-    rx_spline_solve(P, 1, &ws);
-    for (int i = 0; i < P; ++i) rx_spline_coef(P, i, &ws);
-    double b[4] = {HUGE_VAL, -HUGE_VAL, HUGE_VAL, -HUGE_VAL};
-    for (int j = 0; j < W; ++j) {
-      double x, y;
-      rx_track_point(P, W, &ws, width[k], j, wp + 2 * base, nrm + 2 * base, seg + 8 * base, &x, &y);
-      rx_track_bounds(x, y, b);
-    }
-    double dy, dx;
-    rx_track_meta(P, W, &ws, width[k], b, meta + 8 * (size_t)k, &dy, &dx);
-    meta[8 * (size_t)k + 2] = atan2(dy, dx);
-  }
-  return RX_OK;
-}
-
-// ---- culling tables (ABI v25, additive) -----------------------------------------
-int rx_cull_table_sizes(int32_t n, const int32_t* wp_off, int32_t G, int32_t SG, int64_t* out) {
-  if (!out) return fail(RX_EINVAL, "rx_cull_table_sizes: out is null");
-  return cull_check("rx_cull_table_sizes", n, wp_off, nullptr, nullptr, nullptr, G, SG, nullptr, true, nullptr, out);
-}
-
-int rx_build_cull_tables_host(int32_t n, const int32_t* wp_off, const double* wp, const double* seg,
-                              const double* meta, int32_t G, int32_t SG, const rx_cull_tables* t, void* /*stream*/) {
-  std::vector<int32_t> off;
-  int64_t tot[4];
-  const int rc = cull_check("rx_build_cull_tables_host", n, wp_off, wp, seg, meta, G, SG, t, false, &off, tot);
-  if (rc != RX_OK) return rc;
-  const size_t n1 = (size_t)n + 1;
-  for (int32_t k = 0; k < n; ++k) {  // the kernel's steps (rx_cull.hip) with one lane
-    const int32_t wp0 = wp_off[k], W = wp_off[k + 1] - wp0;
-    const double* s = seg + 8 * (size_t)wp0;
-    rx_cull_slot o = {0, 0, 0, 0, tot[0], tot[1], t->chunk_box, t->super_box, t->wchunk_box, t->wsuper_box,
-                      t->chunk_box_f, t->super_box_f};
-    double b[4], longest, geo[4] = {0.0, 0.0, 0.0, 0.0};
-    rx_cull_extent(s, W, 0, 1, t->seg_f + 8 * (size_t)wp0, b, &longest);
-    if (G > 0) {
-      rx_cull_geo(b, rx_cull_reach(s, W, 0, 1, 0.5 * (b[0] + b[2]), 0.5 * (b[1] + b[3])), longest, geo);
-      o.chunk0 = off[n1 + k];
-      o.super0 = SG > 0 ? off[2 * n1 + k] : 0;
-      o.wchunk0 = off[3 * n1 + k];
-      o.wsuper0 = off[4 * n1 + k];
-      rx_cull_boxes(s, wp + 2 * (size_t)wp0, W, G, SG, 0, 1, &o);
-      for (int c = 0; c < 4; ++c) t->slot_geo[4 * (size_t)k + c] = geo[c];
-    }
-    rx_cull_header((rx_slot_hdr*)t->slot_hdr + k, wp0, W, &o, geo, meta + 8 * (size_t)k);
-  }
-  if (G > 0) {
-    std::copy(off.begin() + n1, off.begin() + 2 * n1, t->chunk_off);
-    if (SG > 0) std::copy(off.begin() + 2 * n1, off.begin() + 3 * n1, t->super_off);
-    std::copy(off.begin() + 3 * n1, off.begin() + 4 * n1, t->wchunk_off);
-    std::copy(off.begin() + 4 * n1, off.begin() + 5 * n1, t->wsuper_off);
-  }
-  return RX_OK;
-}
-
-// The launch behind rx_build_cull_tables and rx_upload_tracks_device: `off` (cull_check's
-// five offset arrays) goes up through a stream-ordered allocation, as rx_build_tracks'
-// offsets do (a pageable source: the copy has left `off` when hipMemcpyAsync returns).
-static int cull_launch(const char* fn, int32_t n, const std::vector<int32_t>& off, const int64_t tot[4],
-                       const double* wp, const double* seg, const double* meta, int32_t G, int32_t SG,
-                       const rx_cull_tables* t, hipStream_t s) {
-  int32_t* off_dev = nullptr;
-  const size_t bytes = off.size() * sizeof(int32_t);
-  if (hipMallocAsync((void**)&off_dev, bytes, s) != hipSuccess || !off_dev)
-    return fail(RX_ENOMEM, "%s: hipMallocAsync(%zu bytes) failed", fn, bytes);
-  hipError_t e = hipMemcpyAsync(off_dev, off.data(), bytes, hipMemcpyHostToDevice, s);
-  int lrc = 0;
-  if (e == hipSuccess) lrc = rx_launch_cull_tables(n, G, SG, off_dev, wp, seg, meta, t, tot[0], tot[1], s);
-  const hipError_t ef = hipFreeAsync(off_dev, s);
-  if (e != hipSuccess) return fail(RX_EHIP, "%s: offset copy failed: %s", fn, hipGetErrorString(e));
-  if (lrc != 0) return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)lrc));
-  if (ef != hipSuccess) return fail(RX_EHIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(ef));
-  return RX_OK;
-}
-
-int rx_build_cull_tables(int32_t n, const int32_t* wp_off, const double* wp, const double* seg, const double* meta,
-                         int32_t G, int32_t SG, const rx_cull_tables* t, void* stream) {
-  std::vector<int32_t> off;
-  int64_t tot[4];
-  const int rc = cull_check("rx_build_cull_tables", n, wp_off, wp, seg, meta, G, SG, t, false, &off, tot);
-  if (rc != RX_OK) return rc;
-  return cull_launch("rx_build_cull_tables", n, off, tot, wp, seg, meta, G, SG, t, (hipStream_t)stream);
-}
-
+// ---- track tables already on the device (ABI v25, additive): the handle's side of
+// rx_build_cull_tables and rx_patch_tracks, whose checks and launches are in rx_api_tracks.cpp
 int rx_upload_tracks_device(rx_env* h, int32_t n_tracks, const int32_t* wp_off, const double* wp, const double* nrm,
                             const double* seg, const double* meta, void* stream) {
   if (!h) return fail(RX_EINVAL, "rx_upload_tracks_device: null handle");
@@ -1767,133 +1075,6 @@ int rx_upload_tracks_device(rx_env* h, int32_t n_tracks, const int32_t* wp_off, 
   return RX_OK;
 }
 
-// ---- slots replaced in place (ABI v25, additive) ---------------------------------
-// What the host can check of a patch, before any HIP call or write; ps receives the
-// listed slots' rows for the kernel and the host twin, tot the table's box totals.
-// t == nullptr: the four table arrays only (G and SG are then not looked at).
-static int patch_check(const char* fn, int32_t n, const int32_t* wp_off, const void* wp, const void* nrm,
-                       const void* seg, const void* meta, int32_t G, int32_t SG, const rx_cull_tables* t,
-                       const rx_track_patch* p, std::vector<rx_patch_slot>* ps, int64_t tot[4]) {
-  if (n <= 0) return fail(RX_EINVAL, "%s: n_tracks must be > 0 (got %d)", fn, n);
-  if (!wp_off) return fail(RX_EINVAL, "%s: wp_off is null", fn);
-  if (!wp) return fail(RX_EINVAL, "%s: wp is null", fn);
-  if (!nrm) return fail(RX_EINVAL, "%s: nrm is null", fn);
-  if (!seg) return fail(RX_EINVAL, "%s: seg is null", fn);
-  if (!meta) return fail(RX_EINVAL, "%s: meta is null", fn);
-  if (!p) return fail(RX_EINVAL, "%s: the patch is null", fn);
-  const struct {
-    const void* q;
-    const char* name;
-  } fields[] = {{p->slots, "slots"}, {p->src_off, "src_off"}, {p->wp, "wp"},
-                {p->nrm, "nrm"},     {p->seg, "seg"},         {p->meta, "meta"}};
-  for (const auto& f : fields)
-    if (!f.q) return fail(RX_EINVAL, "%s: patch->%s is null", fn, f.name);
-  std::vector<int32_t> off;
-  const int rc = t ? cull_check(fn, n, wp_off, wp, seg, meta, G, SG, t, false, &off, tot)
-                   : cull_check(fn, n, wp_off, nullptr, nullptr, nullptr, 0, 0, nullptr, true, &off, tot);
-  if (rc != RX_OK) return rc;
-  if (p->n_upd < 1 || p->n_upd > n)
-    return fail(RX_EINVAL, "%s: patch->n_upd must be 1 .. n_tracks = %d (got %d)", fn, n, p->n_upd);
-  if (p->src_off[0] != 0) return fail(RX_EINVAL, "%s: patch->src_off[0] must be 0 (got %d)", fn, p->src_off[0]);
-  const size_t n1 = (size_t)n + 1;
-  ps->assign((size_t)p->n_upd, rx_patch_slot{});
-  for (int32_t j = 0; j < p->n_upd; ++j) {
-    const int32_t k = p->slots[j];
-    if (k < 0 || k >= n)
-      return fail(RX_EINVAL, "%s: patch->slots[%d] = slot %d is outside [0, %d)", fn, j, k, n);
-    if (j > 0 && k <= p->slots[j - 1])
-      return fail(RX_EINVAL, "%s: patch->slots[%d] = slot %d follows slot %d: the slots must be ascending and "
-                             "distinct", fn, j, k, p->slots[j - 1]);
-    const int64_t Ws = (int64_t)p->src_off[j + 1] - p->src_off[j], W = (int64_t)wp_off[k + 1] - wp_off[k];
-    if (Ws != W)
-      return fail(RX_EINVAL, "%s: slot %d: patch->src_off gives source track %d %lld waypoints, the slot has %lld "
-                             "(a replaced slot keeps its waypoint count)", fn, k, j, (long long)Ws, (long long)W);
-    (*ps)[j] = rx_patch_slot{k, p->src_off[j], wp_off[k], (int32_t)W, off[n1 + k], off[2 * n1 + k],
-                             off[3 * n1 + k], off[4 * n1 + k]};
-  }
-  return RX_OK;
-}
-
-// rx_upload_tracks' per-track checks on the source meta rows (host memory), the slot named
-static int patch_check_meta(const char* fn, const rx_track_patch* p, const double* meta_h) {
-  for (int32_t j = 0; j < p->n_upd; ++j) {
-    const double* m = meta_h + 8 * (size_t)j;
-    if (!(m[3] >= 0))
-      return fail(RX_EINVAL, "%s: slot %d (source track %d): width %g is negative or NaN", fn, p->slots[j], j, m[3]);
-    if (!(m[4] > 0))
-      return fail(RX_EINVAL, "%s: slot %d (source track %d): max_track_distance must be > 0 (got %g; NaN marks a "
-                             "track rx_build_tracks found invalid)", fn, p->slots[j], j, m[4]);
-  }
-  return RX_OK;
-}
-
-// The launch behind rx_patch_tracks and rx_replace_tracks_device: the listed slots' rows
-// go up through a stream-ordered allocation, as cull_launch's offsets do.
-static int patch_launch(const char* fn, const std::vector<rx_patch_slot>& ps, const int64_t tot[4], double* wp,
-                        double* nrm, double* seg, double* meta, int32_t G, int32_t SG, const rx_cull_tables* t,
-                        const rx_track_patch* p, hipStream_t s) {
-  rx_patch_slot* ps_dev = nullptr;
-  const size_t bytes = ps.size() * sizeof(rx_patch_slot);
-  if (hipMallocAsync((void**)&ps_dev, bytes, s) != hipSuccess || !ps_dev)
-    return fail(RX_ENOMEM, "%s: hipMallocAsync(%zu bytes) failed", fn, bytes);
-  hipError_t e = hipMemcpyAsync(ps_dev, ps.data(), bytes, hipMemcpyHostToDevice, s);
-  int lrc = 0;
-  if (e == hipSuccess)
-    lrc = rx_launch_patch_slots((int)ps.size(), t ? G : 0, t ? SG : 0, ps_dev, p, wp, nrm, seg, meta, t, tot[0],
-                                tot[1], s);
-  const hipError_t ef = hipFreeAsync(ps_dev, s);
-  if (e != hipSuccess) return fail(RX_EHIP, "%s: slot list copy failed: %s", fn, hipGetErrorString(e));
-  if (lrc != 0) return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)lrc));
-  if (ef != hipSuccess) return fail(RX_EHIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(ef));
-  return RX_OK;
-}
-
-int rx_patch_tracks(int32_t n, const int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta, int32_t G,
-                    int32_t SG, const rx_cull_tables* t, const rx_track_patch* p, void* stream) {
-  std::vector<rx_patch_slot> ps;
-  int64_t tot[4];
-  const int rc = patch_check("rx_patch_tracks", n, wp_off, wp, nrm, seg, meta, G, SG, t, p, &ps, tot);
-  if (rc != RX_OK) return rc;
-  return patch_launch("rx_patch_tracks", ps, tot, wp, nrm, seg, meta, G, SG, t, p, (hipStream_t)stream);
-}
-
-int rx_patch_tracks_host(int32_t n, const int32_t* wp_off, double* wp, double* nrm, double* seg, double* meta,
-                         int32_t G, int32_t SG, const rx_cull_tables* t, const rx_track_patch* p, void* /*stream*/) {
-  std::vector<rx_patch_slot> ps;
-  int64_t tot[4];
-  int rc = patch_check("rx_patch_tracks_host", n, wp_off, wp, nrm, seg, meta, G, SG, t, p, &ps, tot);
-  if (rc != RX_OK) return rc;
-  if ((rc = patch_check_meta("rx_patch_tracks_host", p, p->meta))) return rc;
-  if (!t) G = SG = 0;
-  for (size_t j = 0; j < ps.size(); ++j) {  // the kernel's steps (rx_cull.hip, k_patch_slots) with one lane
-    const rx_patch_slot& d = ps[j];
-    const int32_t k = d.slot, W = d.W;
-    const double* s = p->seg + 8 * (size_t)d.src0;
-    const double* w = p->wp + 2 * (size_t)d.src0;
-    const double* m = p->meta + 8 * j;
-    rx_cull_copy_rows<2>(w, wp + 2 * (size_t)d.wp0, W, 0, 1);
-    rx_cull_copy_rows<2>(p->nrm + 2 * (size_t)d.src0, nrm + 2 * (size_t)d.wp0, W, 0, 1);
-    rx_cull_copy_rows<4>(s, seg + 8 * (size_t)d.wp0, 2 * W, 0, 1);
-    for (int c = 0; c < 8; ++c) meta[8 * (size_t)k + c] = m[c];
-    if (!t) continue;
-    rx_cull_slot o = {0, 0, 0, 0, tot[0], tot[1], t->chunk_box, t->super_box, t->wchunk_box, t->wsuper_box,
-                      t->chunk_box_f, t->super_box_f};
-    double b[4], longest, geo[4] = {0.0, 0.0, 0.0, 0.0};
-    rx_cull_extent(s, W, 0, 1, t->seg_f + 8 * (size_t)d.wp0, b, &longest);
-    if (G > 0) {
-      rx_cull_geo(b, rx_cull_reach(s, W, 0, 1, 0.5 * (b[0] + b[2]), 0.5 * (b[1] + b[3])), longest, geo);
-      o.chunk0 = d.chunk0;
-      o.super0 = SG > 0 ? d.super0 : 0;
-      o.wchunk0 = d.wchunk0;
-      o.wsuper0 = d.wsuper0;
-      rx_cull_boxes(s, w, W, G, SG, 0, 1, &o);
-      for (int c = 0; c < 4; ++c) t->slot_geo[4 * (size_t)k + c] = geo[c];
-    }
-    rx_cull_header((rx_slot_hdr*)t->slot_hdr + k, d.wp0, W, &o, geo, m);
-  }
-  return RX_OK;
-}
-
 int rx_replace_tracks_device(rx_env* h, const rx_track_patch* p, void* stream) {
   const char* fn = "rx_replace_tracks_device";
   if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
@@ -1919,1077 +1100,3 @@ int rx_replace_tracks_device(rx_env* h, const rx_track_patch* p, void* stream) {
   RX_HIP(hipStreamSynchronize(s));
   return RX_OK;
 }
-
-// ---- rendering (ABI v25, additive) ---------------------------------------------
-static int raster_static_args(const char* fn, int32_t n, int32_t size, int32_t n_edges, const void* edge_off,
-                              const void* edges, const void* layer) {
-  if (n <= 0 || n > RX_RASTER_MAX_IMAGES) return fail(RX_EINVAL, "%s: n=%d outside 1..%d", fn, n, RX_RASTER_MAX_IMAGES);
-  if (size < RX_RASTER_SIZE_MIN || size > RX_RASTER_SIZE_MAX)
-    return fail(RX_EINVAL, "%s: size=%d outside %d..%d", fn, size, RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX);
-  if (n_edges < 0) return fail(RX_EINVAL, "%s: n_edges=%d is negative", fn, n_edges);
-  if (!edge_off) return fail(RX_EINVAL, "%s: null pointer: edge_off", fn);
-  if (!edges) return fail(RX_EINVAL, "%s: null pointer: edges", fn);
-  if (!layer) return fail(RX_EINVAL, "%s: null pointer: layer", fn);
-  return RX_OK;
-}
-
-// frame = 0: what rx_raster_trail reads; 1: what rx_raster_frame reads.
-static int raster_io_args(const char* fn, const rx_raster_io* r, int frame) {
-  if (!r) return fail(RX_EINVAL, "%s: null pointer: r", fn);
-  if (r->size < RX_RASTER_SIZE_MIN || r->size > RX_RASTER_SIZE_MAX)
-    return fail(RX_EINVAL, "%s: size=%d outside %d..%d", fn, r->size, RX_RASTER_SIZE_MIN, RX_RASTER_SIZE_MAX);
-  if (r->A != 1 && r->A != 2) return fail(RX_EINVAL, "%s: A=%d must be 1 or 2", fn, r->A);
-  if (r->K <= 0 || r->K > RX_RASTER_MAX_IMAGES)
-    return fail(RX_EINVAL, "%s: K=%d outside 1..%d", fn, r->K, RX_RASTER_MAX_IMAGES);
-  if (r->n_envs <= 0) return fail(RX_EINVAL, "%s: n_envs=%d must be > 0", fn, r->n_envs);
-#define RX_RASTER_PTR(f) \
-  if (!r->f) return fail(RX_EINVAL, "%s: null pointer: " #f, fn)
-  RX_RASTER_PTR(env_ids);
-  RX_RASTER_PTR(x);
-  RX_RASTER_PTR(y);
-  RX_RASTER_PTR(view);
-  RX_RASTER_PTR(trail);
-  if (!frame) {
-    RX_RASTER_PTR(last);
-    return RX_OK;
-  }
-  RX_RASTER_PTR(angle);
-  RX_RASTER_PTR(layer_of);
-  RX_RASTER_PTR(layer);
-  RX_RASTER_PTR(out);
-  RX_RASTER_PTR(out_off);
-#undef RX_RASTER_PTR
-  if (r->n_layers <= 0) return fail(RX_EINVAL, "%s: n_layers=%d must be > 0", fn, r->n_layers);
-  if (r->out_pitch < 0) return fail(RX_EINVAL, "%s: out_pitch=%lld is negative", fn, (long long)r->out_pitch);
-  if (r->out_pitch < 3 * (int64_t)r->size)
-    return fail(RX_EINVAL, "%s: out_pitch=%lld below 3*size=%d", fn, (long long)r->out_pitch, 3 * r->size);
-  if (r->out_size < 0) return fail(RX_EINVAL, "%s: out_size=%lld is negative", fn, (long long)r->out_size);
-  return RX_OK;
-}
-
-int rx_raster_static(int32_t n, int32_t size, int32_t n_edges, const int32_t* edge_off, const int32_t* edges,
-                     uint8_t* layer, void* stream) {
-  int rc = raster_static_args("rx_raster_static", n, size, n_edges, edge_off, edges, layer);
-  if (rc != RX_OK) return rc;
-  if ((rc = rx_launch_raster_static(n, size, n_edges, edge_off, edges, layer, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_raster_static: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_raster_trail(const rx_raster_io* r, void* stream) {
-  int rc = raster_io_args("rx_raster_trail", r, 0);
-  if (rc != RX_OK) return rc;
-  if ((rc = rx_launch_raster_trail(r, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_raster_trail: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_raster_frame(const rx_raster_io* r, void* stream) {
-  int rc = raster_io_args("rx_raster_frame", r, 1);
-  if (rc != RX_OK) return rc;
-  if ((rc = rx_launch_raster_frame(r, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_raster_frame: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-// The host twins: argument checks here, the loops in rx_raster_host.cpp.
-int rx_raster_static_host(int32_t n, int32_t size, int32_t n_edges, const int32_t* edge_off, const int32_t* edges,
-                          uint8_t* layer, void* /*stream*/) {
-  const int rc = raster_static_args("rx_raster_static_host", n, size, n_edges, edge_off, edges, layer);
-  if (rc != RX_OK) return rc;
-  rx_host_raster_static(n, size, n_edges, edge_off, edges, layer);
-  return RX_OK;
-}
-
-int rx_raster_trail_host(const rx_raster_io* r, void* /*stream*/) {
-  const int rc = raster_io_args("rx_raster_trail_host", r, 0);
-  if (rc != RX_OK) return rc;
-  rx_host_raster_trail(r);
-  return RX_OK;
-}
-
-int rx_raster_frame_host(const rx_raster_io* r, void* /*stream*/) {
-  const int rc = raster_io_args("rx_raster_frame_host", r, 1);
-  if (rc != RX_OK) return rc;
-  rx_host_raster_frame(r);
-  return RX_OK;
-}
-
-static int adam_cfg_error(const rx_adam_config* cfg) {
-  if (!cfg) return fail(RX_EINVAL, "rx_adam: cfg is null");
-  if (cfg->n_tensors <= 0 || cfg->n_tensors > RX_ADAM_MAX_TENSORS)
-    return fail(RX_EINVAL, "rx_adam: n_tensors=%d not in [1, %d]", cfg->n_tensors, RX_ADAM_MAX_TENSORS);
-  if (cfg->offsets[0] != 0) return fail(RX_EINVAL, "rx_adam: offsets[0] must be 0");
-  for (int k = 0; k < cfg->n_tensors; ++k)
-    if (cfg->offsets[k + 1] < cfg->offsets[k]) return fail(RX_EINVAL, "rx_adam: offsets not ascending");
-  if (!(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0 && cfg->beta2 >= 0.0 && cfg->beta2 < 1.0 && cfg->eps >= 0.0))
-    return fail(RX_EINVAL, "rx_adam: bad betas/eps");
-  return RX_OK;
-}
-
-size_t rx_adam_workspace_floats(const rx_adam_config* cfg) {
-  if (adam_cfg_error(cfg) != RX_OK) return 0;
-  const int64_t n = cfg->offsets[cfg->n_tensors];
-  const int64_t nb = n > 0 ? (n + RX_ADAM_NORM_ELEMS - 1) / RX_ADAM_NORM_ELEMS : 1;
-  return (size_t)(nb * cfg->n_tensors) + 2;  // + Adam's two step scalars
-}
-
-int rx_adam_clip_step(const rx_adam_config* cfg, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
-                      float* step, const double* lr, const uint8_t* stop, float* ws, void* stream) {
-  if (const int rc = adam_cfg_error(cfg)) return rc;
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !lr || !ws)
-    return fail(RX_EINVAL, "rx_adam_clip_step: null buffer");
-  const int rc = rx_launch_adam(cfg, params, grads, exp_avg, exp_avg_sq, step, lr, stop, ws, (hipStream_t)stream);
-  if (rc != 0) return fail(RX_EHIP, "adam launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_ppo_n_params(int32_t obs_dim);  // rx_ppo.hip
-
-size_t rx_ppo_workspace_floats(int32_t obs_dim, int32_t mb) {
-  return (obs_dim == 15 || obs_dim == 19) && mb > 0 ? rx_ppo_partial_floats(obs_dim, mb) : 0;
-}
-
-size_t rx_ppo_workspace_doubles(int32_t mb) { return mb > 0 ? (size_t)rx_ppo_n_wg(mb) : 0; }
-
-static int check_ppo_batch(const rx_ppo_batch* b) {
-  if (!b) return fail(RX_EINVAL, "rx_ppo: batch is null");
-  if (b->obs_dim != 15 && b->obs_dim != 19) return fail(RX_EINVAL, "rx_ppo: obs_dim=%d (15 or 19)", b->obs_dim);
-  if (b->mb <= 0 || b->n_rows <= 0) return fail(RX_EINVAL, "rx_ppo: mb=%d n_rows=%lld", b->mb, (long long)b->n_rows);
-  if (precision_arg("rx_ppo", "precision", b->precision)) return RX_EINVAL;
-  if (!b->obs || !b->actions || !b->logprobs || !b->advantages || !b->returns || !b->values || !b->perm ||
-      !b->params || !b->log_std)
-    return fail(RX_EINVAL, "rx_ppo: null buffer");
-  return RX_OK;
-}
-
-int rx_ppo_adv_stats(const rx_ppo_batch* b, int32_t n_mb, float* stats, void* stream) {
-  int rc = check_ppo_batch(b);
-  if (rc) return rc;
-  if (n_mb <= 0 || !stats) return fail(RX_EINVAL, "rx_ppo_adv_stats: n_mb=%d stats=%p", n_mb, (void*)stats);
-  if ((int64_t)n_mb * b->mb > b->n_rows) return fail(RX_EINVAL, "rx_ppo_adv_stats: n_mb*mb > n_rows");
-  if ((rc = rx_launch_adv_stats(b, n_mb, stats, nullptr, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "adv stats launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_ppo_adv_moments(const rx_ppo_batch* b, int32_t n_mb, double* moments, void* stream) {
-  int rc = check_ppo_batch(b);
-  if (rc) return rc;
-  if (n_mb <= 0 || !moments) return fail(RX_EINVAL, "rx_ppo_adv_moments: n_mb=%d moments=%p", n_mb, (void*)moments);
-  if ((int64_t)n_mb * b->mb > b->n_rows) return fail(RX_EINVAL, "rx_ppo_adv_moments: n_mb*mb > n_rows");
-  if ((rc = rx_launch_adv_stats(b, n_mb, nullptr, moments, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "adv moments launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-size_t rx_ppo_adv_workspace_doubles(int32_t mb, int32_t n_mb) {
-  return mb > 0 && n_mb > 0 ? 2 * (size_t)n_mb * (size_t)rx_adv_chunks(mb) : 0;
-}
-
-int rx_ppo_adv_stats_ws(const rx_ppo_batch* b, int32_t n_mb, double* ws, float* stats, double* moments, void* stream) {
-  int rc = check_ppo_batch(b);
-  if (rc) return rc;
-  if (n_mb <= 0 || !ws || (!stats && !moments))
-    return fail(RX_EINVAL, "rx_ppo_adv_stats_ws: n_mb=%d ws=%p stats=%p moments=%p", n_mb, (void*)ws, (void*)stats,
-                (void*)moments);
-  if ((int64_t)n_mb * b->mb > b->n_rows) return fail(RX_EINVAL, "rx_ppo_adv_stats_ws: n_mb*mb > n_rows");
-  if ((rc = rx_launch_adv_stats_ws(b, n_mb, ws, moments ? nullptr : stats, moments, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "adv stats launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_ppo_adv_finalize(const double* moments, int32_t n_mb, int64_t count, float* stats, void* stream) {
-  if (n_mb <= 0 || count <= 0 || !moments || !stats)
-    return fail(RX_EINVAL, "rx_ppo_adv_finalize: n_mb=%d count=%lld moments=%p stats=%p", n_mb, (long long)count,
-                (const void*)moments, (void*)stats);
-  const int rc = rx_launch_adv_finalize(moments, n_mb, count, stats, (hipStream_t)stream);
-  if (rc != 0) return fail(RX_EHIP, "adv finalize launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_ppo_minibatch_grad(const rx_ppo_batch* b, int32_t m, float* ws_f32, double* ws_f64, float* grad,
-                          uint8_t* stop, float* kl_at_stop, void* stream) {
-  int rc = check_ppo_batch(b);
-  if (rc) return rc;
-  if (!b->adv_stats) return fail(RX_EINVAL, "rx_ppo_minibatch_grad: adv_stats is null");
-  if (m < 0 || (int64_t)(m + 1) * b->mb > b->n_rows) return fail(RX_EINVAL, "rx_ppo_minibatch_grad: m=%d out of range", m);
-  if (!ws_f32 || !ws_f64 || !grad || !stop || !kl_at_stop) return fail(RX_EINVAL, "rx_ppo_minibatch_grad: null buffer");
-  if ((rc = rx_launch_ppo_grad(b, m, 1.0f, stop, kl_at_stop, nullptr, ws_f32, ws_f64, grad, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "ppo grad launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-size_t rx_ppo_update_workspace_floats(int32_t obs_dim, const rx_adam_config* cfg) {
-  if ((obs_dim != 15 && obs_dim != 19) || adam_cfg_error(cfg) != RX_OK) return 0;
-  // the per-tensor sums of squares of every reduce block + Adam's two step scalars
-  return (size_t)rx_ppo_reduce_blocks(obs_dim) * cfg->n_tensors + 2;
-}
-
-int rx_ppo_minibatch_update(const rx_ppo_batch* b, int32_t m, const rx_adam_config* cfg, float* params,
-                            float* ws_f32, double* ws_f64, float* grad, float* exp_avg, float* exp_avg_sq, float* step,
-                            const double* lr, uint8_t* stop, float* kl_at_stop, float* adam_ws, void* stream) {
-  int rc = check_ppo_batch(b);
-  if (rc) return rc;
-  if ((rc = adam_cfg_error(cfg))) return rc;
-  if (!b->adv_stats) return fail(RX_EINVAL, "rx_ppo_minibatch_update: adv_stats is null");
-  if (m < 0 || (int64_t)(m + 1) * b->mb > b->n_rows)
-    return fail(RX_EINVAL, "rx_ppo_minibatch_update: m=%d out of range", m);
-  if (!params || params != b->params) return fail(RX_EINVAL, "rx_ppo_minibatch_update: params must be b->params");
-  if (cfg->offsets[cfg->n_tensors] != rx_ppo_n_params(b->obs_dim))
-    return fail(RX_EINVAL, "rx_ppo_minibatch_update: cfg covers %lld parameters, the policy has %d",
-                (long long)cfg->offsets[cfg->n_tensors], rx_ppo_n_params(b->obs_dim));
-  if (!ws_f32 || !ws_f64 || !grad || !exp_avg || !exp_avg_sq || !step || !lr || !stop || !kl_at_stop || !adam_ws)
-    return fail(RX_EINVAL, "rx_ppo_minibatch_update: null buffer");
-  const hipStream_t s = (hipStream_t)stream;
-  if ((rc = rx_launch_ppo_grad(b, m, 1.0f, stop, kl_at_stop, nullptr, ws_f32, ws_f64, grad, s, cfg, adam_ws, step, lr)))
-    return fail(RX_EHIP, "ppo grad launch failed: %s", hipGetErrorString((hipError_t)rc));
-  if ((rc = rx_launch_adam_apply(cfg, params, grad, exp_avg, exp_avg_sq, step, lr, stop, adam_ws,
-                                 rx_ppo_reduce_blocks(b->obs_dim), s)))
-    return fail(RX_EHIP, "adam launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_ppo_minibatch_grad_shard(const rx_ppo_batch* b, int32_t m, float scale, float* ws_f32, double* ws_f64,
-                                float* grad, float* kl_out, const uint8_t* stop, void* stream) {
-  int rc = check_ppo_batch(b);
-  if (rc) return rc;
-  if (!b->adv_stats) return fail(RX_EINVAL, "rx_ppo_minibatch_grad_shard: adv_stats is null");
-  if (m < 0 || (int64_t)(m + 1) * b->mb > b->n_rows)
-    return fail(RX_EINVAL, "rx_ppo_minibatch_grad_shard: m=%d out of range", m);
-  if (!(scale > 0.0f)) return fail(RX_EINVAL, "rx_ppo_minibatch_grad_shard: scale=%g", (double)scale);
-  if (!ws_f32 || !ws_f64 || !grad || !kl_out || !stop)
-    return fail(RX_EINVAL, "rx_ppo_minibatch_grad_shard: null buffer");
-  // the kernels only read *stop in shard mode (the decision is rx_ppo_kl_check's)
-  if ((rc = rx_launch_ppo_grad(b, m, scale, const_cast<uint8_t*>(stop), nullptr, kl_out, ws_f32, ws_f64, grad,
-                               (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "ppo grad launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_random_permutation(int64_t n, uint64_t seed, int64_t* out, void* stream) {
-  if (n < 0 || n > (1ll << 62)) return fail(RX_EINVAL, "rx_random_permutation: n = %lld out of range", (long long)n);
-  if (n > 0 && !out) return fail(RX_EINVAL, "rx_random_permutation: null output");
-  const int rc = rx_launch_permutation(n, seed, out, (hipStream_t)stream);
-  if (rc) return fail(RX_EHIP, "rx_random_permutation launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_ppo_kl_check(const float* kl, float kl_target, uint8_t* stop, float* kl_at_stop, void* stream) {
-  if (!kl || !stop || !kl_at_stop) return fail(RX_EINVAL, "rx_ppo_kl_check: null buffer");
-  const int rc = rx_launch_kl_check(kl, kl_target, stop, kl_at_stop, (hipStream_t)stream);
-  if (rc != 0) return fail(RX_EHIP, "kl check launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_policy_act(const rx_policy_io* io, void* stream) {
-  if (!io) return fail(RX_EINVAL, "rx_policy_act: io is null");
-  if (io->obs_dim != 15 && io->obs_dim != 19) return fail(RX_EINVAL, "rx_policy_act: obs_dim=%d (15 or 19)", io->obs_dim);
-  if (io->n <= 0) return fail(RX_EINVAL, "rx_policy_act: n=%lld", (long long)io->n);
-  if (precision_arg("rx_policy_act", "precision", io->precision)) return RX_EINVAL;
-  if ((io->obs_stride != 0 && io->obs_stride < io->obs_dim) || (io->act_stride != 0 && io->act_stride < 2) ||
-      (io->act2_stride != 0 && io->act2_stride < 2))
-    return fail(RX_EINVAL, "rx_policy_act: row strides overlap (obs %lld, act %lld)", (long long)io->obs_stride,
-                (long long)io->act_stride);
-  if (!io->obs || !io->eps || !io->params || !io->log_std || !io->actions || !io->logprobs || !io->values)
-    return fail(RX_EINVAL, "rx_policy_act: null buffer");
-  const int rc = rx_launch_policy_act(io, (hipStream_t)stream);
-  if (rc != 0) return fail(RX_EHIP, "policy launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-// ABI v25, additive: rx_policy_act with per-row parameters from a bank (k_policy_act_bank)
-int rx_policy_act_bank(const rx_policy_bank_io* b, void* stream) {
-  if (!b) return fail(RX_EINVAL, "rx_policy_act_bank: io is null");
-  const rx_policy_io* io = &b->io;
-  if (io->obs_dim != 15 && io->obs_dim != 19)
-    return fail(RX_EINVAL, "rx_policy_act_bank: obs_dim=%d (15 or 19)", io->obs_dim);
-  if (io->n <= 0) return fail(RX_EINVAL, "rx_policy_act_bank: n=%lld must be > 0", (long long)io->n);
-  if (b->n_policies <= 0) return fail(RX_EINVAL, "rx_policy_act_bank: n_policies=%d must be > 0", b->n_policies);
-  if (b->params_stride < rx_ppo_n_params(io->obs_dim))
-    return fail(RX_EINVAL, "rx_policy_act_bank: params_stride=%lld < the %d parameters of obs_dim %d",
-                (long long)b->params_stride, rx_ppo_n_params(io->obs_dim), io->obs_dim);
-  if (precision_arg("rx_policy_act_bank", "precision", io->precision)) return RX_EINVAL;
-  if ((b->tile_cars != 1 && b->tile_cars != 2) || (b->tile_cars == 2 && (io->n & 1)))
-    return fail(RX_EINVAL, "rx_policy_act_bank: tile_cars=%d (1, or 2 with an even n; n=%lld)", b->tile_cars,
-                (long long)io->n);
-  if ((io->obs_stride != 0 && io->obs_stride < io->obs_dim) || (io->act_stride != 0 && io->act_stride < 2) ||
-      (io->act2_stride != 0 && io->act2_stride < 2))
-    return fail(RX_EINVAL, "rx_policy_act_bank: row strides overlap (obs_stride %lld, act_stride %lld, act2_stride %lld)",
-                (long long)io->obs_stride, (long long)io->act_stride, (long long)io->act2_stride);
-  if (!io->obs || !io->eps || !io->params || !io->log_std || !io->actions || !io->logprobs || !io->values ||
-      !b->policy_of_row)
-    return fail(RX_EINVAL, "rx_policy_act_bank: null %s",
-                !io->obs ? "obs" : !io->eps ? "eps" : !io->params ? "params" : !io->log_std ? "log_std"
-                : !io->actions ? "actions" : !io->logprobs ? "logprobs" : !io->values ? "values" : "policy_of_row");
-  const int rc = rx_launch_policy_act_bank(b, (hipStream_t)stream);
-  if (rc != 0) return fail(RX_EHIP, "bank policy launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-// ABI v25, additive: league training (csrc/rx_league.h).  The checks of the three entry
-// points and their host twins, before any HIP call; what: 0 = weights, 1 = draw, 2 = rollout.
-static int league_args(const char* fn, const rx_league_io* lg, int what) {
-  if (!lg) return fail(RX_EINVAL, "%s: null league io", fn);
-  if (lg->n_slots < 1 || lg->n_slots > 64) return fail(RX_EINVAL, "%s: n_slots=%d outside 1..64", fn, lg->n_slots);
-  if (!lg->tally || !lg->cdf) return fail(RX_EINVAL, "%s: null %s", fn, !lg->tally ? "tally" : "cdf");
-  if (what == 0) return RX_OK;
-  if (lg->agent != 0 && lg->agent != 1) return fail(RX_EINVAL, "%s: agent=%d must be 0 or 1", fn, lg->agent);
-  if (!lg->opp_id || !lg->draw_count)
-    return fail(RX_EINVAL, "%s: null %s", fn, !lg->opp_id ? "opp_id" : "draw_count");
-  if (what == 1) return RX_OK;
-  if (!lg->params || !lg->log_std) return fail(RX_EINVAL, "%s: null %s", fn, !lg->params ? "params" : "log_std");
-  if (lg->params_stride < rx_ppo_n_params(19))
-    return fail(RX_EINVAL, "%s: params_stride=%lld < the %d parameters of obs_dim 19", fn,
-                (long long)lg->params_stride, rx_ppo_n_params(19));
-  return precision_arg(fn, "opp_precision", lg->opp_precision);
-}
-
-static int league_weights_args(const char* fn, const rx_league_io* lg, int32_t n_live, int32_t power, double mix,
-                               double prior) {
-  const int rc = league_args(fn, lg, 0);
-  if (rc) return rc;
-  if (n_live < 1 || n_live > lg->n_slots)
-    return fail(RX_EINVAL, "%s: n_live=%d outside 1..n_slots=%d", fn, n_live, lg->n_slots);
-  if (power < 0 || power > 4) return fail(RX_EINVAL, "%s: power=%d outside 0..4", fn, power);
-  if (!(mix >= 0.0 && mix <= 1.0)) return fail(RX_EINVAL, "%s: mix=%g outside [0, 1]", fn, mix);
-  if (!(prior > 0.0)) return fail(RX_EINVAL, "%s: prior=%g must be > 0", fn, prior);
-  return RX_OK;
-}
-
-static int league_draw_args(const char* fn, const rx_league_io* lg, int64_t n, const float* done, const double* info) {
-  const int rc = league_args(fn, lg, 1);
-  if (rc) return rc;
-  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
-  if (done && !info) return fail(RX_EINVAL, "%s: null info (required with done)", fn);
-  return RX_OK;
-}
-
-int rx_league_weights(const rx_league_io* lg, int32_t n_live, int32_t power, double mix, double prior, void* stream) {
-  int rc = league_weights_args("rx_league_weights", lg, n_live, power, mix, prior);
-  if (rc) return rc;
-  if ((rc = rx_launch_league_weights(lg, n_live, power, mix, prior, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_league_weights: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_league_weights_host(const rx_league_io* lg, int32_t n_live, int32_t power, double mix, double prior,
-                           void* /*stream*/) {
-  const int rc = league_weights_args("rx_league_weights_host", lg, n_live, power, mix, prior);
-  if (rc) return rc;
-  rx_host_league_weights(lg, n_live, power, mix, prior);
-  return RX_OK;
-}
-
-int rx_league_draw(const rx_league_io* lg, int64_t n, const float* done, const double* info, void* stream) {
-  int rc = league_draw_args("rx_league_draw", lg, n, done, info);
-  if (rc) return rc;
-  if ((rc = rx_launch_league_draw(lg, n, done, info, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_league_draw: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_league_draw_host(const rx_league_io* lg, int64_t n, const float* done, const double* info, void* /*stream*/) {
-  const int rc = league_draw_args("rx_league_draw_host", lg, n, done, info);
-  if (rc) return rc;
-  rx_host_league_draw(lg, n, done, info);
-  return RX_OK;
-}
-
-// the two-car rollout loop with a per-env opponent from the bank (two_car_rollout_loop)
-int rx_league_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
-                            const rx_league_io* lg, int32_t precision, void* stream) {
-  const char* fn = "rx_league_rollout_steps";
-  // the league io first: its refusals need no handle (tests/test_league_train_cpu.py)
-  int rc = league_args(fn, lg, 2);
-  if (rc) return rc;
-  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
-  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
-  if (!io || !r || !sp) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : !r ? "rollout io" : "self-play io");
-  if (!h->assigned || !h->bound || h->cfg.n_agents != 2 || h->D != 19)
-    return fail(RX_EINVAL, "%s: the handle must be an assigned, bound two-car handle with obs_dim 19", fn);
-  if ((rc = rollout_dims(fn, h, r)) != 0) return rc;
-  if (sp->agent != lg->agent)
-    return fail(RX_EINVAL, "%s: agent %d of the self-play io != agent %d of the league io", fn, sp->agent, lg->agent);
-  if ((rc = rollout_bufs(fn, r)) != 0 || (rc = selfplay_bufs(fn, sp, true)) != 0) return rc;
-  if (!io->info) return fail(RX_EINVAL, "%s: null io->info (the tally reads the terminal step's placement)", fn);
-  return two_car_rollout_loop(h, io, r, sp, lg, precision, stream);
-}
-
-// ABI v25, additive: the track curriculum (csrc/rx_curriculum.h).  The checks of the four entry
-// points and their host twins, before any HIP call; what: 0 = tally, 1 = scores, 2 = draw.
-static int track_args(const char* fn, const rx_track_io* tc, int what) {
-  if (!tc) return fail(RX_EINVAL, "%s: null track io", fn);
-  if (tc->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, tc->n_tracks);
-  if (what == 0 && (!tc->track || !tc->tally))
-    return fail(RX_EINVAL, "%s: null %s", fn, !tc->track ? "track" : "tally");
-  if (what == 1) {
-    if (!tc->tally || !tc->cdf || !tc->p)
-      return fail(RX_EINVAL, "%s: null %s", fn, !tc->tally ? "tally" : !tc->cdf ? "cdf" : "p");
-    if (tc->score != 0 && tc->score != 1) return fail(RX_EINVAL, "%s: score=%d must be 0 or 1", fn, tc->score);
-  }
-  if (what == 2 && (!tc->cdf || !tc->track_of_env))
-    return fail(RX_EINVAL, "%s: null %s", fn, !tc->cdf ? "cdf" : "track_of_env");
-  return RX_OK;
-}
-
-static int track_tally_args(const char* fn, const rx_track_io* tc, int64_t n, const float* done,
-                            const uint8_t* terminated, const double* info) {
-  const int rc = track_args(fn, tc, 0);
-  if (rc) return rc;
-  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
-  if (!done || !terminated || !info)
-    return fail(RX_EINVAL, "%s: null %s", fn, !done ? "done" : !terminated ? "terminated" : "info");
-  return RX_OK;
-}
-
-static int track_scores_args(const char* fn, const rx_track_io* tc, int32_t power, double prior) {
-  const int rc = track_args(fn, tc, 1);
-  if (rc) return rc;
-  if (power < 0 || power > 4) return fail(RX_EINVAL, "%s: power=%d outside 0..4", fn, power);
-  if (!(prior > 0.0)) return fail(RX_EINVAL, "%s: prior=%g must be > 0", fn, prior);
-  return RX_OK;
-}
-
-static int track_draw_args(const char* fn, const rx_track_io* tc, int64_t n, double mix) {
-  const int rc = track_args(fn, tc, 2);
-  if (rc) return rc;
-  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
-  if (!(mix >= 0.0 && mix <= 1.0)) return fail(RX_EINVAL, "%s: mix=%g outside [0, 1]", fn, mix);
-  return RX_OK;
-}
-
-int rx_track_tally(const rx_track_io* tc, int64_t n, const float* done, const uint8_t* terminated, const double* info,
-                   void* stream) {
-  int rc = track_tally_args("rx_track_tally", tc, n, done, terminated, info);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_tally(tc, n, done, terminated, info, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_tally: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_tally_host(const rx_track_io* tc, int64_t n, const float* done, const uint8_t* terminated,
-                        const double* info, void* /*stream*/) {
-  const int rc = track_tally_args("rx_track_tally_host", tc, n, done, terminated, info);
-  if (rc) return rc;
-  rx_host_track_tally(tc, n, done, terminated, info);
-  return RX_OK;
-}
-
-int rx_track_scores(const rx_track_io* tc, int32_t power, double prior, void* stream) {
-  int rc = track_scores_args("rx_track_scores", tc, power, prior);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_scores(tc, power, prior, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_scores: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_scores_host(const rx_track_io* tc, int32_t power, double prior, void* /*stream*/) {
-  const int rc = track_scores_args("rx_track_scores_host", tc, power, prior);
-  if (rc) return rc;
-  rx_host_track_scores(tc, power, prior);
-  return RX_OK;
-}
-
-int rx_track_draw(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, void* stream) {
-  int rc = track_draw_args("rx_track_draw", tc, n, mix);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_draw(tc, n, generation, mix, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_draw: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_draw_host(const rx_track_io* tc, int64_t n, uint32_t generation, double mix, void* /*stream*/) {
-  const int rc = track_draw_args("rx_track_draw_host", tc, n, mix);
-  if (rc) return rc;
-  rx_host_track_draw(tc, n, generation, mix);
-  return RX_OK;
-}
-
-// the single-agent rollout loop with the tally (rollout_loop)
-int rx_track_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
-                           int32_t precision, void* stream) {
-  const char* fn = "rx_track_rollout_steps";
-  // the track io first: its refusals need no handle (tests/test_curriculum_cpu.py)
-  int rc = track_args(fn, tc, 0);
-  if (rc) return rc;
-  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
-  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
-  if (!io || !r) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : "rollout io");
-  if (!h->assigned || !h->bound || h->cfg.n_agents != 1)
-    return fail(RX_EINVAL, "%s: the handle must be an assigned, bound single-agent handle", fn);
-  if ((rc = rollout_dims(fn, h, r)) != 0 || (rc = rollout_bufs(fn, r)) != 0) return rc;
-  if (!io->terminated || !io->info)
-    return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
-                !io->terminated ? "terminated" : "info");
-  return rollout_loop(fn, h, io, r, tc, precision, stream);
-}
-
-// ABI v25, additive: the track curriculum for self-play (csrc/rx_track_duel.h).  The checks of the
-// three entry points and their host twins, before any HIP call.
-static int track_duel_io(const char* fn, const rx_track_duel_io* td) {
-  if (!td) return fail(RX_EINVAL, "%s: null track duel io", fn);
-  if (td->agent != 0 && td->agent != 1) return fail(RX_EINVAL, "%s: agent=%d must be 0 or 1", fn, td->agent);
-  if (!td->duel) return fail(RX_EINVAL, "%s: null duel", fn);
-  return RX_OK;
-}
-
-static int track_tally2_args(const char* fn, const rx_track_io* tc, const rx_track_duel_io* td, int64_t n,
-                             const float* done, const uint8_t* terminated, const double* info) {
-  int rc = track_args(fn, tc, 0);
-  if (rc || (rc = track_duel_io(fn, td)) != 0) return rc;
-  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
-  if (!done || !terminated || !info)
-    return fail(RX_EINVAL, "%s: null %s", fn, !done ? "done" : !terminated ? "terminated" : "info");
-  return RX_OK;
-}
-
-static int track_duel_scores_args(const char* fn, const rx_track_io* tc, const rx_track_duel_io* td, int32_t power,
-                                  double prior) {
-  if (!tc) return fail(RX_EINVAL, "%s: null track io", fn);
-  if (tc->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, tc->n_tracks);
-  if (!tc->tally || !tc->cdf || !tc->p)
-    return fail(RX_EINVAL, "%s: null %s", fn, !tc->tally ? "tally" : !tc->cdf ? "cdf" : "p");
-  if (tc->score < 0 || tc->score > 3) return fail(RX_EINVAL, "%s: score=%d outside 0..3", fn, tc->score);
-  const int rc = track_duel_io(fn, td);
-  if (rc) return rc;
-  if (power < 0 || power > 4) return fail(RX_EINVAL, "%s: power=%d outside 0..4", fn, power);
-  if (!(prior > 0.0)) return fail(RX_EINVAL, "%s: prior=%g must be > 0", fn, prior);
-  return RX_OK;
-}
-
-int rx_track_tally2(const rx_track_io* tc, const rx_track_duel_io* td, int64_t n, const float* done,
-                    const uint8_t* terminated, const double* info, void* stream) {
-  int rc = track_tally2_args("rx_track_tally2", tc, td, n, done, terminated, info);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_tally2(tc, td, n, done, terminated, info, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_tally2: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_tally2_host(const rx_track_io* tc, const rx_track_duel_io* td, int64_t n, const float* done,
-                         const uint8_t* terminated, const double* info, void* /*stream*/) {
-  const int rc = track_tally2_args("rx_track_tally2_host", tc, td, n, done, terminated, info);
-  if (rc) return rc;
-  rx_host_track_tally2(tc, td, n, done, terminated, info);
-  return RX_OK;
-}
-
-int rx_track_duel_scores(const rx_track_io* tc, const rx_track_duel_io* td, int32_t power, double prior,
-                         void* stream) {
-  int rc = track_duel_scores_args("rx_track_duel_scores", tc, td, power, prior);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_duel_scores(tc, td, power, prior, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_duel_scores: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_duel_scores_host(const rx_track_io* tc, const rx_track_duel_io* td, int32_t power, double prior,
-                              void* /*stream*/) {
-  const int rc = track_duel_scores_args("rx_track_duel_scores_host", tc, td, power, prior);
-  if (rc) return rc;
-  rx_host_track_duel_scores(tc, td, power, prior);
-  return RX_OK;
-}
-
-// the two-car rollout loop with the tally (two_car_rollout_loop); lg: the league's opponents, or null
-int rx_track_duel_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_selfplay_io* sp,
-                                const rx_league_io* lg, const rx_track_io* tc, const rx_track_duel_io* td,
-                                int32_t precision, void* stream) {
-  const char* fn = "rx_track_duel_rollout_steps";
-  // the track and league ios first: their refusals need no handle (tests/test_track_selfplay_cpu.py)
-  int rc = track_args(fn, tc, 0);
-  if (rc || (rc = track_duel_io(fn, td)) != 0) return rc;
-  if (lg && (rc = league_args(fn, lg, 2)) != 0) return rc;
-  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
-  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
-  if (!io || !r || !sp) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : !r ? "rollout io" : "self-play io");
-  if (!h->assigned || !h->bound || h->cfg.n_agents != 2 || h->D != 19)
-    return fail(RX_EINVAL, "%s: the handle must be an assigned, bound two-car handle with obs_dim 19", fn);
-  if ((rc = rollout_dims(fn, h, r)) != 0) return rc;
-  if (sp->agent != 0 && sp->agent != 1) return fail(RX_EINVAL, "%s: agent=%d must be 0 or 1", fn, sp->agent);
-  if (td->agent != sp->agent)
-    return fail(RX_EINVAL, "%s: agent %d of the track duel io != agent %d of the self-play io", fn, td->agent,
-                sp->agent);
-  if (lg && lg->agent != td->agent)
-    return fail(RX_EINVAL, "%s: agent %d of the league io != agent %d of the track duel io", fn, lg->agent, td->agent);
-  if ((rc = rollout_bufs(fn, r)) != 0 || (rc = selfplay_bufs(fn, sp, lg != nullptr)) != 0) return rc;
-  if (!lg && (rc = precision_arg(fn, "opp_precision", sp->opp_precision)) != 0) return rc;
-  if (!io->terminated || !io->info)
-    return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
-                !io->terminated ? "terminated" : "info");
-  return two_car_rollout_loop(h, io, r, sp, lg, precision, stream, tc, td);
-}
-
-// ABI v25, additive: episodic track draws (rx_track_episode, csrc/rx_curriculum.h).  The checks that
-// need no handle: rx_track_tally's, rx_track_draw's table and mix, and the episode io.
-// table: whether the draw reads tc->cdf (the replay forms read rx_track_learn_io's tables instead).
-static int track_episode_args(const char* fn, const rx_track_io* tc, const rx_track_episode_io* ep,
-                              bool table = true) {
-  const int rc = track_args(fn, tc, 0);
-  if (rc) return rc;
-  if (table && !tc->cdf) return fail(RX_EINVAL, "%s: null cdf", fn);
-  if (!ep) return fail(RX_EINVAL, "%s: null episode io", fn);
-  if (!ep->draws) return fail(RX_EINVAL, "%s: null draws", fn);
-  if (!ep->env_pos != !ep->pos_slot)
-    return fail(RX_EINVAL, "%s: null %s (env_pos and pos_slot: both or neither)", fn,
-                !ep->env_pos ? "env_pos" : "pos_slot");
-  if (!(ep->mix >= 0.0 && ep->mix <= 1.0)) return fail(RX_EINVAL, "%s: mix=%g outside [0, 1]", fn, ep->mix);
-  return RX_OK;
-}
-
-// the handle of the two handle-bound forms: lane-varying slots and next-step autoreset
-static int track_episode_handle(const char* fn, const rx_env* h, const rx_track_io* tc) {
-  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
-  if (!h->assigned || !h->bound || h->cfg.n_agents != 1)
-    return fail(RX_EINVAL, "%s: the handle must be an assigned, bound single-agent handle", fn);
-  if (!h->sched.lane_tracks)
-    return fail(RX_EINVAL, "%s: the handle's schedule is not lane-varying: set rx_config.lane_tracks = 1 (it needs "
-                           "one lane per env: with at most %d envs set dyn_lpe = 1 as well)", fn, RX_WIDE_N);
-  if (h->cfg.autoreset != RX_AUTORESET_NEXT_STEP)
-    return fail(RX_EINVAL, "%s: autoreset=%d must be RX_AUTORESET_NEXT_STEP: the step after a terminal one resets "
-                           "the env from the slot just drawn", fn, h->cfg.autoreset);
-  if (tc->track != h->st.track)
-    return fail(RX_EINVAL, "%s: track must be the handle's bound rx_state.track", fn);
-  return RX_OK;
-}
-
-int rx_track_episode(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, const float* done,
-                     const uint8_t* terminated, const double* info, void* stream) {
-  const char* fn = "rx_track_episode";
-  int rc = track_episode_args(fn, tc, ep);
-  if (rc || (rc = track_tally_args(fn, tc, n, done, terminated, info)) != 0) return rc;
-  if ((rc = rx_launch_track_episode(tc, ep, n, done, terminated, info, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_episode_host(const rx_track_io* tc, const rx_track_episode_io* ep, int64_t n, const float* done,
-                          const uint8_t* terminated, const double* info, void* /*stream*/) {
-  const char* fn = "rx_track_episode_host";
-  int rc = track_episode_args(fn, tc, ep);
-  if (rc || (rc = track_tally_args(fn, tc, n, done, terminated, info)) != 0) return rc;
-  rx_host_track_episode(tc, ep, n, done, terminated, info);
-  return RX_OK;
-}
-
-int rx_track_episode_step(rx_env* h, const rx_track_io* tc, const rx_track_episode_io* ep, const rx_io* io,
-                          const float* done, void* stream) {
-  const char* fn = "rx_track_episode_step";
-  int rc = track_episode_args(fn, tc, ep);
-  if (rc || (rc = track_episode_handle(fn, h, tc)) != 0) return rc;
-  if (!io) return fail(RX_EINVAL, "%s: null io", fn);
-  if (!done) done = io->done_f32;
-  if (!done || !io->terminated || !io->info)
-    return fail(RX_EINVAL, "%s: null %s", fn, !done ? "done" : !io->terminated ? "io->terminated" : "io->info");
-  rx_track_episode_io e = *ep;
-  e.env_pos = h->env_pos.p;
-  e.pos_slot = h->pos_slot.p;
-  if ((rc = rx_launch_track_episode(tc, &e, h->cfg.n_envs, done, io->terminated, io->info, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-// the single-agent rollout loop with the tally and the episodic draw (rollout_loop)
-int rx_track_episodic_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
-                                    const rx_track_episode_io* ep, int32_t* slots, int32_t precision, void* stream) {
-  const char* fn = "rx_track_episodic_rollout_steps";
-  // the track and episode ios first: their refusals need no handle
-  int rc = track_episode_args(fn, tc, ep);
-  if (rc) return rc;
-  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
-  if ((rc = track_episode_handle(fn, h, tc)) != 0) return rc;
-  if (!io || !r) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : "rollout io");
-  if ((rc = rollout_dims(fn, h, r)) != 0 || (rc = rollout_bufs(fn, r)) != 0) return rc;
-  if (!io->terminated || !io->info)
-    return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
-                !io->terminated ? "terminated" : "info");
-  rx_track_episode_io e = *ep;
-  e.env_pos = h->env_pos.p;
-  e.pos_slot = h->pos_slot.p;
-  return rollout_loop(fn, h, io, r, tc, precision, stream, &e, slots);
-}
-
-// ABI v25, additive: the curriculum's replay scores (csrc/rx_track_replay.h).  The checks of the four
-// entry points and their host twins, before any HIP call.
-static int learn_null(const char* fn, const char* name) { return fail(RX_EINVAL, "%s: null %s", fn, name); }
-
-static int learn_io(const char* fn, const rx_track_learn_io* lt) {
-  if (!lt) return fail(RX_EINVAL, "%s: null track learn io", fn);
-  if (lt->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, lt->n_tracks);
-  return RX_OK;
-}
-
-static int learn_tally_args(const char* fn, const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv) {
-  const int rc = learn_io(fn, lt);
-  if (rc) return rc;
-  if (lt->kind != 0 && lt->kind != 1) return fail(RX_EINVAL, "%s: kind=%d must be 0 or 1", fn, lt->kind);
-  if (!lt->track) return learn_null(fn, "track");
-  if (!lt->learn) return learn_null(fn, "learn");
-  if (T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, T);
-  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
-  if (!adv) return learn_null(fn, "adv");
-  return RX_OK;
-}
-
-static int learn_fold_args(const char* fn, const rx_track_learn_io* lt, double alpha) {
-  const int rc = learn_io(fn, lt);
-  if (rc) return rc;
-  if (!lt->learn) return learn_null(fn, "learn");
-  if (!lt->score) return learn_null(fn, "score");
-  if (!lt->seen) return learn_null(fn, "seen");
-  if (!(alpha > 0.0 && alpha <= 1.0)) return fail(RX_EINVAL, "%s: alpha=%g outside (0, 1]", fn, alpha);
-  return RX_OK;
-}
-
-static int learn_tables_args(const char* fn, const rx_track_learn_io* lt, int32_t power, int32_t now) {
-  const int rc = learn_io(fn, lt);
-  if (rc) return rc;
-  if (!lt->score) return learn_null(fn, "score");
-  if (!lt->seen) return learn_null(fn, "seen");
-  if (!lt->rank) return learn_null(fn, "rank");
-  if (!lt->cdf_score) return learn_null(fn, "cdf_score");
-  if (!lt->cdf_stale) return learn_null(fn, "cdf_stale");
-  if (power < 0 || power > 10) return fail(RX_EINVAL, "%s: power=%d outside 0..10", fn, power);
-  if (now < 0) return fail(RX_EINVAL, "%s: now=%d must be >= 0", fn, now);
-  return RX_OK;
-}
-
-static int learn_draw_args(const char* fn, const rx_track_learn_io* lt, int64_t n, double mix, double stale_mix) {
-  const int rc = learn_io(fn, lt);
-  if (rc) return rc;
-  if (!lt->cdf_score) return learn_null(fn, "cdf_score");
-  if (!lt->track_of_env) return learn_null(fn, "track_of_env");
-  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
-  if (!(mix >= 0.0 && mix <= 1.0)) return fail(RX_EINVAL, "%s: mix=%g outside [0, 1]", fn, mix);
-  if (!(stale_mix >= 0.0 && stale_mix <= 1.0))
-    return fail(RX_EINVAL, "%s: stale_mix=%g outside [0, 1]", fn, stale_mix);
-  if (!(mix + stale_mix <= 1.0))
-    return fail(RX_EINVAL, "%s: mix + stale_mix = %g + %g above 1", fn, mix, stale_mix);
-  if (stale_mix > 0.0 && !lt->cdf_stale) return learn_null(fn, "cdf_stale");
-  return RX_OK;
-}
-
-int rx_track_learn_tally(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv, void* stream) {
-  int rc = learn_tally_args("rx_track_learn_tally", lt, T, n, adv);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_learn_tally(lt, T, n, adv, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_learn_tally: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_learn_tally_host(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv, void* /*stream*/) {
-  const int rc = learn_tally_args("rx_track_learn_tally_host", lt, T, n, adv);
-  if (rc) return rc;
-  rx_host_track_learn_tally(lt, T, n, adv);
-  return RX_OK;
-}
-
-int rx_track_learn_fold(const rx_track_learn_io* lt, int32_t update, double alpha, void* stream) {
-  int rc = learn_fold_args("rx_track_learn_fold", lt, alpha);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_learn_fold(lt, update, alpha, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_learn_fold: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_learn_fold_host(const rx_track_learn_io* lt, int32_t update, double alpha, void* /*stream*/) {
-  const int rc = learn_fold_args("rx_track_learn_fold_host", lt, alpha);
-  if (rc) return rc;
-  rx_host_track_learn_fold(lt, update, alpha);
-  return RX_OK;
-}
-
-int rx_track_learn_tables(const rx_track_learn_io* lt, int32_t power, int32_t now, void* stream) {
-  int rc = learn_tables_args("rx_track_learn_tables", lt, power, now);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_learn_tables(lt, power, now, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_learn_tables: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_learn_tables_host(const rx_track_learn_io* lt, int32_t power, int32_t now, void* /*stream*/) {
-  const int rc = learn_tables_args("rx_track_learn_tables_host", lt, power, now);
-  if (rc) return rc;
-  rx_host_track_learn_tables(lt, power, now);
-  return RX_OK;
-}
-
-int rx_track_learn_draw(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix, double stale_mix,
-                        void* stream) {
-  int rc = learn_draw_args("rx_track_learn_draw", lt, n, mix, stale_mix);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_learn_draw(lt, n, generation, mix, stale_mix, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_learn_draw: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_learn_draw_host(const rx_track_learn_io* lt, int64_t n, uint32_t generation, double mix,
-                             double stale_mix, void* /*stream*/) {
-  const int rc = learn_draw_args("rx_track_learn_draw_host", lt, n, mix, stale_mix);
-  if (rc) return rc;
-  rx_host_track_learn_draw(lt, n, generation, mix, stale_mix);
-  return RX_OK;
-}
-
-// ABI v25, additive: the replay scores on episodic draws -- the tally by per-step slot and the
-// episode-end draw from the replay tables (csrc/rx_track_replay.h).  Checks before any HIP call.
-static int learn_tally_slots_args(const char* fn, const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
-                                  const int32_t* slots) {
-  const int rc = learn_io(fn, lt);
-  if (rc) return rc;
-  if (lt->kind != 0 && lt->kind != 1) return fail(RX_EINVAL, "%s: kind=%d must be 0 or 1", fn, lt->kind);
-  if (!lt->learn) return learn_null(fn, "learn");
-  if (T <= 0) return fail(RX_EINVAL, "%s: T=%d must be > 0", fn, T);
-  if (n <= 0 || n > INT32_MAX) return fail(RX_EINVAL, "%s: n=%lld must be in 1..2^31-1", fn, (long long)n);
-  if (!adv) return learn_null(fn, "adv");
-  if (!slots) return learn_null(fn, "slots");
-  return RX_OK;
-}
-
-int rx_track_learn_tally_slots(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
-                               const int32_t* slots, const float* dones, void* stream) {
-  const char* fn = "rx_track_learn_tally_slots";
-  int rc = learn_tally_slots_args(fn, lt, T, n, adv, slots);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_learn_tally_slots(lt, T, n, adv, slots, dones, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_learn_tally_slots_host(const rx_track_learn_io* lt, int32_t T, int64_t n, const float* adv,
-                                    const int32_t* slots, const float* dones, void* /*stream*/) {
-  const int rc = learn_tally_slots_args("rx_track_learn_tally_slots_host", lt, T, n, adv, slots);
-  if (rc) return rc;
-  rx_host_track_learn_tally_slots(lt, T, n, adv, slots, dones);
-  return RX_OK;
-}
-
-// the checks of the replay episodic forms that need no handle: rx_track_episode's but for tc->cdf,
-// then the learn io's tables and the two mixes (rx_track_learn_draw's rules)
-static int learn_episode_args(const char* fn, const rx_track_io* tc, const rx_track_learn_io* lt,
-                              const rx_track_episode_io* ep, double stale_mix) {
-  int rc = track_episode_args(fn, tc, ep, false);
-  if (rc || (rc = learn_io(fn, lt)) != 0) return rc;
-  if (lt->n_tracks != tc->n_tracks)
-    return fail(RX_EINVAL, "%s: n_tracks=%d of the track learn io != n_tracks=%d of the track io", fn, lt->n_tracks,
-                tc->n_tracks);
-  if (!lt->cdf_score) return learn_null(fn, "cdf_score");
-  if (!(stale_mix >= 0.0 && stale_mix <= 1.0))
-    return fail(RX_EINVAL, "%s: stale_mix=%g outside [0, 1]", fn, stale_mix);
-  if (!(ep->mix + stale_mix <= 1.0))
-    return fail(RX_EINVAL, "%s: mix + stale_mix = %g + %g above 1", fn, ep->mix, stale_mix);
-  if (stale_mix > 0.0 && !lt->cdf_stale) return learn_null(fn, "cdf_stale");
-  return RX_OK;
-}
-
-int rx_track_learn_episode(const rx_track_io* tc, const rx_track_learn_io* lt, const rx_track_episode_io* ep,
-                           double stale_mix, int64_t n, const float* done, const uint8_t* terminated,
-                           const double* info, void* stream) {
-  const char* fn = "rx_track_learn_episode";
-  int rc = learn_episode_args(fn, tc, lt, ep, stale_mix);
-  if (rc || (rc = track_tally_args(fn, tc, n, done, terminated, info)) != 0) return rc;
-  if ((rc = rx_launch_track_learn_episode(tc, lt, ep, stale_mix, n, done, terminated, info, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_learn_episode_host(const rx_track_io* tc, const rx_track_learn_io* lt, const rx_track_episode_io* ep,
-                                double stale_mix, int64_t n, const float* done, const uint8_t* terminated,
-                                const double* info, void* /*stream*/) {
-  const char* fn = "rx_track_learn_episode_host";
-  int rc = learn_episode_args(fn, tc, lt, ep, stale_mix);
-  if (rc || (rc = track_tally_args(fn, tc, n, done, terminated, info)) != 0) return rc;
-  rx_host_track_learn_episode(tc, lt, ep, stale_mix, n, done, terminated, info);
-  return RX_OK;
-}
-
-int rx_track_learn_episode_step(rx_env* h, const rx_track_io* tc, const rx_track_learn_io* lt,
-                                const rx_track_episode_io* ep, double stale_mix, const rx_io* io, const float* done,
-                                void* stream) {
-  const char* fn = "rx_track_learn_episode_step";
-  int rc = learn_episode_args(fn, tc, lt, ep, stale_mix);
-  if (rc || (rc = track_episode_handle(fn, h, tc)) != 0) return rc;
-  if (!io) return fail(RX_EINVAL, "%s: null io", fn);
-  if (!done) done = io->done_f32;
-  if (!done || !io->terminated || !io->info)
-    return fail(RX_EINVAL, "%s: null %s", fn, !done ? "done" : !io->terminated ? "io->terminated" : "io->info");
-  rx_track_episode_io e = *ep;
-  e.env_pos = h->env_pos.p;
-  e.pos_slot = h->pos_slot.p;
-  if ((rc = rx_launch_track_learn_episode(tc, lt, &e, stale_mix, h->cfg.n_envs, done, io->terminated, io->info,
-                                          (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "%s: launch failed: %s", fn, hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-// the single-agent rollout loop with the tally and the episodic draw from the replay tables (rollout_loop)
-int rx_track_learn_episodic_rollout_steps(rx_env* h, const rx_io* io, const rx_rollout_io* r, const rx_track_io* tc,
-                                          const rx_track_learn_io* lt, const rx_track_episode_io* ep, double stale_mix,
-                                          int32_t* slots, int32_t precision, void* stream) {
-  const char* fn = "rx_track_learn_episodic_rollout_steps";
-  // the track, learn and episode ios first: their refusals need no handle
-  int rc = learn_episode_args(fn, tc, lt, ep, stale_mix);
-  if (rc) return rc;
-  if ((rc = precision_arg(fn, "precision", precision)) != 0) return rc;
-  if ((rc = track_episode_handle(fn, h, tc)) != 0) return rc;
-  if (!io || !r) return fail(RX_EINVAL, "%s: null %s", fn, !io ? "io" : "rollout io");
-  if ((rc = rollout_dims(fn, h, r)) != 0 || (rc = rollout_bufs(fn, r)) != 0) return rc;
-  if (!io->terminated || !io->info)
-    return fail(RX_EINVAL, "%s: null io->%s (the tally reads the terminal step's rows)", fn,
-                !io->terminated ? "terminated" : "info");
-  rx_track_episode_io e = *ep;
-  e.env_pos = h->env_pos.p;
-  e.pos_slot = h->pos_slot.p;
-  return rollout_loop(fn, h, io, r, tc, precision, stream, &e, slots, lt, stale_mix);
-}
-
-// ABI v25, additive: track evolution (csrc/rx_track_evolve.h).  The checks of the two entry points and
-// their host twins, before any HIP call.
-static int evolve_null(const char* fn, const char* name) { return fail(RX_EINVAL, "%s: null %s", fn, name); }
-
-static int evolve_io(const char* fn, const rx_track_evolve_io* ev) {
-  if (!ev) return fail(RX_EINVAL, "%s: null track evolve io", fn);
-  if (ev->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, ev->n_tracks);
-  if (ev->n_spawn < 0 || ev->n_spawn > ev->n_tracks)
-    return fail(RX_EINVAL, "%s: n_spawn=%d outside 0..n_tracks=%d", fn, ev->n_spawn, ev->n_tracks);
-  if (ev->n_spawn > 0) {
-    if (!ev->slots) return evolve_null(fn, "slots");
-    if (!ev->plan) return evolve_null(fn, "plan");
-  }
-  if (!ev->cp_off) return evolve_null(fn, "cp_off");
-  return RX_OK;
-}
-
-static int evolve_plan_args(const char* fn, const rx_track_evolve_io* ev, double edit_frac) {
-  const int rc = evolve_io(fn, ev);
-  if (rc) return rc;
-  if (!ev->cdf_score) return evolve_null(fn, "cdf_score");
-  if (!(edit_frac >= 0.0 && edit_frac <= 1.0))
-    return fail(RX_EINVAL, "%s: edit_frac=%g outside [0, 1]", fn, edit_frac);
-  return RX_OK;
-}
-
-static int evolve_args(const char* fn, const rx_track_evolve_io* ev) {
-  const int rc = evolve_io(fn, ev);
-  if (rc) return rc;
-  if (!ev->cp) return evolve_null(fn, "cp");
-  if (!ev->width) return evolve_null(fn, "width");
-  if (!ev->cp_off_new) return evolve_null(fn, "cp_off_new");
-  if (!ev->cp_new) return evolve_null(fn, "cp_new");
-  if (!ev->width_new) return evolve_null(fn, "width_new");
-  return RX_OK;
-}
-
-int rx_track_evolve_plan(const rx_track_evolve_io* ev, uint32_t generation, double edit_frac, void* stream) {
-  int rc = evolve_plan_args("rx_track_evolve_plan", ev, edit_frac);
-  if (rc) return rc;
-  if (ev->n_spawn == 0) return RX_OK;
-  if ((rc = rx_launch_track_evolve_plan(ev, generation, edit_frac, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_evolve_plan: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_evolve_plan_host(const rx_track_evolve_io* ev, uint32_t generation, double edit_frac, void* /*stream*/) {
-  const int rc = evolve_plan_args("rx_track_evolve_plan_host", ev, edit_frac);
-  if (rc) return rc;
-  rx_host_track_evolve_plan(ev, generation, edit_frac);
-  return RX_OK;
-}
-
-int rx_track_evolve(const rx_track_evolve_io* ev, uint32_t generation, void* stream) {
-  int rc = evolve_args("rx_track_evolve", ev);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_evolve(ev, generation, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_evolve: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_evolve_host(const rx_track_evolve_io* ev, uint32_t generation, void* /*stream*/) {
-  const int rc = evolve_args("rx_track_evolve_host", ev);
-  if (rc) return rc;
-  rx_host_track_evolve(ev, generation);
-  return RX_OK;
-}
-
-// ABI v25, additive: track evolution in place.  which: 0 classes, 1 inplace, 2 commit.
-static int evolve_inplace_args(const char* fn, const rx_track_evolve_inplace_io* ev, int which, double edit_frac) {
-  if (!ev) return fail(RX_EINVAL, "%s: null track evolve inplace io", fn);
-  if (ev->n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks=%d must be > 0", fn, ev->n_tracks);
-  if (ev->n_spawn < 0 || ev->n_spawn > ev->n_tracks)
-    return fail(RX_EINVAL, "%s: n_spawn=%d outside 0..n_tracks=%d", fn, ev->n_spawn, ev->n_tracks);
-  if (which == 1 && !(edit_frac >= 0.0 && edit_frac <= 1.0))
-    return fail(RX_EINVAL, "%s: edit_frac=%g outside [0, 1]", fn, edit_frac);
-  if (which != 0 && ev->n_spawn == 0) return RX_OK;  // nothing is read
-  if (which != 0 && !ev->slots) return evolve_null(fn, "slots");
-  if (!ev->cp_off) return evolve_null(fn, "cp_off");
-  if (which != 0) {
-    if (!ev->cp) return evolve_null(fn, "cp");
-    if (!ev->width) return evolve_null(fn, "width");
-  }
-  if (which == 0 && !ev->cdf_score) return evolve_null(fn, "cdf_score");
-  if (which != 2) {
-    if (!ev->order) return evolve_null(fn, "order");
-    if (!ev->cdf_class) return evolve_null(fn, "cdf_class");
-    if (!ev->class_end) return evolve_null(fn, "class_end");
-  }
-  if (which == 1 && !ev->plan) return evolve_null(fn, "plan");
-  if (which != 0) {
-    if (!ev->out_off) return evolve_null(fn, "out_off");
-    if (!ev->cp_out) return evolve_null(fn, "cp_out");
-    if (!ev->width_out) return evolve_null(fn, "width_out");
-  }
-  return RX_OK;
-}
-
-int rx_track_evolve_classes(const rx_track_evolve_inplace_io* ev, void* stream) {
-  int rc = evolve_inplace_args("rx_track_evolve_classes", ev, 0, 0.0);
-  if (rc) return rc;
-  if ((rc = rx_launch_track_evolve_classes(ev, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_evolve_classes: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_evolve_classes_host(const rx_track_evolve_inplace_io* ev, void* /*stream*/) {
-  const int rc = evolve_inplace_args("rx_track_evolve_classes_host", ev, 0, 0.0);
-  if (rc) return rc;
-  rx_host_track_evolve_classes(ev);
-  return RX_OK;
-}
-
-int rx_track_evolve_inplace(const rx_track_evolve_inplace_io* ev, uint32_t generation, double edit_frac, void* stream) {
-  int rc = evolve_inplace_args("rx_track_evolve_inplace", ev, 1, edit_frac);
-  if (rc) return rc;
-  if (ev->n_spawn == 0) return RX_OK;
-  if ((rc = rx_launch_track_evolve_inplace(ev, generation, edit_frac, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_evolve_inplace: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_evolve_inplace_host(const rx_track_evolve_inplace_io* ev, uint32_t generation, double edit_frac,
-                                 void* /*stream*/) {
-  const int rc = evolve_inplace_args("rx_track_evolve_inplace_host", ev, 1, edit_frac);
-  if (rc) return rc;
-  if (ev->n_spawn == 0) return RX_OK;
-  rx_host_track_evolve_inplace(ev, generation, edit_frac);
-  return RX_OK;
-}
-
-int rx_track_evolve_commit(const rx_track_evolve_inplace_io* ev, void* stream) {
-  int rc = evolve_inplace_args("rx_track_evolve_commit", ev, 2, 0.0);
-  if (rc) return rc;
-  if (ev->n_spawn == 0) return RX_OK;
-  if ((rc = rx_launch_track_evolve_commit(ev, (hipStream_t)stream)) != 0)
-    return fail(RX_EHIP, "rx_track_evolve_commit: launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return RX_OK;
-}
-
-int rx_track_evolve_commit_host(const rx_track_evolve_inplace_io* ev, void* /*stream*/) {
-  const int rc = evolve_inplace_args("rx_track_evolve_commit_host", ev, 2, 0.0);
-  if (rc) return rc;
-  if (ev->n_spawn == 0) return RX_OK;
-  rx_host_track_evolve_commit(ev);
-  return RX_OK;
-}
-
-}  // extern "C"

@@ -2,7 +2,7 @@
 // (rx_track_tally_host / rx_track_episode_host / rx_track_scores_host /
 // rx_track_draw_host / rx_track_tally2_host / rx_track_duel_scores_host, ABI v25 additive): the loops of rx_curriculum.hip one env / one slot at a time over the
 // same rx_curriculum.h functions.  Compiled as plain C++ (not as HIP), so
-// rx_curriculum.h takes its host form; rx_api.cpp checks the arguments before it
+// rx_curriculum.h takes its host form; rx_api_curriculum.cpp checks the arguments before it
 // calls in here.  No HIP call.
 #include "rx.h"
 #include "rx_curriculum.h"

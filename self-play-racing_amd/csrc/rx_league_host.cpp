@@ -2,7 +2,7 @@
 // (rx_league_weights_host / rx_league_draw_host, ABI v25 additive): the loops of
 // rx_league.hip one slot / one env at a time over the same rx_league.h functions.
 // Compiled as plain C++ (not as HIP), so rx_league.h takes its host form;
-// rx_api.cpp checks the arguments before it calls in here.  No HIP call.
+// rx_api_curriculum.cpp checks the arguments before it calls in here.  No HIP call.
 #include "rx.h"
 #include "rx_league.h"
 

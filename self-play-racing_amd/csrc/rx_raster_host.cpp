@@ -1,7 +1,7 @@
 // rx_raster_host.cpp -- the host twins of the renderer's kernels
 // (rx_raster_*_host, ABI v25 additive): the loops of rx_render.hip one pixel at
 // a time over the same rx_raster.h functions.  Compiled as plain C++ (not as
-// HIP), so rx_math.h and rx_raster.h take their host form; rx_api.cpp checks
+// HIP), so rx_math.h and rx_raster.h take their host form; rx_api_tracks.cpp checks
 // the arguments before it calls in here.  No HIP call.
 #include <algorithm>
 #include <cstring>

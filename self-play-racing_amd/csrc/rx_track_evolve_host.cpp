@@ -2,7 +2,7 @@
 // (rx_track_evolve_plan_host / rx_track_evolve_host and the in-place form's
 // rx_track_evolve_classes_host / _inplace_host / _commit_host, ABI v25 additive): the loops of
 // rx_track_evolve.hip one slot at a time over the same rx_track_evolve.h functions.
-// Compiled as plain C++ (not as HIP); rx_api.cpp checks the arguments before it
+// Compiled as plain C++ (not as HIP); rx_api_curriculum.cpp checks the arguments before it
 // calls in here.  No HIP call.
 #include "rx.h"
 #include "rx_track_evolve.h"

@@ -2,7 +2,7 @@
 // (rx_track_learn_tally_host / _tally_slots_host / _fold_host / _tables_host / _draw_host /
 // rx_track_learn_episode_host, ABI v25 additive): the loops of rx_track_replay.hip one value / one slot / one env at a
 // time over the same rx_track_replay.h functions.  Compiled as plain C++ (not as
-// HIP); rx_api.cpp checks the arguments before it calls in here.  No HIP call.
+// HIP); rx_api_curriculum.cpp checks the arguments before it calls in here.  No HIP call.
 #include <algorithm>
 #include <vector>
 
