@@ -1717,9 +1717,13 @@ __device__ __forceinline__ void leaf_segments(const double4* __restrict__ seg, i
 // them; bestf >= best.  |b * id| stays far below f32 overflow: no double lies
 // within 2^-64 of an odd multiple of pi/2 at the angles a car reaches, so a
 // nonzero cos / sin rounds to |d| > 2^-65 and |id| < 2^65.  An f32
-// direction component of 0 makes id and c infinite: b * inf + c is +-inf or
-// NaN, and fmin / fmax drop a NaN, leaving the axis unconstrained -- more
-// boxes kept, never fewer.
+// direction component of 0 (the sine of angle 0: the one double whose sine
+// is 0) would make id and c infinite and b * inf + c a NaN wherever b and c
+// differ in sign -- and fmin(NaN, +inf) = +inf is an entry at infinity, not an
+// unconstrained axis: an origin at y = -3 lost the box y in [-5, 4].  The
+// caller therefore gives such an axis id = 0 and c = -inf / +inf (rays_wave):
+// every box's slab is (-inf, +inf) there, the axis constrains nothing -- more
+// boxes kept, never fewer -- and no NaN reaches the tests below.
 // The box decision from the slab interval [lo, hi] (entry clamped at -mtf):
 // x = lo - |lo| k and y = hi + |hi| k bound the exact entry from below and
 // the exit from above (k = 2^-20 covers the <= 6 * 2^-24 relative roundings
@@ -1758,9 +1762,8 @@ __device__ __forceinline__ void ray_finish(const rx_kargs& a, int pos, int q, in
 // are the matching origin offsets (times id), so each axis' entry / exit distance needs no
 // min / max (4 fewer VALU).  Same decision as chunk_needed_f: with the axis'
 // direction sign fixed, rounding is monotone, so min(t1, t2) IS the near
-// plane's t and max(t1, t2) the far one's; only where chunk_needed_f meets a
-// NaN (0 * inf: origin on a slab plane, f32 direction component 0) does this
-// test drop the NaN and keep the box -- more conservative, never less.
+// plane's t and max(t1, t2) the far one's (an axis whose f32 direction
+// component is 0 comes with cn = -inf, cf = +inf and id = 0: open in both).
 template <bool LV = false>
 __device__ __forceinline__ bool chunk_needed_q(const float* __restrict__ box, rx_f2 cn, rx_f2 cf, rx_f2 id2,
                                                float mtf, float bm) {
@@ -1992,7 +1995,13 @@ __device__ __forceinline__ void rays_wave(const rx_kargs& a, const rx_wave we, c
     const float mtf = (float)mt * (1.0f + 0x1p-20f) + 1e-6f;
     const rx_f2 nlo = {-(oxf + mbf), -(oyf + mbf)}, nhi = {mbf - oxf, mbf - oyf};
     const float csf = (float)cs, snf = (float)sn;
-    const rx_f2 id2 = {1.0f / csf, 1.0f / snf};
+    // an axis the f32 direction does not move along is open: id = 0, offsets -inf / +inf (chunk_needed_f)
+    const bool zx = csf == 0.0f, zy = snf == 0.0f;
+    const rx_f2 id2 = {zx ? 0.0f : 1.0f / csf, zy ? 0.0f : 1.0f / snf};
+    auto open_axes = [&](rx_f2& c1, rx_f2& c2) {
+      c1.x = zx ? -__builtin_inff() : c1.x, c2.x = zx ? __builtin_inff() : c2.x;
+      c1.y = zy ? -__builtin_inff() : c1.y, c2.y = zy ? __builtin_inff() : c2.y;
+    };
     // visit chunks outward from the wave's first car
     int w0 = (int)(ldc(a.ray_hint + i) * (double)W + 0.5);  // (the order of the visits only, never the minimum)
     w0 = w0 < 0 ? 0 : (w0 >= W ? W - 1 : w0);
@@ -2022,11 +2031,15 @@ __device__ __forceinline__ void rays_wave(const rx_kargs& a, const rx_wave we, c
       if (!LV && a.box_quadrants && __all(quad == quad0)) {
         const rx_f2 nn = {(quad0 & 1) ? nhi.x : nlo.x, (quad0 & 2) ? nhi.y : nlo.y};
         const rx_f2 nf = {(quad0 & 1) ? nlo.x : nhi.x, (quad0 & 2) ? nlo.y : nhi.y};
-        cull_scan<true, F, LPR, LV, PF>(a, k, W, nch, seg, c0, quad0 + 1, nn * id2, nf * id2, id2, mtf, ox, oy, v3x,
-                                    v3y, best, bestf, tested, scanned, pf);
+        rx_f2 c1 = nn * id2, c2 = nf * id2;
+        open_axes(c1, c2);
+        cull_scan<true, F, LPR, LV, PF>(a, k, W, nch, seg, c0, quad0 + 1, c1, c2, id2, mtf, ox, oy, v3x, v3y, best,
+                                    bestf, tested, scanned, pf);
       } else {
-        cull_scan<false, F, LPR, LV, PF>(a, k, W, nch, seg, c0, 0, nlo * id2, nhi * id2, id2, mtf, ox, oy, v3x, v3y,
-                                     best, bestf, tested, scanned, pf);
+        rx_f2 c1 = nlo * id2, c2 = nhi * id2;
+        open_axes(c1, c2);
+        cull_scan<false, F, LPR, LV, PF>(a, k, W, nch, seg, c0, 0, c1, c2, id2, mtf, ox, oy, v3x, v3y, best, bestf,
+                                     tested, scanned, pf);
       }
     };
     // LV: no float32 pre-filter -- with per-lane segment loads the filter's extra
