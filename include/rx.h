@@ -1572,6 +1572,50 @@ int rx_track_evolve_inplace_host(const rx_track_evolve_inplace_io* ev, uint32_t 
 int rx_track_evolve_commit(const rx_track_evolve_inplace_io* ev, void* stream);
 int rx_track_evolve_commit_host(const rx_track_evolve_inplace_io* ev, void* stream);
 
+/* ABI v25, additive: POSITIONS REGROUPED BY SLOT -- on the lane-varying schedule a wave holds 64
+ * consecutive positions of any slots, rx_assign orders the positions by slot, and every episodic
+ * draw (rx_track_episode_step) sends one env to another slot and leaves it where it sits.  The
+ * regroup puts the positions back in slot order on the device: it resets nothing and leaves
+ * every env-order output as it would have been (DESIGN.md §3 "Positions regrouped by slot").
+ *
+ * The plan.  New position j holds what old position src[j] held, where src is the old
+ * positions ordered by (pos_slot[p], p) ascending -- a STABLE sort, so the layout is a function
+ * of its inputs alone (unlike the spatial re-sort's, whose order inside a bin follows the
+ * arrival of atomics), and
+ *   perm_out[j] = perm[src[j]],  pos_slot_out[j] = pos_slot[src[j]],  env_pos_out[perm_out[j]] = j.
+ * rx_regroup_plan_host: HOST pointers, plain C++, no HIP call; it takes no stream and is not one
+ * of the (device, host) pairs that share a body and a refusal table.  RX_EINVAL, each with its own
+ * message and nothing written: n < 0, n_tracks <= 0, a null pointer, a slot outside
+ * [0, n_tracks), a perm entry outside [0, n).  The outputs must not overlap the inputs.
+ * rx_regroup_plan: the same arrays as DEVICE pointers, a scratch buffer of at least
+ * rx_regroup_scratch_bytes(n, n_tracks) bytes (4-byte aligned; -1 for n < 0 or n_tracks <= 0)
+ * and a stream.  Launches only: no allocation, no host wait, no transfer.  It equals the
+ * twin element for element on every input the twin accepts; on others it writes some
+ * permutation and never outside its buffers.  Checked before any launch (RX_EINVAL): n,
+ * n_tracks, null pointers, scratch_bytes too small, scratch misaligned.
+ *
+ * rx_regroup_slots: the move on a live handle -- the plan from the handle's env order and
+ * position slots, the working-state rows gathered by src into the shadow copy, and state,
+ * env order and position slots copied back; the env's position array becomes the inverse of
+ * the new order.  Every buffer keeps its address and the scratch was reserved by rx_assign,
+ * so the call is stream-ordered and may be captured.  To be called between two calls that
+ * step the env (never inside one: rx_steps' snapshots are indexed by position within a call).
+ * Refused before any launch: null handle RX_EINVAL; no track table, no assignment or no
+ * bound state RX_ESTATE; a two-car handle RX_EINVAL; a schedule that is not lane-varying
+ * RX_EINVAL (the grouped and wide schedules bind waves to slots: rx_assign is their regroup).
+ *
+ * rx_lane_layout: a blocking download of the env order, the slot at each position and the
+ * position of each env (int32 [n_envs] each, HOST pointers), for tests and tools; the same
+ * refusals, and RX_EINVAL for a null output. */
+int32_t rx_regroup_plan_host(int32_t n, int32_t n_tracks, const int32_t* perm, const int32_t* pos_slot,
+                             int32_t* src_out, int32_t* perm_out, int32_t* pos_slot_out, int32_t* env_pos_out);
+int64_t rx_regroup_scratch_bytes(int32_t n, int32_t n_tracks);
+int rx_regroup_plan(int32_t n, int32_t n_tracks, const int32_t* perm, const int32_t* pos_slot, int32_t* src_out,
+                    int32_t* perm_out, int32_t* pos_slot_out, int32_t* env_pos_out, void* scratch,
+                    int64_t scratch_bytes, void* stream);
+int rx_regroup_slots(rx_env* h, void* stream);
+int rx_lane_layout(rx_env* h, int32_t* perm_out, int32_t* pos_slot_out, int32_t* env_pos_out);
+
 #ifdef __cplusplus
 }
 #endif

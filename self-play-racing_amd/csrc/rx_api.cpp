@@ -212,6 +212,10 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
   if (sc.lane_tracks) {  // the kernels read each position's slot: the order stays fixed
     if ((rc = upload(h->pos_slot, plan.pos_slot.data(), plan.pos_slot.size()))) return rc;
     if ((rc = upload(h->env_pos, plan.env_pos.data(), plan.env_pos.size()))) return rc;
+    if (A == 1) {  // rx_regroup_slots' buffers: here, so the call itself may run under capture
+      if ((rc = reserve(h->regroup_scratch, rx_regroup_scratch_size(N)))) return rc;
+      if ((rc = reserve(h->regroup_src, (size_t)N)) || (rc = reserve(h->regroup_slot, (size_t)N))) return rc;
+    }
   } else if (sc.sort_on) {  // the spatial re-sort's bins, keys and counters
     const size_t total = (size_t)sc.sort_bins;
     std::vector<uint32_t> zk(std::max<size_t>((size_t)N, total), 0u);
@@ -486,6 +490,89 @@ static int sort_envs_now(rx_env* h, hipStream_t s) {
   const int rc = rx_sort_envs(h->keys_in.p, h->keys_off.p, h->cfg.n_envs, h->cfg.n_agents, h->sort_hist.p,
                               h->sort_cursor.p, h->sched.sort_bins, h->perm[0].p, h->perm[1].p, &work, &tmp, s, hist_done);
   if (rc != 0) return fail(RX_EHIP, "spatial sort failed: %s", hipGetErrorString((hipError_t)rc));
+  return RX_OK;
+}
+
+// ---- positions regrouped by slot (ABI v25, additive; DESIGN.md §3 "Positions regrouped by slot")
+int32_t rx_regroup_plan_host(int32_t n, int32_t n_tracks, const int32_t* perm, const int32_t* pos_slot,
+                             int32_t* src_out, int32_t* perm_out, int32_t* pos_slot_out, int32_t* env_pos_out) {
+  std::string err;
+  const int rc = rx_plan_regroup(n, n_tracks, perm, pos_slot, src_out, perm_out, pos_slot_out, env_pos_out, &err);
+  return rc ? fail(rc, "%s", err.c_str()) : RX_OK;
+}
+
+int64_t rx_regroup_scratch_bytes(int32_t n, int32_t n_tracks) {
+  if (n < 0 || n_tracks <= 0) return -1;
+  return (int64_t)rx_regroup_scratch_size(n);
+}
+
+int rx_regroup_plan(int32_t n, int32_t n_tracks, const int32_t* perm, const int32_t* pos_slot, int32_t* src_out,
+                    int32_t* perm_out, int32_t* pos_slot_out, int32_t* env_pos_out, void* scratch,
+                    int64_t scratch_bytes, void* stream) {
+  const char* fn = "rx_regroup_plan";
+  if (n < 0) return fail(RX_EINVAL, "%s: n must be >= 0 (got %d)", fn, n);
+  if (n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks must be > 0 (got %d)", fn, n_tracks);
+  const void* ptrs[] = {perm, pos_slot, src_out, perm_out, pos_slot_out, env_pos_out, scratch};
+  const char* names[] = {"perm", "pos_slot", "src_out", "perm_out", "pos_slot_out", "env_pos_out", "scratch"};
+  for (int i = 0; i < 7; ++i)
+    if (!ptrs[i]) return fail(RX_EINVAL, "%s: null %s", fn, names[i]);
+  if (scratch_bytes < (int64_t)rx_regroup_scratch_size(n))
+    return fail(RX_EINVAL, "%s: scratch of %lld bytes, rx_regroup_scratch_bytes(%d, %d) = %lld", fn,
+                (long long)scratch_bytes, n, n_tracks, (long long)rx_regroup_scratch_size(n));
+  if ((uintptr_t)scratch % sizeof(uint32_t)) return fail(RX_EINVAL, "%s: scratch must be 4-byte aligned", fn);
+  return launched(fn, rx_launch_regroup_plan(n, n_tracks, perm, pos_slot, src_out, perm_out, pos_slot_out,
+                                             env_pos_out, scratch, (hipStream_t)stream));
+}
+
+// the handles the two entries below take: single-agent on the lane-varying schedule
+static int regroup_handle(const char* fn, const rx_env* h) {
+  if (!h) return fail(RX_EINVAL, "%s: null handle", fn);
+  if (h->n_tracks <= 0) return fail(RX_ESTATE, "%s: no track table (rx_upload_tracks)", fn);
+  if (!h->assigned) return fail(RX_ESTATE, "%s: no env assignment (rx_assign)", fn);
+  if (!h->bound) return fail(RX_ESTATE, "%s: no state bound (rx_bind_state)", fn);
+  if (h->cfg.n_agents != 1)
+    return fail(RX_EINVAL, "%s: a two-car handle: its schedule binds every wave to one slot (no plan resolves "
+                           "two-car envs to the lane-varying schedule), and rx_assign is its regroup", fn);
+  if (!h->sched.lane_tracks)
+    return fail(RX_EINVAL, "%s: the handle's schedule is not lane-varying: the grouped and wide schedules bind "
+                           "waves to slots and rx_assign is their regroup (rx_config.lane_tracks = 1)", fn);
+  return RX_OK;
+}
+
+// Plan from the live perm and pos_slot (the new perm into the shadow perm[1], env_pos rewritten in
+// place: the plan does not read it), gather the working rows into work_tmp by src, copy back.  Launches
+// only, on the caller's stream, into buffers rx_assign reserved: capturable, and every buffer the step,
+// rollout and episodic kernels read keeps its address.  Between calls that step the env nothing else is
+// indexed by position on this schedule (the pose snapshots and task rows of rx_steps live for one call;
+// the ray tasks are position-major and never re-ranked).
+int rx_regroup_slots(rx_env* h, void* stream) {
+  const char* fn = "rx_regroup_slots";
+  int rc = regroup_handle(fn, h);
+  if (rc) return rc;
+  const int N = h->cfg.n_envs;
+  if (!h->regroup_scratch.p || h->regroup_src.n < (size_t)N || h->regroup_slot.n < (size_t)N)
+    return fail(RX_ESTATE, "%s: no scratch (rx_assign reserves it)", fn);
+  const hipStream_t s = (hipStream_t)stream;
+  if ((rc = rx_launch_regroup_plan(N, h->n_tracks, h->perm[0].p, h->pos_slot.p, h->regroup_src.p, h->perm[1].p,
+                                   h->regroup_slot.p, h->env_pos.p, h->regroup_scratch.p, s)) != 0)
+    return launched(fn, rc);
+  rx_state work = h->work, tmp = h->work_tmp;
+  return launched(fn, rx_launch_regroup_move(N, h->regroup_src.p, h->perm[1].p, h->perm[0].p, h->regroup_slot.p,
+                                             h->pos_slot.p, &work, &tmp, s));
+}
+
+int rx_lane_layout(rx_env* h, int32_t* perm_out, int32_t* pos_slot_out, int32_t* env_pos_out) {
+  const char* fn = "rx_lane_layout";
+  if (!perm_out || !pos_slot_out || !env_pos_out)
+    return fail(RX_EINVAL, "%s: null %s", fn, !perm_out ? "perm_out" : !pos_slot_out ? "pos_slot_out" : "env_pos_out");
+  const int rc = regroup_handle(fn, h);
+  if (rc) return rc;
+  const size_t bytes = (size_t)h->cfg.n_envs * sizeof(int32_t);
+  RX_HIP(hipSetDevice(h->cfg.device));
+  RX_HIP(hipDeviceSynchronize());
+  RX_HIP(hipMemcpy(perm_out, h->perm[0].p, bytes, hipMemcpyDeviceToHost));
+  RX_HIP(hipMemcpy(pos_slot_out, h->pos_slot.p, bytes, hipMemcpyDeviceToHost));
+  RX_HIP(hipMemcpy(env_pos_out, h->env_pos.p, bytes, hipMemcpyDeviceToHost));
   return RX_OK;
 }
 

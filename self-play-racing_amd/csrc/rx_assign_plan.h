@@ -130,5 +130,11 @@ int rx_config_check(const rx_config* cfg, std::string* err);
 int rx_plan_assignment(const rx_config& cfg, int32_t n_tracks, const int32_t* wp_off, const int32_t* track_of_env,
                        rx_assignment* out, std::string* err);
 
+// rx_regroup_plan_host's body (rx_regroup_plan_host.cpp): the positions of a lane-varying env
+// regrouped by slot, a stable sort by (pos_slot[p], p).  RX_OK, or RX_EINVAL with the message in
+// *err and nothing written.  The outputs must not overlap the inputs.
+int rx_plan_regroup(int32_t n, int32_t n_tracks, const int32_t* perm, const int32_t* pos_slot, int32_t* src_out,
+                    int32_t* perm_out, int32_t* pos_slot_out, int32_t* env_pos_out, std::string* err);
+
 // rx_schedule's row (int32 [RX_SCHEDULE_W]) of a resolved schedule.
 void rx_sched_row(const rx_config& cfg, const rx_sched& s, int32_t dyn_calls, int32_t* out);

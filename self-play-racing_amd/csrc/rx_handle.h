@@ -102,6 +102,10 @@ struct rx_env {
   DevBuf<int32_t> pos_slot;                // with lane_tracks: [N] slot of the env at each position
   DevBuf<int32_t> env_pos;                 // with lane_tracks: [N] position of each env, the inverse of perm
                                            // (rx_track_episode_step: the episodic draw rewrites pos_slot)
+  // rx_regroup_slots (lane_tracks, single-agent; reserved by rx_assign so the call allocates nothing):
+  // the sort's scratch, src [N] and the new pos_slot [N] before the copy back (the new perm goes to perm[1])
+  DevBuf<uint8_t> regroup_scratch;
+  DevBuf<int32_t> regroup_src, regroup_slot;
   DevBuf<uint8_t> policy_frag;  // the bf16 rollout's operand fragments of both trunks (k_policy_frag, rx_rollout_steps)
   DevBuf<double> rel_angles;
   std::vector<double> rel_angles_h;

@@ -449,6 +449,17 @@ extern "C" int rx_sort_envs(const uint32_t* keys, uint32_t* off, int n, int A, u
 extern "C" int rx_launch_permutation(int64_t n, uint64_t seed, int64_t* out, hipStream_t s);
 extern "C" int rx_state_sync(const rx_state* work, const rx_state* user, const int32_t* perm, int n, int A,
                              int to_user, hipStream_t s);
+// positions regrouped by slot (rx_sort.hip; include/rx.h rx_regroup_plan): the stable order of the
+// positions by (pos_slot, position) and what follows from it, in `scratch` of rx_regroup_scratch_size(n)
+// bytes; rx_launch_regroup_move: the single-agent working rows gathered by src into the shadow copy
+// and copied back with the new perm and pos_slot
+extern "C" size_t rx_regroup_scratch_size(int n);
+extern "C" int rx_launch_regroup_plan(int n, int n_tracks, const int32_t* perm, const int32_t* pos_slot,
+                                      int32_t* src_out, int32_t* perm_out, int32_t* pos_slot_out, int32_t* env_pos_out,
+                                      void* scratch, hipStream_t s);
+extern "C" int rx_launch_regroup_move(int n, const int32_t* src, const int32_t* perm_tmp, int32_t* perm,
+                                      const int32_t* slot_tmp, int32_t* pos_slot, const rx_state* work,
+                                      const rx_state* tmp, hipStream_t s);
 // rx_eval_steps' per-step metric accumulation (rx_eval.hip): one lane per env position,
 // x / y / flags from the working state (position order), the rest in env order
 extern "C" int rx_launch_eval_acc(int n, int A, const int32_t* perm, const rx_state* work, const rx_io* io,

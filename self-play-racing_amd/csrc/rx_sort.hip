@@ -24,7 +24,12 @@
 // waves (not fixed run to run; nothing depends on it).
 //
 // rx_state_sync: the caller's bound arrays (env order) <-> the working copy.
+//
+// At the end of the file: the lane-varying schedule's regroup of the positions by slot
+// (rx_regroup_plan, rx_regroup_slots), a stable radix sort that moves the same rows.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "rx_internal.h"
 
@@ -314,5 +319,202 @@ extern "C" int rx_launch_permutation(int64_t n, uint64_t seed, int64_t* out, hip
   while (bits < 62 && (1ll << bits) < n) ++bits;  // 2^bits >= n and < 2n (cycle-walk length)
   const int64_t grid = (n + kBlock - 1) / kBlock;
   hipLaunchKernelGGL(k_feistel_perm, dim3((unsigned)grid), dim3(kBlock), 0, s, n, bits, seed, out);
+  return (int)hipGetLastError();
+}
+
+namespace {
+
+// ---- Positions regrouped by slot (lane-varying schedule; include/rx.h rx_regroup_plan,
+// DESIGN.md §3 "Positions regrouped by slot").  src = the old positions ordered by
+// (pos_slot[p], p): a STABLE sort, so the layout is the host twin's (rx_regroup_plan_host)
+// element for element and does not depend on the arrival order of anything.  LSD radix
+// sort of the position index on 8-bit digits of the slot, one pass per byte of
+// n_tracks - 1, each pass three launches over tiles of kBlock consecutive elements:
+//   k_rg_count    per workgroup: the tile's digit counts (LDS, integer adds) -> the
+//                 digit-major table cnt[d * nblk + b]
+//   k_rg_scan     one workgroup per digit: exclusive scan of the digit's row in place and the
+//                 row's total, so tile b's elements of digit d start at (digits below d) + row[b]
+//   k_rg_scatter  stable: an element's rank among the equal-digit lanes before it in its
+//                 wave from ballots (8, one per digit bit), the counts of the waves before
+//                 its own and the scan of the 256 digit totals from LDS; no atomics
+// k_rg_finish applies src to perm and pos_slot and writes the inverse of the new perm.
+// Nothing here can write outside its buffers whatever pos_slot or perm hold: the digits are
+// taken of the value as it is, the counts of a pass sum to n, and env_pos is written only
+// where the env id lies in [0, n).
+constexpr int kRgDigits = 256;
+
+__device__ __forceinline__ uint32_t rg_digit(const int32_t* __restrict__ pos_slot, int idx, int shift) {
+  return ((uint32_t)pos_slot[idx] >> shift) & (kRgDigits - 1);
+}
+
+// in == nullptr: the first pass, whose input order is the identity
+__global__ __launch_bounds__(kBlock) void k_rg_count(const int32_t* __restrict__ in,
+                                                      const int32_t* __restrict__ pos_slot, int n, int shift,
+                                                      int nblk, uint32_t* __restrict__ cnt) {
+  __shared__ uint32_t c[kRgDigits];
+  const int t = threadIdx.x, i = blockIdx.x * kBlock + t;
+  c[t] = 0u;
+  __syncthreads();
+  if (i < n) atomicAdd(&c[rg_digit(pos_slot, in ? in[i] : i, shift)], 1u);
+  __syncthreads();
+  cnt[(size_t)t * nblk + blockIdx.x] = c[t];  // kBlock == kRgDigits: thread t owns digit t
+}
+
+// one workgroup per digit: exclusive scan of the digit's row of tile counts in place (coalesced,
+// kBlock entries a turn with the running total carried), the row's total -> tot[d]
+__global__ __launch_bounds__(kBlock) void k_rg_scan(uint32_t* __restrict__ cnt, int nblk, uint32_t* __restrict__ tot) {
+  __shared__ uint32_t wtot[kBlock / 64];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  uint32_t* __restrict__ row = cnt + (size_t)blockIdx.x * nblk;
+  uint32_t carry = 0;
+  for (int b0 = 0; b0 < nblk; b0 += kBlock) {  // the same trips for every thread
+    const int b = b0 + t;
+    const uint32_t c = b < nblk ? row[b] : 0u;
+    uint32_t inc = c;  // inclusive scan within the wave, then over the wave totals
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += y;
+    }
+    if (lane == 63) wtot[w] = inc;
+    __syncthreads();
+    uint32_t run = carry + inc - c, all = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) {
+      if (k < w) run += wtot[k];
+      all += wtot[k];
+    }
+    if (b < nblk) row[b] = run;
+    carry += all;
+    __syncthreads();  // the next turn rewrites wtot
+  }
+  if (t == 0) tot[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(kBlock) void k_rg_scatter(const int32_t* __restrict__ in,
+                                                        const int32_t* __restrict__ pos_slot, int n, int shift,
+                                                        int nblk, const uint32_t* __restrict__ cnt,
+                                                        const uint32_t* __restrict__ tot, int32_t* __restrict__ out) {
+  __shared__ uint32_t wcnt[kBlock / 64][kRgDigits];
+  __shared__ uint32_t dbase[kRgDigits];  // first output index of each digit: the exclusive scan of tot
+  __shared__ uint32_t wsum[kBlock / 64];
+  const int t = threadIdx.x, i = blockIdx.x * kBlock + t, lane = t & 63, w = t >> 6;
+  const bool v = i < n;
+  const int idx = v ? (in ? in[i] : i) : 0;
+  const uint32_t d = v ? rg_digit(pos_slot, idx, shift) : 0u;
+  const uint32_t base = cnt[(size_t)d * nblk + blockIdx.x];  // the tile's first index within the digit
+  const uint32_t td = tot[t];  // kBlock == kRgDigits: thread t scans digit t's total
+  uint32_t inc = td;
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  if (lane == 63) wsum[w] = inc;
+#pragma unroll
+  for (int k = 0; k < kBlock / 64; ++k) wcnt[k][t] = 0u;
+  // the lanes of this wave that hold an element of the same digit
+  unsigned long long same = __ballot(v);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const unsigned long long m = __ballot((d >> b) & 1u);
+    same &= ((d >> b) & 1u) ? m : ~m;
+  }
+  const uint32_t before = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+  __syncthreads();
+  if (v && before == 0u) wcnt[w][d] = (uint32_t)__popcll(same);  // the digit's first lane in the wave
+  uint32_t ex = inc - td;
+  for (int k = 0; k < w; ++k) ex += wsum[k];
+  dbase[t] = ex;
+  __syncthreads();
+  if (!v) return;
+  uint32_t dst = dbase[d] + base + before;
+  for (int k = 0; k < w; ++k) dst += wcnt[k][d];
+  if (dst < (uint32_t)n) out[dst] = idx;  // always true: the counts of a pass sum to n
+}
+
+// src == nullptr: no pass ran (one slot), the order stays
+__global__ __launch_bounds__(kBlock) void k_rg_finish(const int32_t* __restrict__ src, int n,
+                                                       const int32_t* __restrict__ perm,
+                                                       const int32_t* __restrict__ pos_slot,
+                                                       int32_t* __restrict__ src_out, int32_t* __restrict__ perm_out,
+                                                       int32_t* __restrict__ pos_slot_out,
+                                                       int32_t* __restrict__ env_pos_out) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= n) return;
+  const int s = src ? src[j] : j;
+  if ((uint32_t)s >= (uint32_t)n) return;  // never: src is a permutation of [0, n)
+  const int e = perm[s];
+  src_out[j] = s;
+  perm_out[j] = e;
+  pos_slot_out[j] = pos_slot[s];
+  if ((uint32_t)e < (uint32_t)n) env_pos_out[e] = j;
+}
+
+// the move of a live handle: row j of the shadow copy takes working row src[j] ...
+__global__ __launch_bounds__(kBlock) void k_regroup_gather(const int32_t* __restrict__ src, int n, rx_state work,
+                                                            rx_state tmp) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= n) return;
+  const int s = src[j];
+  if ((uint32_t)s < (uint32_t)n) move_row<1>(work, s, tmp, j);
+}
+
+// ... and shadow -> working copy with the new perm and pos_slot (coalesced; every buffer keeps its address)
+__global__ __launch_bounds__(kBlock) void k_regroup_copy(int n, const int32_t* __restrict__ perm_tmp,
+                                                          int32_t* __restrict__ perm,
+                                                          const int32_t* __restrict__ slot_tmp,
+                                                          int32_t* __restrict__ pos_slot, rx_state tmp, rx_state work) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= n) return;
+  perm[j] = perm_tmp[j];
+  pos_slot[j] = slot_tmp[j];
+  move_row<1>(tmp, j, work, j);
+}
+
+static_assert(kBlock == kRgDigits, "k_rg_count: one thread per digit");
+
+}  // namespace
+
+// passes of the radix sort: the bytes of n_tracks - 1 (none for one slot)
+static int rg_passes(int n_tracks) {
+  int p = 0;
+  for (uint32_t m = (uint32_t)(n_tracks - 1); m; m >>= 8) ++p;
+  return p;
+}
+
+// scratch: two index buffers [n], the digit-major count table [256][tiles] and the digit totals [256]
+extern "C" size_t rx_regroup_scratch_size(int n) {
+  const size_t nblk = ((size_t)std::max(n, 0) + kBlock - 1) / kBlock;
+  return (2 * (size_t)std::max(n, 0) + kRgDigits * nblk + kRgDigits) * sizeof(uint32_t) + 16;
+}
+
+extern "C" int rx_launch_regroup_plan(int n, int n_tracks, const int32_t* perm, const int32_t* pos_slot,
+                                      int32_t* src_out, int32_t* perm_out, int32_t* pos_slot_out, int32_t* env_pos_out,
+                                      void* scratch, hipStream_t s) {
+  if (n <= 0) return 0;
+  const int nblk = (n + kBlock - 1) / kBlock;
+  int32_t* idx[2] = {reinterpret_cast<int32_t*>(scratch), reinterpret_cast<int32_t*>(scratch) + n};
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(scratch) + 2 * (size_t)n;
+  uint32_t* tot = cnt + (size_t)kRgDigits * nblk;
+  const int passes = rg_passes(n_tracks);
+  const int32_t* in = nullptr;
+  for (int p = 0; p < passes; ++p) {
+    int32_t* out = idx[p & 1];
+    hipLaunchKernelGGL(k_rg_count, dim3(nblk), dim3(kBlock), 0, s, in, pos_slot, n, 8 * p, nblk, cnt);
+    hipLaunchKernelGGL(k_rg_scan, dim3(kRgDigits), dim3(kBlock), 0, s, cnt, nblk, tot);
+    hipLaunchKernelGGL(k_rg_scatter, dim3(nblk), dim3(kBlock), 0, s, in, pos_slot, n, 8 * p, nblk, cnt, tot, out);
+    in = out;
+  }
+  hipLaunchKernelGGL(k_rg_finish, dim3(nblk), dim3(kBlock), 0, s, in, n, perm, pos_slot, src_out, perm_out, pos_slot_out,
+                     env_pos_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rx_launch_regroup_move(int n, const int32_t* src, const int32_t* perm_tmp, int32_t* perm,
+                                      const int32_t* slot_tmp, int32_t* pos_slot, const rx_state* work,
+                                      const rx_state* tmp, hipStream_t s) {
+  if (n <= 0) return 0;
+  const int grid = (n + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_regroup_gather, dim3(grid), dim3(kBlock), 0, s, src, n, *work, *tmp);
+  hipLaunchKernelGGL(k_regroup_copy, dim3(grid), dim3(kBlock), 0, s, n, perm_tmp, perm, slot_tmp, pos_slot, *tmp, *work);
   return (int)hipGetLastError();
 }

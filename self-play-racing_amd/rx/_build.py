@@ -21,10 +21,10 @@ SOURCES = ["rx_kernels.hip", "rx_sort.hip", "rx_optim.hip", "rx_ppo.hip", "rx_tr
            "rx_league.hip", "rx_cull.hip", "rx_curriculum.hip", "rx_track_replay.hip", "rx_track_evolve.hip",
            "rx_api.cpp", "rx_api_loops.cpp", "rx_api_train.cpp", "rx_api_tracks.cpp", "rx_api_curriculum.cpp",
            "rx_raster_host.cpp", "rx_league_host.cpp", "rx_curriculum_host.cpp", "rx_track_replay_host.cpp",
-           "rx_track_evolve_host.cpp", "rx_assign_plan_host.cpp"]
+           "rx_track_evolve_host.cpp", "rx_assign_plan_host.cpp", "rx_regroup_plan_host.cpp"]
 # compiled as plain C++, not as HIP: shared headers take their host form (rx_math.h's rx_sincos on the host)
 HOST_ONLY = {"rx_raster_host.cpp", "rx_league_host.cpp", "rx_curriculum_host.cpp", "rx_track_replay_host.cpp",
-             "rx_track_evolve_host.cpp", "rx_assign_plan_host.cpp"}
+             "rx_track_evolve_host.cpp", "rx_assign_plan_host.cpp", "rx_regroup_plan_host.cpp"}
 HEADERS = ["rx_internal.h", "rx_math.h", "rx_sincos_table.h", "rx_policy.h", "rx_policy_mfma.h", "rx_spline.h",
            "rx_raster.h", "rx_league.h", "rx_cull.h", "rx_curriculum.h", "rx_track_duel.h", "rx_track_replay.h", "rx_track_evolve.h",
            "rx_assign_plan.h", "rx_handle.h"]

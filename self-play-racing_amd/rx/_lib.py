@@ -50,7 +50,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_track_learn_episode_host", "rx_track_learn_episode_step", "rx_track_learn_episodic_rollout_steps",
            "rx_track_tally2", "rx_track_tally2_host", "rx_track_duel_scores", "rx_track_duel_scores_host",
            "rx_track_duel_rollout_steps",
-           "rx_steps_plan", "rx_patch_tracks", "rx_patch_tracks_host", "rx_replace_tracks_device", "rx_assign_plan")
+           "rx_steps_plan", "rx_patch_tracks", "rx_patch_tracks_host", "rx_replace_tracks_device", "rx_assign_plan",
+           "rx_regroup_plan_host", "rx_regroup_scratch_bytes", "rx_regroup_plan", "rx_regroup_slots", "rx_lane_layout")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -427,6 +428,12 @@ def load(build_if_missing=True):
                                   ctypes.POINTER(RxCullTables), ctypes.POINTER(RxTrackPatch), _P]
     L.rx_patch_tracks_host.argtypes = L.rx_patch_tracks.argtypes
     L.rx_replace_tracks_device.argtypes = [_P, ctypes.POINTER(RxTrackPatch), _P]
+    L.rx_regroup_plan_host.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_P] * 6
+    L.rx_regroup_scratch_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
+    L.rx_regroup_scratch_bytes.restype = ctypes.c_int64
+    L.rx_regroup_plan.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_P] * 7 + [ctypes.c_int64, _P]
+    L.rx_regroup_slots.argtypes = [_P, _P]
+    L.rx_lane_layout.argtypes = [_P, _P, _P, _P]
     L.rx_eval_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxEvalIO), ctypes.c_int32, _P]
     L.rx_policy_act_bank.argtypes = [ctypes.POINTER(RxPolicyBankIO), _P]
     L.rx_match_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxMatchIO), ctypes.c_int32, _P]
@@ -487,7 +494,7 @@ def load(build_if_missing=True):
     for name in EXPORTS:
         if name not in ("rx_last_error", "rx_abi_version", "rx_ppo_workspace_floats", "rx_ppo_workspace_doubles",
                         "rx_ppo_update_workspace_floats", "rx_adam_workspace_floats",
-                        "rx_ppo_adv_workspace_doubles"):
+                        "rx_ppo_adv_workspace_doubles", "rx_regroup_scratch_bytes"):
             getattr(L, name).restype = ctypes.c_int
     if L.rx_abi_version() != ABI_VERSION:
         raise RxError(f"librx ABI {L.rx_abi_version()} != {ABI_VERSION} (rebuild: python -m rx._build)")

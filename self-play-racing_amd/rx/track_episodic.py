@@ -67,6 +67,10 @@ class EpisodicCurriculumPPO(CurriculumPPO):
     pool's.
     ``config["episodic_slots"]`` = True records the [T, N] slots of each rollout
     (``slots()``).
+    ``config["episodic_regroup_every"]`` = K (default 0 = never): before the rollout of
+    every update u > 0 with u % K == 0 the envs' positions are put back in slot order
+    (``RacingVectorEnv.regroup_slots``, outside the captured rollout graph, which stays);
+    scheduling only, every result is the same bit for bit.
 
     Refused (ValueError): what CurriculumPPO refuses, and envs whose schedule does
     not come out lane-varying or whose autoreset is not next-step."""
@@ -76,6 +80,9 @@ class EpisodicCurriculumPPO(CurriculumPPO):
         if self.scores_every < 1:
             raise ValueError(f"episodic_scores_every={self.scores_every} must be >= 1")
         self.partial = bool(config.get("episodic_partial", False))
+        self.regroup_every = int(config.get("episodic_regroup_every", 0))
+        if self.regroup_every < 0:
+            raise ValueError(f"episodic_regroup_every={self.regroup_every} must be >= 0 (0 = never)")
         self._updates = 0
         self._carry = None  # the last rollout's (next_obs, next_done)
         super().__init__(env_fn, config, device)
@@ -100,6 +107,8 @@ class EpisodicCurriculumPPO(CurriculumPPO):
     def collect_rollout(self, obs, actions, logprobs, dones, rewards, values, next_obs, next_done):
         if self._updates % self.scores_every == 0:
             self.curriculum.scores()  # outside any captured graph: the draws read the table it leaves
+        if self.regroup_every and self._updates and self._updates % self.regroup_every == 0:
+            self.envs.regroup_slots()  # the draws of the rollouts so far scattered the slots over the waves
         self._updates += 1
         out = super().collect_rollout(obs, actions, logprobs, dones, rewards, values, next_obs, next_done)
         self._carry = (out[6], out[7])

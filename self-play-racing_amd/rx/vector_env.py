@@ -152,6 +152,7 @@ class RacingVectorEnv:
             half_cone = np.pi / 3 if A == 1 else np.pi / 2
         self._table = None  # set_tracks: the device-resident table the envs run on
         self.track_generation = 0  # track swaps so far (set_tracks)
+        self.regroups = 0  # regroup_slots calls so far
         if track_set is not None:
             self.tracks = track_set
         elif track_backend == "scipy":
@@ -324,6 +325,29 @@ class RacingVectorEnv:
         obs = self.reset_device()
         self._episode_start[:] = time.perf_counter()
         return obs
+
+    def regroup_slots(self, stream=None):
+        """Put the positions of a lane-varying env back in slot order on the device
+        (rx_regroup_slots): a stable sort of the positions by the slot they hold now, the
+        working-state rows moved with them.  Episodic draws (rx.track_episodic) send
+        envs to unrelated slots and leave them where they sit, so a wave's 64 lanes
+        come to read 64 slots' tables; this restores the layout rx_assign starts from.
+        No env is reset and every env-order output (obs, reward, done, info, state) is
+        unchanged bit for bit.  Launches only, on ``stream`` (default the current one):
+        no host wait, may be captured; to be called between steps / rollouts.  RxError on
+        an env that is not single-agent on the lane-varying schedule.  Counted in
+        ``regroups``."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self.L.rx_regroup_slots(self._h, s.cuda_stream), "rx_regroup_slots")
+        self.regroups += 1
+
+    def lane_layout(self):
+        """(perm, pos_slot, env_pos) of a lane-varying env, host int32 [N] each: the env id
+        and the slot at every position, and the position of every env (rx_lane_layout;
+        synchronises the device)."""
+        out = [np.empty(self.num_envs, np.int32) for _ in range(3)]
+        _lib.check(self.L.rx_lane_layout(self._h, *(o.ctypes.data for o in out)), "rx_lane_layout")
+        return tuple(out)
 
     def replace_tracks(self, slots, control_points, widths):
         """New tracks in some slots of the live env's pool, in place, without the

@@ -7,6 +7,7 @@
     python tools/curriculum_train.py --episodic --envs 4096 --steps 128 --updates 60 --tracks 512
     python tools/curriculum_train.py --episodic --replay value_l1 --envs 4096 --steps 128 --updates 60 --tracks 512
     python tools/curriculum_train.py --episodic --partial --evolve --envs 4096 --steps 128 --updates 60 --tracks 512
+    python tools/curriculum_train.py --episodic --regroup-every 1 --envs 4096 --steps 128 --updates 60 --tracks 512
 
 ``CurriculumPPO`` on a pool of ``--tracks`` distinct tracks (env i starts on slot
 i % tracks): every finished episode is tallied against its slot on the device;
@@ -37,7 +38,9 @@ resample that retires slots resets only the envs on them.  ``--episodic --partia
 filled on the device, by fresh tracks and by edited children of high-ranked tracks
 of the slot's own point count.  ``--episodic --evolve`` without ``--partial`` is
 refused: only the partial path keeps a slot's point count, and the global path
-of ``--evolve`` rebuilds the table the episodic draws run on.  Every curriculum run also reports the
+of ``--evolve`` rebuilds the table the episodic draws run on.  ``--episodic
+--regroup-every K`` (``episodic_regroup_every``) puts the envs' positions back in slot
+order on the device before the rollout of every K-th update (scheduling only).  Every curriculum run also reports the
 episodes tallied per update, the slots that reached ``--min-episodes`` and, per
 update, the share of the envs on the fullest slot (with replay scores also on the
 slot ranked first).
@@ -92,6 +95,7 @@ def run(kind, args, evaluator):
         if replay:
             from rx.track_replay_episodic import EpisodicReplayCurriculumPPO as cls
         cfg["episodic_partial"] = bool(args.partial)
+        cfg["episodic_regroup_every"] = args.regroup_every
         if evolve:  # (only with --partial: main() refuses the rest)
             from rx.track_evolve_episodic import EpisodicEvolvingCurriculumPPO as cls
     t = cls(lambda i: RacingEnv(num_sensors=11, track_pool=pool, track_id=i % n, track_width=widths[i % n]), cfg,
@@ -160,6 +164,9 @@ def main():
     ap.add_argument("--partial", action="store_true",
                     help="with --episodic: retired slots are replaced in place and only their envs reset "
                          "(episodic_partial), no global reset")
+    ap.add_argument("--regroup-every", type=int, default=0,
+                    help="with --episodic: put the envs' positions back in slot order on the device before the "
+                         "rollout of every K-th update (episodic_regroup_every; 0 = never; scheduling only)")
     ap.add_argument("--prec", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--show", type=int, default=20, help="slots of the table to print, the most failed first")
@@ -170,6 +177,8 @@ def main():
         sys.exit("--episodic moves envs between the slots of a fixed table, and --evolve on the global path gives a "
                  "retired slot a new point count and rebuilds that table: pass --partial as well, which evolves the "
                  "retired slots in place at their own point count (DESIGN.md §4)")
+    if args.regroup_every and not args.episodic:
+        sys.exit("--regroup-every regroups the lane-varying envs of the episodic trainers: pass --episodic as well")
     if args.partial and not args.episodic:
         sys.exit("--partial replaces retired slots under the episodic trainers: pass --episodic as well")
     if not torch.cuda.is_available():
