@@ -125,8 +125,9 @@ typedef struct {
      lane_tracks on, the single-agent kernels take waves of 64 consecutive envs of ANY slots and every lane
      reads its own slot's tables with vector loads (culling decisions per lane).  0 auto: on when grouping
      by slot would fill the dynamics waves less than half on average (more than 2 x ceil(N / 64) waves);
-     1 on; -1 off.  Single-agent envs on the split step at one lane per env and per ray only (wide kernels,
-     two-car envs: off).  Scheduling only: bit-identical results. */
+     1 on; -1 off.  Single-agent envs on the split step at one lane per env and per ray only (wide kernels:
+     off; two-car envs: this field has no effect on them, their switch is rx_set_lane_cars, off unless
+     called).  Scheduling only: bit-identical results. */
   int32_t lane_tracks;
   int32_t reserved0;       /* ABI v23: must be 0 (was kin_sort, a dropped A/B schedule) */
 } rx_config;
@@ -253,6 +254,24 @@ typedef struct {
 } rx_assign_plan_io;
 int rx_assign_plan(const rx_config* cfg, int32_t n_tracks, const int32_t* wp_off, const int32_t* track_of_env,
                    rx_assign_plan_io* io);
+
+/* Lane-varying track slots for two-car envs (additive to ABI v25; DESIGN.md §3 "Lane-varying two-car
+ * envs").  rx_config.lane_tracks governs single-agent handles only; a two-car handle takes the same
+ * schedule -- dynamics waves of 64 consecutive positions of ANY slots, every lane reading its own
+ * slot's tables, one lane per env, per ray and per REWARD env, no ray-task sort, no spatial re-sort,
+ * bit-identical results -- from this option, in rx_config.lane_tracks' encoding: -1 off (a fresh
+ * handle), 0 auto (on when grouping by slot needs more than 2 x ceil(N / 64) dynamics waves), 1 on.
+ * The call only records the choice: the next rx_assign resolves it, and every later one again, so
+ * under 0 a new assignment may switch the schedule on or off.  RX_EINVAL for a null handle, a mode
+ * outside -1 .. 1, and a single-agent handle (rx_config.lane_tracks governs it).  On such a handle
+ * rx_schedule's lane-varying word is 1; its ray-wave table is block-major without padding records
+ * (per 64-position block ceil(count * 2 * n_sensors / 64) waves, task_start relative to the block). */
+int rx_set_lane_cars(rx_env* h, int32_t mode);
+
+/* rx_assign_plan with that option: the plan of a two-car handle on which rx_set_lane_cars(h,
+ * lane_cars) was called (rx_assign_plan is this with -1).  n_agents = 1: RX_EINVAL. */
+int rx_assign_plan_cars(const rx_config* cfg, int32_t lane_cars, int32_t n_tracks, const int32_t* wp_off,
+                        const int32_t* track_of_env, rx_assign_plan_io* io);
 
 /* Bind the caller-owned device state (pointers are kept until re-bound).
  * Once both rx_bind_state and rx_assign have run, the engine copies the bound

@@ -197,7 +197,7 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
   const int N = h->cfg.n_envs, A = h->cfg.n_agents, R = h->cfg.n_sensors;
   rx_assignment plan;
   std::string err;
-  int rc = rx_plan_assignment(h->cfg, h->n_tracks, h->wp_off_h.data(), track_of_env, &plan, &err);
+  int rc = rx_plan_assignment(h->cfg, h->n_tracks, h->wp_off_h.data(), track_of_env, &plan, &err, h->lane_cars);
   if (rc) return fail(rc, "%s", err.c_str());
   const rx_sched& sc = plan.sched;
   RX_HIP(hipSetDevice(h->cfg.device));
@@ -270,16 +270,25 @@ int rx_assign(rx_env* h, const int32_t* track_of_env) {
   return RX_OK;
 }
 
-int rx_assign_plan(const rx_config* cfg, int32_t n_tracks, const int32_t* wp_off, const int32_t* track_of_env,
-                   rx_assign_plan_io* io) {
-  if (!cfg || !wp_off || !track_of_env || !io) return fail(RX_EINVAL, "rx_assign_plan: null argument");
-  if (n_tracks <= 0) return fail(RX_EINVAL, "rx_assign_plan: n_tracks must be > 0 (got %d)", n_tracks);
+int rx_set_lane_cars(rx_env* h, int32_t mode) {
+  if (!h) return fail(RX_EINVAL, "rx_set_lane_cars: null handle");
+  if (mode < -1 || mode > 1) return fail(RX_EINVAL, "rx_set_lane_cars: lane_cars must be 0 (auto), 1 or -1 (got %d)", mode);
+  if (h->cfg.n_agents != 2)
+    return fail(RX_EINVAL, "rx_set_lane_cars: a single-agent handle: rx_config.lane_tracks governs its schedule");
+  h->lane_cars = mode;  // resolved by the next rx_assign
+  return RX_OK;
+}
+
+// rx_assign_plan / rx_assign_plan_cars (fn names the entry in the texts)
+static int assign_plan(const char* fn, const rx_config* cfg, int32_t lane_cars, int32_t n_tracks, const int32_t* wp_off,
+                       const int32_t* track_of_env, rx_assign_plan_io* io) {
+  if (n_tracks <= 0) return fail(RX_EINVAL, "%s: n_tracks must be > 0 (got %d)", fn, n_tracks);
   for (int k = 0; k < n_tracks; ++k)
     if (wp_off[k + 1] - wp_off[k] < 2)
       return fail(RX_EINVAL, "track %d has %d waypoints (need >= 2)", k, wp_off[k + 1] - wp_off[k]);
   rx_assignment plan;
   std::string err;
-  const int rc = rx_plan_assignment(*cfg, n_tracks, wp_off, track_of_env, &plan, &err);
+  const int rc = rx_plan_assignment(*cfg, n_tracks, wp_off, track_of_env, &plan, &err, lane_cars);
   if (rc) return fail(rc, "%s", err.c_str());
   const rx_sched& sc = plan.sched;
   const bool room = io->schedule && io->perm && io->dyn_waves && io->ray_waves && io->dyn_cap >= sc.n_dyn_waves &&
@@ -299,6 +308,21 @@ int rx_assign_plan(const rx_config* cfg, int32_t n_tracks, const int32_t* wp_off
   if (io->env_pos) std::copy(plan.env_pos.begin(), plan.env_pos.end(), io->env_pos);
   if (io->sort_base) std::copy(plan.sort_base.begin(), plan.sort_base.end(), io->sort_base);
   return RX_OK;
+}
+
+int rx_assign_plan(const rx_config* cfg, int32_t n_tracks, const int32_t* wp_off, const int32_t* track_of_env,
+                   rx_assign_plan_io* io) {
+  if (!cfg || !wp_off || !track_of_env || !io) return fail(RX_EINVAL, "rx_assign_plan: null argument");
+  return assign_plan("rx_assign_plan", cfg, -1, n_tracks, wp_off, track_of_env, io);
+}
+
+int rx_assign_plan_cars(const rx_config* cfg, int32_t lane_cars, int32_t n_tracks, const int32_t* wp_off,
+                        const int32_t* track_of_env, rx_assign_plan_io* io) {
+  if (!cfg || !wp_off || !track_of_env || !io) return fail(RX_EINVAL, "rx_assign_plan_cars: null argument");
+  if (cfg->n_agents == 1)
+    return fail(RX_EINVAL, "rx_assign_plan_cars: n_agents = 1: rx_config.lane_tracks governs a single-agent schedule "
+                           "(rx_assign_plan)");
+  return assign_plan("rx_assign_plan_cars", cfg, lane_cars, n_tracks, wp_off, track_of_env, io);
 }
 
 // working copy <-> the caller's arrays (env order); blocking = finish before

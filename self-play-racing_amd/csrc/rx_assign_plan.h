@@ -104,7 +104,8 @@ struct rx_sched {
   int32_t ray_tail = 0, ray_tail_lpr = 2;  // tail classes cast at ray_tail_lpr lanes per ray (0 = none)
   int32_t ray_tail_from = -1;              // first ray wave of the tail (-1 = none)
   int32_t task_sort = 1;                   // ray-task direction sort every task_sort dynamics launches
-  int32_t lane_tracks = 0;                 // lane-varying slots (rx_config.lane_tracks, the plan's choice)
+  int32_t lane_tracks = 0;                 // lane-varying slots (rx_config.lane_tracks; two-car handles:
+                                           // rx_set_lane_cars -- the plan's choice either way)
   bool sort_on = false;                    // spatial re-sort: sort_bins bins of 1 << sort_shift waypoints
   int32_t sort_bins = 0, sort_shift = 0;   // (both 0 without it)
   int32_t n_dyn_waves = 0, n_ray_waves = 0;
@@ -126,9 +127,11 @@ int rx_config_check(const rx_config* cfg, std::string* err);
 
 // The assignment of track_of_env [n_envs] over n_tracks slots of wp_off[k + 1] - wp_off[k]
 // waypoints.  RX_OK, or a refusal (config range, slot id, ray_order 2 sensor count) with
-// the message in *err and *out as it was.
+// the message in *err and *out as it was.  lane_cars: a two-car handle's lane-varying option
+// (rx_set_lane_cars: -1 off, 0 auto, 1 on; rx_config.lane_tracks never reaches two-car envs), which
+// single-agent configs ignore; outside -1 .. 1 it is refused.
 int rx_plan_assignment(const rx_config& cfg, int32_t n_tracks, const int32_t* wp_off, const int32_t* track_of_env,
-                       rx_assignment* out, std::string* err);
+                       rx_assignment* out, std::string* err, int32_t lane_cars = -1);
 
 // rx_regroup_plan_host's body (rx_regroup_plan_host.cpp): the positions of a lane-varying env
 // regrouped by slot, a stable sort by (pos_slot[p], p).  RX_OK, or RX_EINVAL with the message in

@@ -27,7 +27,7 @@ int fail(std::string* err, int code, const char* fmt, ...) {
 // The launch schedule (rx_config ABI v17 fields; 0 = the measured default for N) of N envs of A
 // cars over slots of slot_n envs and at least min_w waypoints.  ray_tail is the request: the
 // placement clips it to the classes there are.
-rx_sched resolve_schedule(const rx_config& c, int min_w, const std::vector<int32_t>& slot_n) {
+rx_sched resolve_schedule(const rx_config& c, int min_w, const std::vector<int32_t>& slot_n, int32_t lane_cars) {
   const int N = c.n_envs, A = c.n_agents;
   rx_sched s;
   s.dyn_lpe = (A == 1 && N <= RX_DYN1_SMALL_N) ? RX_DYN1_LPE_SMALL : 1;
@@ -65,12 +65,15 @@ rx_sched resolve_schedule(const rx_config& c, int min_w, const std::vector<int32
   // ANY slots (per-lane track loads) when the grouping would need more than twice ceil(N / 64)
   // waves.  Single-agent envs at one lane per env (the split step or the one-kernel k_dyn1<1>);
   // it implies one lane per ray and per REWARD env and no ray-task sort or spatial re-sort.
+  // Two-car envs (k_kin2 / k_dyn2 at a lane per env) take the same schedule by the same rule, but
+  // from the handle's option (rx_set_lane_cars), not from rx_config.lane_tracks: off unless asked.
   {
     long long grouped = 0;
     for (const int32_t n : slot_n) grouped += (n + 63) / 64;
     const long long full = (N + 63) / 64;
-    const bool can = A == 1 && s.dyn_lpe == 1;
-    s.lane_tracks = can && c.lane_tracks >= 0 && (c.lane_tracks == 1 || grouped > 2 * full) ? 1 : 0;
+    const bool can = s.dyn_lpe == 1;  // (two-car envs: always)
+    const int32_t mode = A == 2 ? lane_cars : c.lane_tracks;
+    s.lane_tracks = can && mode >= 0 && (mode == 1 || grouped > 2 * full) ? 1 : 0;
   }
   if (s.lane_tracks) {
     s.ray_lpr = 1;
@@ -298,9 +301,11 @@ int rx_config_check(const rx_config* cfg, std::string* err) {
 }
 
 int rx_plan_assignment(const rx_config& c, int32_t n_tracks, const int32_t* wp_off, const int32_t* track_of_env,
-                       rx_assignment* out, std::string* err) {
+                       rx_assignment* out, std::string* err, int32_t lane_cars) {
   int rc = rx_config_check(&c, err);
   if (rc != RX_OK) return rc;
+  if (lane_cars < -1 || lane_cars > 1)
+    return fail(err, RX_EINVAL, "lane_cars must be 0 (auto), 1 or -1 (got %d)", lane_cars);
   const int N = c.n_envs, A = c.n_agents, R = c.n_sensors;
   for (int e = 0; e < N; ++e)
     if (track_of_env[e] < 0 || track_of_env[e] >= n_tracks)
@@ -318,9 +323,13 @@ int rx_plan_assignment(const rx_config& c, int32_t n_tracks, const int32_t* wp_o
   int min_w = 1 << 30;
   for (int k = 0; k < n_tracks; ++k) min_w = std::min(min_w, wp_off[k + 1] - wp_off[k]);
   rx_sched& s = a.sched;
-  s = resolve_schedule(c, min_w, a.slot_n);
+  s = resolve_schedule(c, min_w, a.slot_n, lane_cars);
   wave_tables t = s.lane_tracks ? lane_varying_waves(N, A, R) : grouped_waves(c, s, track_of_env, a.perm);
-  if (c.ray_order >= 1 || s.lane_tracks) {
+  // Two-car lane-varying tables stay as built, block-major with no padding records: a block's
+  // 2 R rays per env fill up to 2 R waves, so padding the block count to 8 would add up to
+  // 14 R empty workgroups, and with a slot per lane the waves of a block share no table lines
+  // for one XCD's L2 to keep.
+  if (s.lane_tracks ? A == 1 : c.ray_order >= 1) {
     int maxw = 0;
     for (size_t g = 0; g < t.group_end.size(); ++g)
       maxw = std::max(maxw, t.group_end[g] - (g ? t.group_end[g - 1] : 0));

@@ -98,6 +98,7 @@ struct rx_env {
   int64_t* draw_cursor = nullptr;
   DevBuf<int32_t> draw_rank, draw_tmp;
   DevBuf<int64_t> draw_base;
+  int32_t lane_cars = -1;  // rx_set_lane_cars (two-car handles): -1 off, 0 auto, 1 on; rx_assign resolves it
   rx_sched sched;  // the schedule the assignment resolved (rx_assign_plan.h): written whole, after the last upload
   DevBuf<int32_t> pos_slot;                // with lane_tracks: [N] slot of the env at each position
   DevBuf<int32_t> env_pos;                 // with lane_tracks: [N] position of each env, the inverse of perm

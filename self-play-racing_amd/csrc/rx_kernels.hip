@@ -1048,23 +1048,32 @@ __device__ __forceinline__ bool rect_intersect(const double ax[4], const double 
 // car `sub`'s closest-waypoint pass (the REWARD chain's two sequential passes
 // become one), the pair exchanges progress / crash flag, and lane 0 of the pair
 // does the rest; sub_block picks which 32 of the dynamics wave's 64 envs.
-template <int PART, int RLPE = 1>
+// LV (lane-varying slots, rx_set_lane_cars): the wave's 64 positions may hold 64 slots, so every
+// per-slot scalar comes per lane from the slot's header and every culling decision around the
+// argmins is the lane's own, as in dyn1_env; the arithmetic and its order are the same.
+template <int PART, int RLPE = 1, bool LV = false>
 __device__ __forceinline__ void dyn2_env(const rx_kargs& a, int wave, double* ang_out, int& e_out, double ep_out[3],
                                          int sub_block = 0) {
   constexpr bool FULL = PART == RX_PART_FULL, KIN = PART == RX_PART_KIN, REW = PART == RX_PART_REWARD;
   static_assert(RLPE == 1 || (RLPE == 2 && REW), "two lanes per env: the REWARD part only");
+  static_assert(!LV || RLPE == 1, "lane-varying slots: one lane per env");
   if (wave >= a.n_dyn_waves) return;
   const rx_wave we = a.dyn_waves[wave];
   const int lane = (int)(threadIdx.x & 63) / RLPE + sub_block * (64 / RLPE);
   const int sub = (int)threadIdx.x & (RLPE - 1);
-  const int k = uniform(we.track);
-  const int wp0 = uniform(a.tr.wp_off[k]);
-  const int W = uniform(a.tr.wp_off[k + 1]) - wp0;
+  // LV: the lane's own slot (lanes past the wave's envs read slot 0's header and leave below)
+  const int k = LV ? (lane < we.count ? a.pos_slot[we.perm_start + lane] : 0) : uniform(we.track);
+  const rx_slot_hdr* __restrict__ hd = a.tr.hdr + k;  // LV: every per-slot scalar from one line
+  const int wp0 = LV ? hd->wp0 : uniform(a.tr.wp_off[k]);
+  const int W = LV ? hd->W : uniform(a.tr.wp_off[k + 1]) - wp0;
   const double2* __restrict__ wp = reinterpret_cast<const double2*>(a.tr.wp) + wp0;
   const double2* __restrict__ nrm = reinterpret_cast<const double2*>(a.tr.nrm) + wp0;
-  const double* __restrict__ meta = a.tr.meta + 8 * k;
-  const double width = uniform_d(meta[3]);
-  const double maxd = uniform_d(meta[4]);
+  const double* __restrict__ meta = LV ? hd->meta : a.tr.meta + 8 * k;
+  const double width = LV ? meta[3] : uniform_d(meta[3]);
+  const double maxd = LV ? meta[4] : uniform_d(meta[4]);
+  // the slot's closest-waypoint cull tables (read only where a culled argmin runs)
+  auto wcb = [&] { return a.tr.wchunk_box + 4 * (size_t)(LV ? hd->wchunk_off : uniform(a.tr.wchunk_off[k])); };
+  auto wsb = [&] { return a.tr.wsuper_box + 4 * (size_t)(LV ? hd->wsuper_off : uniform(a.tr.wsuper_off[k])); };
   if (lane >= we.count) return;
   const int p = we.perm_start + lane;  // working-state position (see dyn1_env)
   const int e = a.perm[p];             // env id: io rows, the start-slot draw
@@ -1168,7 +1177,7 @@ __device__ __forceinline__ void dyn2_env(const rx_kargs& a, int wave, double* an
       // collision; only this car's corners are live during its pass
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        if (!__any(mv[q])) continue;
+        if (!vote<LV>(mv[q])) continue;
         const double2 sc = reinterpret_cast<const double2*>(a.cs_scratch)[2 * p + q];
         double px[5], py[5];
         px[0] = c[q].x;
@@ -1178,9 +1187,8 @@ __device__ __forceinline__ void dyn2_env(const rx_kargs& a, int wave, double* an
         if (a.cull_chunk > 0) {
           const int prev[1] = {prev_waypoint(c[q].progress, W)};
           const double ccx[1] = {c[q].x}, ccy[1] = {c[q].y};
-          argmin_culled<5, 1>(wp, a.tr.wchunk_box + 4 * (size_t)uniform(a.tr.wchunk_off[k]),
-                              a.tr.wsuper_box + 4 * (size_t)uniform(a.tr.wsuper_off[k]), W, px, py, prev, ccx, ccy,
-                              a.argmin_window, idx, a.io.counters, nullptr, mv[q]);
+          argmin_culled<5, 1, LV>(wp, wcb(), wsb(), W, px, py, prev, ccx, ccy, a.argmin_window, idx, a.io.counters,
+                                  nullptr, mv[q]);
         } else {
           argmin_pts<5>(wp, W, px, py, idx);
         }
@@ -1222,12 +1230,11 @@ __device__ __forceinline__ void dyn2_env(const rx_kargs& a, int wave, double* an
         // left out of its pass (its result is not used).
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-          if (!__any(mv[q])) continue;
+          if (!vote<LV>(mv[q])) continue;
           const int prev[1] = {prev_waypoint(c[q].progress, W)};
           const double ccx[1] = {c[q].x}, ccy[1] = {c[q].y};
-          argmin_culled<5, 1>(wp, a.tr.wchunk_box + 4 * (size_t)uniform(a.tr.wchunk_off[k]),
-                              a.tr.wsuper_box + 4 * (size_t)uniform(a.tr.wsuper_off[k]), W, px + 5 * q, py + 5 * q,
-                              prev, ccx, ccy, a.argmin_window, idx + 5 * q, a.io.counters, nullptr, mv[q]);
+          argmin_culled<5, 1, LV>(wp, wcb(), wsb(), W, px + 5 * q, py + 5 * q, prev, ccx, ccy, a.argmin_window,
+                                  idx + 5 * q, a.io.counters, nullptr, mv[q]);
         }
       } else {
         argmin_pts<10>(wp, W, px, py, idx);
@@ -1460,7 +1467,8 @@ __device__ __forceinline__ void dyn2_env(const rx_kargs& a, int wave, double* an
 
 // k_dyn2 (PART = FULL) and k_kin2 (PART = KIN, one wave per workgroup so that
 // block b's wave lands on the XCD of block b's REWARD and raycast waves).
-template <int PART>
+// LV (lane-varying slots): no ray-task sort, launched with no sort LDS.
+template <int PART, bool LV = false>
 __global__ __launch_bounds__(256) void k_dyn2(rx_kargs a) {
   const int wave = uniform(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
   if (wave >= a.n_dyn_waves) return;
@@ -1469,12 +1477,12 @@ __global__ __launch_bounds__(256) void k_dyn2(rx_kargs a) {
   const int wl = NW == 1 ? 0 : (int)(threadIdx.x >> 6);
   int32_t* cnt = task_lds + wl * (kTaskSectors + 64 * 32);
   int32_t* stage = cnt + kTaskSectors;
-  const bool sorting = a.tasks_out != nullptr;
+  const bool sorting = !LV && a.tasks_out != nullptr;
   if (sorting) cnt[threadIdx.x & 63] = 0;
   const unsigned long long prof_t0 = prof_start(a);
   double ang[2], ep[3] = {0.0, 0.0, 0.0};
   int e = -1;
-  dyn2_env<PART>(a, wave, ang, e, ep);
+  dyn2_env<PART, 1, LV>(a, wave, ang, e, ep);
   if (PART == RX_PART_FULL) add_episode_stats(a, ep);
   if (sorting) sort_block_tasks<2>(a, uniform(a.dyn_waves[wave].perm_start), e, ang, cnt, stage);
   prof_end(a, wave, prof_t0);
@@ -2233,6 +2241,12 @@ __global__ __launch_bounds__(256) void k_rays_wide(rx_kargs a) {
 #ifndef RX_STEP2_MINW_2
 #define RX_STEP2_MINW_2 6  // two-car k_step2<2>: 80 VGPRs (fewer REWARD spills; 8 -> 6 waves: +9 % at 8,192 envs, +1 % at 65,536)
 #endif
+#ifndef RX_STEP2_MINW_2LV
+// lane-varying two-car envs (k_step2<2, 1, 1, true>): 5 waves per SIMD (96 VGPRs, 21 spilled; 6: 80 VGPRs, 65
+// spilled) -- 8,192 envs on 8,192 slots, ms per step 0.0840 / 0.0921 / 0.0965 at 5 / 6 / 7 waves, same session
+// (tools/bench_lane_cars.py --minw, profiles/lane_cars/minw.json)
+#define RX_STEP2_MINW_2LV 5
+#endif
 // One instantiation per (REWARD lanes per env, lanes per ray) schedule: with
 // the three schedules of each half inlined into ONE kernel, its register
 // allocation was the maximum over all of them, and the REWARD half spilled at
@@ -2261,7 +2275,7 @@ __device__ __forceinline__ void step2_body(const rx_kargs& a, int n_rw) {
       const int n1 = n_rw / 2, w = b % n1, sb = b / n1;  // as the single-agent REWARD half at 2 lanes
       dyn2_env<RX_PART_REWARD, 2>(a, w, ang, e, ep, sb);
     } else {
-      dyn2_env<RX_PART_REWARD>(a, b, ang, e, ep);
+      dyn2_env<RX_PART_REWARD, 1, LV>(a, b, ang, e, ep);
     }
     add_episode_stats(a, ep);
   } else {
@@ -2271,7 +2285,8 @@ __device__ __forceinline__ void step2_body(const rx_kargs& a, int n_rw) {
 }
 
 template <int A, int RLPE, int LPR, bool LV = false>
-__global__ __launch_bounds__(64, A == 1 ? (LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW) : RX_STEP2_MINW_2) void k_step2(
+__global__ __launch_bounds__(64, A == 1 ? (LV ? RX_STEP2_MINW_LV : RX_STEP2_MINW)
+                                        : (LV ? RX_STEP2_MINW_2LV : RX_STEP2_MINW_2)) void k_step2(
     rx_kargs a, int n_rw) {
   step2_body<A, RLPE, LPR, LV>(a, n_rw);
 }
@@ -2814,6 +2829,14 @@ static void launch_step2_lpr(const rx_kargs* a, dim3 grid, int n_rw, hipStream_t
 extern "C" int rx_launch_split(const rx_kargs* a, int n_agents, int part, hipStream_t s) {
   if (n_agents == 2) {  // k_kin2, then k_step2<2> (REWARD waves padded to 8, as below)
     const int n_rw2 = a->reward_lpe * ((a->n_dyn_waves + 7) / 8 * 8);
+    if (a->lane_tracks) {  // lane-varying slots (rx_set_lane_cars: one lane per env and per ray, no task sort)
+      if (part == RX_SPLIT_KIN)
+        hipLaunchKernelGGL((k_dyn2<RX_PART_KIN, true>), dim3(a->n_dyn_waves), dim3(64), 0, s, *a);
+      else
+        hipLaunchKernelGGL((k_step2<2, 1, 1, true>), dim3(n_rw2 + (part == RX_SPLIT_REWARD ? 0 : a->n_ray_waves)),
+                           dim3(64), 0, s, *a, n_rw2);
+      return (int)hipGetLastError();
+    }
     if (part == RX_SPLIT_KIN) {
       hipLaunchKernelGGL((k_dyn2<RX_PART_KIN>), dim3(a->n_dyn_waves), dim3(64), task_sort_lds_bytes(a, 2, 1), s, *a);
     } else {
@@ -2954,6 +2977,8 @@ extern "C" int rx_launch_step(const rx_kargs* a, int n_agents, int phases, hipSt
       hipLaunchKernelGGL((k_dyn1<2, RX_PART_FULL>), grd, blk, lds, s, *a);
     else if (n_agents == 1)
       hipLaunchKernelGGL((k_dyn1<1, RX_PART_FULL>), grd, blk, lds, s, *a);
+    else if (a->lane_tracks)
+      hipLaunchKernelGGL((k_dyn2<RX_PART_FULL, true>), grd, blk, 0, s, *a);
     else
       hipLaunchKernelGGL((k_dyn2<RX_PART_FULL>), grd, blk, lds, s, *a);
   }
@@ -2970,6 +2995,8 @@ extern "C" int rx_launch_step(const rx_kargs* a, int n_agents, int phases, hipSt
       hipLaunchKernelGGL((k_rays<1, true>), dim3(a->n_ray_waves), dim3(64), 0, s, *a);
     else if (n_agents == 1)
       hipLaunchKernelGGL(k_rays<1>, dim3(a->n_ray_waves), dim3(64), 0, s, *a);
+    else if (a->lane_tracks)
+      hipLaunchKernelGGL((k_rays<2, true>), dim3(a->n_ray_waves), dim3(64), 0, s, *a);
     else
       hipLaunchKernelGGL(k_rays<2>, dim3(a->n_ray_waves), dim3(64), 0, s, *a);
   }

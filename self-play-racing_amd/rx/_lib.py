@@ -51,7 +51,8 @@ EXPORTS = ("rx_last_error", "rx_abi_version", "rx_create", "rx_destroy", "rx_sen
            "rx_track_tally2", "rx_track_tally2_host", "rx_track_duel_scores", "rx_track_duel_scores_host",
            "rx_track_duel_rollout_steps",
            "rx_steps_plan", "rx_patch_tracks", "rx_patch_tracks_host", "rx_replace_tracks_device", "rx_assign_plan",
-           "rx_regroup_plan_host", "rx_regroup_scratch_bytes", "rx_regroup_plan", "rx_regroup_slots", "rx_lane_layout")
+           "rx_regroup_plan_host", "rx_regroup_scratch_bytes", "rx_regroup_plan", "rx_regroup_slots", "rx_lane_layout",
+           "rx_set_lane_cars", "rx_assign_plan_cars")
 RX_KERNEL_NAMES = ("k_dyn", "k_rays", "k_kin1", "k_step2", "k_step2_reward")
 ADAM_MAX_TENSORS = 32
 RX_PHASE_DYNAMICS, RX_PHASE_RAYS = 1, 2
@@ -157,17 +158,25 @@ class RxAssignPlanIO(ctypes.Structure):
                                               "sort_shift")] + [(k, _P) for k in ASSIGN_PLAN_PTRS]
 
 
-def assign_plan(cfg, wp_off, track_of_env):
+def assign_plan(cfg, wp_off, track_of_env, lane_cars=None):
     """rx_assign_plan for an RxConfig, wp_off int32 [n_tracks + 1] and track_of_env int32 [n_envs]: a dict of
     schedule (by SCHEDULE_KEYS), perm, sort_bins, sort_shift, dyn_waves / ray_waves int32 [n][4], slot_n, and
     pos_slot / env_pos (lane-varying schedules, else None) and sort_base (with sort_bins > 0, else None).
+    lane_cars (-1, 0, 1): rx_assign_plan_cars, the plan of a two-car handle with that rx_set_lane_cars mode.
     A refusal raises RxError with the library's text."""
     L = load()
     wp_off = np.ascontiguousarray(wp_off, np.int32)
     toe = np.ascontiguousarray(track_of_env, np.int32)
     n_tracks, N = len(wp_off) - 1, cfg.n_envs
     io = RxAssignPlanIO()
-    check(L.rx_assign_plan(ctypes.byref(cfg), n_tracks, ptr(wp_off), ptr(toe), ctypes.byref(io)), "rx_assign_plan")
+
+    def plan():
+        args = (n_tracks, ptr(wp_off), ptr(toe), ctypes.byref(io))
+        if lane_cars is None:
+            check(L.rx_assign_plan(ctypes.byref(cfg), *args), "rx_assign_plan")
+        else:
+            check(L.rx_assign_plan_cars(ctypes.byref(cfg), int(lane_cars), *args), "rx_assign_plan_cars")
+    plan()
     out = dict(schedule=np.zeros(SCHEDULE_W, np.int32), perm=np.zeros(N, np.int32),
                dyn_waves=np.zeros((io.n_dyn_waves, 4), np.int32), ray_waves=np.zeros((io.n_ray_waves, 4), np.int32),
                slot_n=np.zeros(n_tracks, np.int32), pos_slot=np.zeros(N, np.int32), env_pos=np.zeros(N, np.int32),
@@ -175,7 +184,7 @@ def assign_plan(cfg, wp_off, track_of_env):
     io.dyn_cap, io.ray_cap = io.n_dyn_waves, io.n_ray_waves
     for k in ASSIGN_PLAN_PTRS:
         setattr(io, k, out[k].ctypes.data)
-    check(L.rx_assign_plan(ctypes.byref(cfg), n_tracks, ptr(wp_off), ptr(toe), ctypes.byref(io)), "rx_assign_plan")
+    plan()
     out["schedule"] = {k: int(v) for k, v in zip(SCHEDULE_KEYS, out["schedule"])}
     out["sort_bins"], out["sort_shift"] = io.sort_bins, io.sort_shift
     if not out["schedule"]["lane_tracks"]:
@@ -434,6 +443,9 @@ def load(build_if_missing=True):
     L.rx_regroup_plan.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_P] * 7 + [ctypes.c_int64, _P]
     L.rx_regroup_slots.argtypes = [_P, _P]
     L.rx_lane_layout.argtypes = [_P, _P, _P, _P]
+    L.rx_set_lane_cars.argtypes = [_P, ctypes.c_int32]
+    L.rx_assign_plan_cars.argtypes = [ctypes.POINTER(RxConfig), ctypes.c_int32, ctypes.c_int32, _P, _P,
+                                      ctypes.POINTER(RxAssignPlanIO)]
     L.rx_eval_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxEvalIO), ctypes.c_int32, _P]
     L.rx_policy_act_bank.argtypes = [ctypes.POINTER(RxPolicyBankIO), _P]
     L.rx_match_steps.argtypes = [_P, ctypes.POINTER(RxIO), ctypes.POINTER(RxMatchIO), ctypes.c_int32, _P]

@@ -115,8 +115,9 @@ class SelfPlayPPO(PPO):
         c = self.config
         lo, n = rdist.shard(c["num_envs"])
         fn = env_fn if lo == 0 else (lambda i: env_fn(lo + i))
+        # config["lane_cars"] (-1 / 0 / 1): the two-car lane-varying schedule (RacingVectorEnv); absent = off
         venv = build_vector_env(fn, n, c["seed"] + rdist.rank(), self.device,
-                                track_backend=c.get("track_backend", "scipy"))
+                                track_backend=c.get("track_backend", "scipy"), lane_cars=c.get("lane_cars"))
         if c.get("start_draws", "hash") == "numpy":  # the reference's np.random start-slot stream
             if rdist.world() > 1:
                 # every rank would replay the SAME np.random stream for its own env shard, not

@@ -124,11 +124,14 @@ class RacingVectorEnv:
     ``track_backend``: who builds the track table when no ``track_set`` is
     passed -- "scipy" (the reference's splines, one slot at a time), "native"
     or "device" (rx.track.TrackSet.build: every distinct slot in one librx call,
-    on the host or on this env's device)."""
+    on the host or on this env's device).  ``lane_cars`` (two-car envs only):
+    the lane-varying schedule's switch for them, rx_set_lane_cars -- -1 off, 0
+    auto, 1 on; None makes no call (off).  The mode lives in the handle, so
+    ``set_tracks`` and ``reassign_tracks`` resolve it again (``venv.lane_cars``)."""
 
     def __init__(self, control_points, widths, n_agents=1, n_sensors=11, device=None, autoreset="next_step",
                  seed=0, speed_weight=8.0, max_steps=3000, half_cone=None, track_set=None, cull_chunk=8,
-                 sort_interval=None, ray_order=None, cull_super=8, sched=None, track_backend="scipy"):
+                 sort_interval=None, ray_order=None, cull_super=8, sched=None, track_backend="scipy", lane_cars=None):
         self.L = _lib.load()
         self.device = torch.device(device) if device is not None else _default_device()
         if self.device.type != "cuda":
@@ -138,6 +141,10 @@ class RacingVectorEnv:
             raise ValueError("need one width per env")
         self.num_envs = N
         self.n_agents = A = int(n_agents)
+        if lane_cars is not None and (A != 2 or lane_cars not in (-1, 0, 1)):
+            raise ValueError("lane_cars is -1, 0 or 1 and for two-car envs only (single-agent envs: "
+                             "sched=dict(lane_tracks=...))")
+        self.lane_cars = -1 if lane_cars is None else int(lane_cars)  # the handle's rx_set_lane_cars mode
         self.n_sensors = R = int(n_sensors)
         if sort_interval is None:
             sort_interval = default_sort_interval(N, A)
@@ -210,6 +217,8 @@ class RacingVectorEnv:
             h = _lib._P()
             _lib.check(self.L.rx_create(cfg, h), "rx_create")
             self._h = h
+            if lane_cars is not None:  # recorded in the handle: every later rx_assign resolves it again
+                _lib.check(self.L.rx_set_lane_cars(self._h, self.lane_cars), "rx_set_lane_cars")
             self._upload_tracks()
             self._st["speed_weight"] = None  # per-env weights: set_speed_weights()
             st = self._state_struct()
@@ -523,7 +532,8 @@ class RacingVectorEnv:
         """What rx_assign builds for this env's config and track table (rx_assign_plan: host only, the
         handle is not touched; _lib.assign_plan's dict), for ``track_of_env`` or the current slots."""
         toe = self.track_of_env if track_of_env is None else track_of_env
-        return _lib.assign_plan(self._cfg, self.tracks.arrays()["wp_off"], toe)
+        return _lib.assign_plan(self._cfg, self.tracks.arrays()["wp_off"], toe,
+                                lane_cars=self.lane_cars if self.n_agents == 2 else None)
 
     def enable_counters(self, on=True):
         """Per-wave culling counters (rx_io.counters): chunk tests / scans."""
