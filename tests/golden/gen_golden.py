@@ -34,6 +34,9 @@ Sets:
                       tracks -- answered by Track.raycast, RacingEnv.step and
                       MultiRacingEnv.step on a Track subclass of this script that
                       overrides gen_waypoints alone; the geometry it derived.
+  placed.npz      (set ``placed``) the pinned rows of tests/placed_cases.py's KATs --
+                      the golden spline tracks 0 and 16 moved and scaled -- answered
+                      the same way.  Needs geometry.npz.
   reference_line_counts.json (set ``line_counts``) lines per .py file of the
                       reference, for tests/test_citations_cpu.py.
 
@@ -824,6 +827,79 @@ def gen_eval_metrics(track, racing_env):
     _save("eval_metrics.npz", **res)
 
 
+def _kat_single_outputs(envs, sk):
+    """RacingEnv.step on every row of single-agent KAT columns sk (envs: by slot): the o_* columns."""
+    cols = {k: [] for k in ("o_x", "o_y", "o_angle", "o_vx", "o_vy", "o_progress", "o_crashed", "o_finished",
+                            "o_steps", "o_last_progress", "o_last_steering", "o_cp", "o_obs", "o_reward",
+                            "o_terminated", "o_truncated", "o_info_speed", "o_info_progress", "o_progress_delta")}
+    for i in range(len(sk["x"])):
+        env = envs[int(sk["track"][i])]
+        s = {k: float(sk[k][i]) for k in ("x", "y", "angle", "vx", "vy", "progress", "last_progress", "last_steering")}
+        s.update(crashed=bool(sk["crashed"][i]), finished=bool(sk["finished"][i]), steps=int(sk["steps"][i]),
+                 cp=tuple(bool(b) for b in sk["cp"][i]))
+        env.speed_weight = float(sk["speed_weight"][i])
+        _inject_single(env, s)
+        obs, rew, term, trunc, info = env.step(sk["action"][i])
+        c = env.car
+        for key, v in (("o_x", float(c.x)), ("o_y", float(c.y)), ("o_angle", float(c.angle)), ("o_vx", float(c.vx)),
+                       ("o_vy", float(c.vy)), ("o_progress", float(c.progress)), ("o_crashed", bool(c.crashed)),
+                       ("o_finished", bool(c.finished)), ("o_steps", env.steps),
+                       ("o_last_progress", float(env.last_progress)), ("o_last_steering", float(env.last_steering)),
+                       ("o_cp", (env.checkpoints[0.25], env.checkpoints[0.50], env.checkpoints[0.75])), ("o_obs", obs),
+                       ("o_reward", float(rew)), ("o_terminated", bool(term)), ("o_truncated", bool(trunc)),
+                       ("o_info_speed", float(info["speed"])), ("o_info_progress", float(info["progress"])),
+                       ("o_progress_delta", float(info["progress_delta"]))):
+            cols[key].append(v)
+    cols = {k: np.array(v) for k, v in cols.items()}
+    cols["o_cp"] = cols["o_cp"].astype(np.uint8)
+    return cols
+
+
+def _kat_multi_outputs(envs, mk):
+    """MultiRacingEnv.step on every row of two-car KAT columns mk (envs: by slot): the o_* columns."""
+    keys = ("o_x", "o_y", "o_angle", "o_vx", "o_vy", "o_progress", "o_crashed", "o_finished", "o_has_crashed",
+            "o_finished_step", "o_last_progress", "o_last_steering", "o_cp", "o_steps", "o_obs", "o_reward",
+            "o_done", "o_done_all", "o_truncated", "o_placement", "o_info_speed", "o_info_progress")
+    cols = {k: [] for k in keys}
+    for i in range(len(mk["steps"])):
+        env = envs[int(mk["track"][i])]
+        env.reset(seed=0)
+        for q, c in enumerate(env.cars):
+            c.x, c.y, c.angle = float(mk["x"][i, q]), float(mk["y"][i, q]), float(mk["angle"][i, q])
+            c.vx, c.vy, c.progress = float(mk["vx"][i, q]), float(mk["vy"][i, q]), float(mk["progress"][i, q])
+            c.crashed, c.finished = bool(mk["crashed"][i, q]), bool(mk["finished"][i, q])
+            d = env.agents_data[q]
+            d["last_progress"], d["last_steering"] = float(mk["last_progress"][i, q]), float(mk["last_steering"][i, q])
+            cp = mk["cp"][i, q]
+            d["checkpoints"] = {0.25: bool(cp[0]), 0.50: bool(cp[1]), 0.75: bool(cp[2])}
+            d["has_crashed"] = bool(mk["has_crashed"][i, q])
+            fs = int(mk["finished_step"][i, q])
+            d["finished_step"] = None if fs < 0 else fs
+        env.steps = int(mk["steps"][i])
+        obs, rew, dones, trunc, infos = env.step({f"{q}": mk["action"][i, q] for q in range(2)})
+        cs, ad = env.cars, env.agents_data
+        cols["o_x"].append([float(c.x) for c in cs]); cols["o_y"].append([float(c.y) for c in cs])
+        cols["o_angle"].append([float(c.angle) for c in cs]); cols["o_vx"].append([float(c.vx) for c in cs])
+        cols["o_vy"].append([float(c.vy) for c in cs]); cols["o_progress"].append([float(c.progress) for c in cs])
+        cols["o_crashed"].append([bool(c.crashed) for c in cs]); cols["o_finished"].append([bool(c.finished) for c in cs])
+        cols["o_has_crashed"].append([bool(d["has_crashed"]) for d in ad])
+        cols["o_finished_step"].append([(-1 if d["finished_step"] is None else d["finished_step"]) for d in ad])
+        cols["o_last_progress"].append([float(d["last_progress"]) for d in ad])
+        cols["o_last_steering"].append([float(d["last_steering"]) for d in ad])
+        cols["o_cp"].append([(d["checkpoints"][0.25], d["checkpoints"][0.50], d["checkpoints"][0.75]) for d in ad])
+        cols["o_steps"].append(env.steps)
+        cols["o_obs"].append(np.stack([obs["0"], obs["1"]]))
+        cols["o_reward"].append([float(rew["0"]), float(rew["1"])])
+        cols["o_done"].append(bool(dones["0"])); cols["o_done_all"].append(bool(dones["__all__"]))
+        cols["o_truncated"].append(bool(trunc))
+        cols["o_placement"].append([int(infos[f"{q}"].get("placement", 0)) for q in range(2)])
+        cols["o_info_speed"].append([float(infos[f"{q}"]["speed"]) for q in range(2)])
+        cols["o_info_progress"].append([float(infos[f"{q}"]["progress"]) for q in range(2)])
+    cols = {k: np.array(v) for k, v in cols.items()}
+    cols["o_cp"] = cols["o_cp"].astype(np.uint8)
+    return cols
+
+
 def gen_lattice(track, racing_env, multi_racing_env):
     """lattice.npz: tests/lattice_cases.py's KATs through the reference's own Track.raycast,
     RacingEnv.step and MultiRacingEnv.step.  The tracks are Track / MultiTrack subclasses whose
@@ -868,9 +944,6 @@ def gen_lattice(track, racing_env, multi_racing_env):
     out["ray_t"] = np.array(t)
     # --- single-agent steps
     sk = lat.single_kats()
-    cols = {k: [] for k in ("o_x", "o_y", "o_angle", "o_vx", "o_vy", "o_progress", "o_crashed", "o_finished",
-                            "o_steps", "o_last_progress", "o_last_steering", "o_cp", "o_obs", "o_reward",
-                            "o_terminated", "o_truncated", "o_info_speed", "o_info_progress", "o_progress_delta")}
     envs = {}
     orig = racing_env.Track
     racing_env.Track = LatticeTrack
@@ -880,37 +953,15 @@ def gen_lattice(track, racing_env, multi_racing_env):
             envs[k].reset(seed=0)
     finally:
         racing_env.Track = orig
-    for i in range(len(sk["x"])):
-        env = envs[int(sk["track"][i])]
-        s = {k: float(sk[k][i]) for k in ("x", "y", "angle", "vx", "vy", "progress", "last_progress", "last_steering")}
-        s.update(crashed=bool(sk["crashed"][i]), finished=bool(sk["finished"][i]), steps=int(sk["steps"][i]),
-                 cp=tuple(bool(b) for b in sk["cp"][i]))
-        env.speed_weight = float(sk["speed_weight"][i])
-        _inject_single(env, s)
-        obs, rew, term, trunc, info = env.step(sk["action"][i])
-        c = env.car
-        for key, v in (("o_x", float(c.x)), ("o_y", float(c.y)), ("o_angle", float(c.angle)), ("o_vx", float(c.vx)),
-                       ("o_vy", float(c.vy)), ("o_progress", float(c.progress)), ("o_crashed", bool(c.crashed)),
-                       ("o_finished", bool(c.finished)), ("o_steps", env.steps),
-                       ("o_last_progress", float(env.last_progress)), ("o_last_steering", float(env.last_steering)),
-                       ("o_cp", (env.checkpoints[0.25], env.checkpoints[0.50], env.checkpoints[0.75])), ("o_obs", obs),
-                       ("o_reward", float(rew)), ("o_terminated", bool(term)), ("o_truncated", bool(trunc)),
-                       ("o_info_speed", float(info["speed"])), ("o_info_progress", float(info["progress"])),
-                       ("o_progress_delta", float(info["progress_delta"]))):
-            cols[key].append(v)
+    cols = _kat_single_outputs(envs, sk)
     for k in lat.SINGLE_COLS:
         out["single_" + k] = sk[k]
     for k, v in cols.items():
-        out["single_" + k] = np.array(v)
-    out["single_o_cp"] = out["single_o_cp"].astype(np.uint8)
+        out["single_" + k] = v
     print("lattice single: crashes", int(out["single_o_crashed"].sum()), "term", int(out["single_o_terminated"].sum()),
           "trunc", int(out["single_o_truncated"].sum()), "of", len(sk["x"]))
     # --- two-car steps
     mk = lat.multi_kats()
-    keys = ("o_x", "o_y", "o_angle", "o_vx", "o_vy", "o_progress", "o_crashed", "o_finished", "o_has_crashed",
-            "o_finished_step", "o_last_progress", "o_last_steering", "o_cp", "o_steps", "o_obs", "o_reward",
-            "o_done", "o_done_all", "o_truncated", "o_placement", "o_info_speed", "o_info_progress")
-    cols = {k: [] for k in keys}
     orig = multi_racing_env.MultiTrack
     multi_racing_env.MultiTrack = LatticeMultiTrack
     try:
@@ -918,50 +969,91 @@ def gen_lattice(track, racing_env, multi_racing_env):
                                                    track_width=[w]) for k, (_, wp, w) in slot.items()}
     finally:
         multi_racing_env.MultiTrack = orig
-    for i in range(len(mk["steps"])):
-        env = envs[int(mk["track"][i])]
-        env.reset(seed=0)
-        for q, c in enumerate(env.cars):
-            c.x, c.y, c.angle = float(mk["x"][i, q]), float(mk["y"][i, q]), float(mk["angle"][i, q])
-            c.vx, c.vy, c.progress = float(mk["vx"][i, q]), float(mk["vy"][i, q]), float(mk["progress"][i, q])
-            c.crashed, c.finished = bool(mk["crashed"][i, q]), bool(mk["finished"][i, q])
-            d = env.agents_data[q]
-            d["last_progress"], d["last_steering"] = float(mk["last_progress"][i, q]), float(mk["last_steering"][i, q])
-            cp = mk["cp"][i, q]
-            d["checkpoints"] = {0.25: bool(cp[0]), 0.50: bool(cp[1]), 0.75: bool(cp[2])}
-            d["has_crashed"] = bool(mk["has_crashed"][i, q])
-            fs = int(mk["finished_step"][i, q])
-            d["finished_step"] = None if fs < 0 else fs
-        env.steps = int(mk["steps"][i])
-        obs, rew, dones, trunc, infos = env.step({f"{q}": mk["action"][i, q] for q in range(2)})
-        cs, ad = env.cars, env.agents_data
-        cols["o_x"].append([float(c.x) for c in cs]); cols["o_y"].append([float(c.y) for c in cs])
-        cols["o_angle"].append([float(c.angle) for c in cs]); cols["o_vx"].append([float(c.vx) for c in cs])
-        cols["o_vy"].append([float(c.vy) for c in cs]); cols["o_progress"].append([float(c.progress) for c in cs])
-        cols["o_crashed"].append([bool(c.crashed) for c in cs]); cols["o_finished"].append([bool(c.finished) for c in cs])
-        cols["o_has_crashed"].append([bool(d["has_crashed"]) for d in ad])
-        cols["o_finished_step"].append([(-1 if d["finished_step"] is None else d["finished_step"]) for d in ad])
-        cols["o_last_progress"].append([float(d["last_progress"]) for d in ad])
-        cols["o_last_steering"].append([float(d["last_steering"]) for d in ad])
-        cols["o_cp"].append([(d["checkpoints"][0.25], d["checkpoints"][0.50], d["checkpoints"][0.75]) for d in ad])
-        cols["o_steps"].append(env.steps)
-        cols["o_obs"].append(np.stack([obs["0"], obs["1"]]))
-        cols["o_reward"].append([float(rew["0"]), float(rew["1"])])
-        cols["o_done"].append(bool(dones["0"])); cols["o_done_all"].append(bool(dones["__all__"]))
-        cols["o_truncated"].append(bool(trunc))
-        cols["o_placement"].append([int(infos[f"{q}"].get("placement", 0)) for q in range(2)])
-        cols["o_info_speed"].append([float(infos[f"{q}"]["speed"]) for q in range(2)])
-        cols["o_info_progress"].append([float(infos[f"{q}"]["progress"]) for q in range(2)])
+    cols = _kat_multi_outputs(envs, mk)
     for k in lat.MULTI_COLS:
         out["multi_" + k] = mk[k]
     for k, v in cols.items():
-        out["multi_" + k] = np.array(v)
-    out["multi_o_cp"] = out["multi_o_cp"].astype(np.uint8)
+        out["multi_" + k] = v
     out["multi_kind"] = mk["kind"]
     out["single_parked"] = sk["parked"]
     print("lattice multi: contacts/crash/done:", int((out["multi_o_reward"] < -4).sum()),
           int(out["multi_o_crashed"].sum()), int(out["multi_o_done_all"].sum()))
     _save("lattice.npz", **out)
+
+
+def gen_placed(track, racing_env, multi_racing_env):
+    """placed.npz: the pinned rows of tests/placed_cases.py's KATs (placed_cases.pinned: a thinned
+    share of every slot's rows) through Track.raycast, RacingEnv.step and MultiRacingEnv.step, on
+    Track / MultiTrack subclasses whose gen_waypoints returns the slot's waypoints, as gen_lattice.
+    Keys: ray_* (+ ray_idx: the rows' indices in placed_cases.ray_kats), single_*, multi_*; the
+    `track` columns are placed_cases' slots."""
+    root = os.path.dirname(os.path.dirname(HERE))
+    for p in (root, os.path.join(root, "self-play-racing_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import environment.multi_track as multi_track
+    from tests import placed_cases as pc
+    from tests.golden_util import Golden
+
+    class PlacedTrack(track.Track):
+        def gen_waypoints(self, factor=30):
+            return np.asarray(self.control_points, dtype=np.float64)
+
+    class PlacedMultiTrack(multi_track.MultiTrack):
+        def gen_waypoints(self, factor=30):
+            return np.asarray(self.control_points, dtype=np.float64)
+
+    golden = Golden()
+    recs = pc.slot_records(golden)
+    out = {}
+    # --- geometry: what the reference derives from a slot's waypoints is the slot
+    T = {k: PlacedTrack(control_points=r["wp"], track_width=r["width"]) for k, r in enumerate(recs)}
+    for k, r in enumerate(recs):
+        g = _track_record(T[k])
+        for key in ("wp", "nrm", "starts", "v2"):
+            assert g[key].tobytes() == np.ascontiguousarray(r[key]).tobytes(), (k, key)
+    # --- rays
+    idx, rk = pc.pinned(golden, "ray")
+    out["ray_idx"] = idx
+    for k, v in rk.items():
+        out["ray_" + k] = v
+    out["ray_t"] = np.array([float(T[int(k)].raycast(np.array([float(ox), float(oy)]), float(d), 50.0))
+                             for k, ox, oy, d in zip(rk["track"], rk["ox"], rk["oy"], rk["dir"])])
+    # --- single-agent steps
+    idx, sk = pc.pinned(golden, "single")
+    envs = {}
+    orig = racing_env.Track
+    racing_env.Track = PlacedTrack
+    try:
+        for k, r in enumerate(recs):
+            envs[k] = racing_env.RacingEnv(num_sensors=11, track_pool=[r["wp"]], track_id=0, track_width=r["width"])
+            envs[k].reset(seed=0)
+    finally:
+        racing_env.Track = orig
+    out["single_idx"] = idx
+    for k in pc.SINGLE_COLS:
+        out["single_" + k] = sk[k]
+    for k, v in _kat_single_outputs(envs, sk).items():
+        out["single_" + k] = v
+    print("placed single: crashes", int(out["single_o_crashed"].sum()), "term", int(out["single_o_terminated"].sum()),
+          "trunc", int(out["single_o_truncated"].sum()), "of", len(sk["x"]))
+    # --- two-car steps
+    idx, mk = pc.pinned(golden, "multi")
+    orig = multi_racing_env.MultiTrack
+    multi_racing_env.MultiTrack = PlacedMultiTrack
+    try:
+        envs = {k: multi_racing_env.MultiRacingEnv(num_agents=2, num_sensors=11, track_pool=[recs[k]["wp"]], track_id=0,
+                                                   track_width=[recs[k]["width"]]) for k in pc.MULTI_SLOTS}
+    finally:
+        multi_racing_env.MultiTrack = orig
+    out["multi_idx"] = idx
+    for k in pc.MULTI_COLS + ("kind",):
+        out["multi_" + k] = mk[k]
+    for k, v in _kat_multi_outputs(envs, mk).items():
+        out["multi_" + k] = v
+    print("placed multi: contacts/crash/done:", int((out["multi_o_reward"] < -4).sum()),
+          int(out["multi_o_crashed"].sum()), int(out["multi_o_done_all"].sum()))
+    _save("placed.npz", **out)
 
 
 def gen_line_counts():
@@ -990,7 +1082,7 @@ def gen_line_counts():
 def main(argv):
     want = set(argv[1:]) or {"geometry", "raycast", "step_single", "traj_single", "step_multi", "gae", "agent",
                              "ppo_update", "ppo_update_mb32k", "schedules", "eval_metrics", "line_counts",
-                             "lattice"}
+                             "lattice", "placed"}
     if "line_counts" in want:
         gen_line_counts()
         want.discard("line_counts")
@@ -1019,6 +1111,8 @@ def main(argv):
         gen_step_multi(track, multi_racing_env, recs)
     if "lattice" in want:
         gen_lattice(track, racing_env, multi_racing_env)
+    if "placed" in want:
+        gen_placed(track, racing_env, multi_racing_env)
     if "gae" in want:
         gen_gae()
     if "agent" in want:
