@@ -353,6 +353,14 @@ class MultiEvaluator:
         self.device = self.venv.device
         self.fused = FusedEval(self.venv) if backend == "fused" else None
 
+    def run_actions(self, actions, max_steps=None):
+        """Open-loop evaluation of ``actions`` [T, N, 2, 2] (fused backend): the summary dict.
+        ``max_steps`` (default: the evaluator's) ends the loop as metrics.py:92 does: an
+        episode still running then has no placement."""
+        if self.fused is None:
+            raise ValueError("run_actions needs backend='fused'")
+        return _record_summary(self.fused.run_actions(actions, self.max_steps if max_steps is None else max_steps))
+
     @torch.no_grad()
     def run(self, agent, record_actions=False, prec="fp32"):
         """backend "fused", ``record_actions``: also returns the [T, N, 2, 2] actions taken."""

@@ -29,6 +29,16 @@ Sets:
                       evaluate.py pool (seed 42, widths by run), driven by a
                       scripted agent; the actions it issued are recorded so
                       the device evaluator can replay them open loop.
+  traj_multi.npz  (set ``traj_multi``) whole two-car episodes of MultiRacingEnv from its own
+                      reset (both start orders) to dones['__all__'], two scripted
+                      controllers: finishes by either car, a crash of both, a car frozen
+                      while the other drives on, a truncation, runs of contact steps;
+                      the same rows through environment/wrappers.py's SelfPlayWrapper
+                      for agent_idx 0 and 1 (asserted equal, indices stored).
+  eval_multi.npz  (set ``eval_multi``) utils/metrics.py:80-150 eval_multi_agent on the
+                      eval_metrics pool, a scripted agent driving both cars; returned
+                      dictionaries, actions issued, start orders (= the seed's shuffle
+                      stream), and one call with max_steps=40 (placement None).
   lattice.npz     (set ``lattice``) the KATs of tests/lattice_cases.py -- rays,
                       single-agent and two-car steps on integer-waypoint
                       tracks -- answered by Track.raycast, RacingEnv.step and
@@ -318,17 +328,23 @@ def gen_step_single(track, racing_env, recs_tracks, per_track=700):
     _save("step_single.npz", **out)
 
 
-def _controller(env, rng, gain, speed_cap, noise):
-    """Pure-pursuit driver so golden trajectories reach checkpoints and finishes."""
-    c, T = env.car, env.track
+def _controller(env, rng, gain, speed_cap, noise, car=None, offset=0.0, coast=0.0):
+    """Pure-pursuit driver so golden trajectories reach checkpoints and finishes.
+    ``car``: the index of the car it drives in a two-car env (None: env.car);
+    ``offset``: its target lies that far from the centre line along the normal;
+    ``coast``: the throttle action above ``speed_cap`` (MultiRacingEnv.step maps the action
+    to (a + 1) / 2, multi_racing_env.py:217, so only -1 lets a two-car env's car slow down)."""
+    c, T = (env.car if car is None else env.cars[car]), env.track
     W = len(T.waypoints)
     i = T.closest_waypoint_idx(c.x, c.y)
     tgt = T.waypoints[(i + 8) % W]
+    if offset:
+        tgt = tgt + T.normals[(i + 8) % W] * offset
     desired = np.arctan2(tgt[1] - c.y, tgt[0] - c.x)
     err = (desired - c.angle + np.pi) % (2 * np.pi) - np.pi
     steer = np.clip(gain * err + rng.normal(0, noise), -1.2, 1.2)
     spd = np.hypot(c.vx, c.vy)
-    thr = 1.0 if spd < speed_cap else 0.0
+    thr = 1.0 if spd < speed_cap else coast
     if rng.random() < 0.05:
         thr = rng.uniform(-0.2, 1.2)
     return np.array([steer, thr], dtype=np.float32)
@@ -455,6 +471,309 @@ def gen_step_multi(track, multi_racing_env, recs_tracks, per_track=500):
     print("step_multi: contacts/crash/finish/done:", int((out["o_reward"] < -4).sum()), int(out["o_crashed"].sum()),
           int(out["o_finished"].sum()), int(out["o_done_all"].sum()))
     _save("step_multi.npz", **out)
+
+
+def _repo_on_path():
+    root = os.path.dirname(os.path.dirname(HERE))
+    for p in (root, os.path.join(root, "self-play-racing_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+
+
+def _multi_env(multi_racing_env, recs_tracks, ti):
+    if ti == DEFAULT_TRACK:
+        return multi_racing_env.MultiRacingEnv(num_agents=2, num_sensors=11)
+    rec = recs_tracks[ti]
+    return multi_racing_env.MultiRacingEnv(num_agents=2, num_sensors=11, track_pool=[rec["cp"]], track_id=0,
+                                           track_width=[rec["width"]])
+
+
+def _forced_reset(reset, first):
+    """``reset()`` with np.random.shuffle replaced by the order [first, 1 - first] (as
+    gen_step_multi): the global RNG is not touched."""
+    seq = iter([[first, 1 - first]])
+    orig = np.random.shuffle
+    np.random.shuffle = lambda lst, _s=seq: lst.__setitem__(slice(None), next(_s))
+    try:
+        return reset()
+    finally:
+        np.random.shuffle = orig
+
+
+_MULTI_STEP_COLS = ("actions", "obs", "reward", "done", "done_all", "truncated", "placement", "info_speed",
+                    "info_progress", "x", "y", "angle", "vx", "vy", "progress", "crashed", "finished", "has_crashed",
+                    "finished_step", "last_progress", "last_steering", "cp", "steps", "contact", "car_rays")
+
+
+def _car_rays(env):
+    """How many of the 22 sensor rays end on the other car: raycast_with_cars shorter than
+    the wall distance (Track.raycast, capped at the sensor range as raycast_with_cars caps
+    its car distance, so an uncapped wall hit beyond 50 does not count).  Read-only calls."""
+    n = 0
+    rel = np.linspace(-np.pi / 2, np.pi / 2, env.num_sensors)
+    for car in env.cars:
+        origin = np.array([car.x, car.y])
+        for r in rel:
+            d = car.angle + r
+            wall = min(env.track.raycast(origin, d, env.max_sensor_range), env.max_sensor_range)
+            n += bool(env.track.raycast_with_cars(origin, d, env.cars, env.max_sensor_range) < wall)
+    return n
+
+
+def _multi_episode(env, first, plans, cols, limit=3100, measure=True):
+    """One two-car episode from the reference's own reset (start order forced) to
+    dones['__all__'], each car driven by its own _controller with its own default_rng.
+    plans: per car (gain, speed_cap, noise, offset, seed).  Appends the per-step columns
+    to ``cols``; returns (reset obs [2, D], reset x, y, angle [2], number of steps)."""
+    obs, _ = _forced_reset(lambda: env.reset(seed=0), first)
+    reset = (np.stack([obs["0"], obs["1"]]), [float(c.x) for c in env.cars], [float(c.y) for c in env.cars],
+             [float(c.angle) for c in env.cars])
+    rngs = [np.random.default_rng(p[4]) for p in plans]
+    n = 0
+    for _ in range(limit):
+        acts = {f"{q}": _controller(env, rngs[q], plans[q][0], plans[q][1], plans[q][2], car=q, offset=plans[q][3],
+                                    coast=-1.0)
+                for q in range(2)}
+        obs, rew, dones, trunc, infos = env.step(acts)
+        cs, ad = env.cars, env.agents_data
+        row = dict(
+            actions=np.stack([acts["0"], acts["1"]]), obs=np.stack([obs["0"], obs["1"]]),
+            reward=[float(rew["0"]), float(rew["1"])], done=bool(dones["0"]), done_all=bool(dones["__all__"]),
+            truncated=bool(trunc), placement=[int(infos[f"{q}"].get("placement", 0)) for q in range(2)],
+            info_speed=[float(infos[f"{q}"]["speed"]) for q in range(2)],
+            info_progress=[float(infos[f"{q}"]["progress"]) for q in range(2)],
+            x=[float(c.x) for c in cs], y=[float(c.y) for c in cs], angle=[float(c.angle) for c in cs],
+            vx=[float(c.vx) for c in cs], vy=[float(c.vy) for c in cs], progress=[float(c.progress) for c in cs],
+            crashed=[bool(c.crashed) for c in cs], finished=[bool(c.finished) for c in cs],
+            has_crashed=[bool(d["has_crashed"]) for d in ad],
+            finished_step=[(-1 if d["finished_step"] is None else d["finished_step"]) for d in ad],
+            last_progress=[float(d["last_progress"]) for d in ad],
+            last_steering=[float(d["last_steering"]) for d in ad],
+            cp=[(d["checkpoints"][0.25], d["checkpoints"][0.50], d["checkpoints"][0.75]) for d in ad],
+            steps=env.steps,
+            contact=bool(cs[0].check_car_collision([cs[1]])) if measure else False,
+            car_rays=_car_rays(env) if measure else 0)
+        for k in _MULTI_STEP_COLS:
+            cols[k].append(row[k])
+        n += 1
+        if dones["__all__"]:
+            break
+    else:
+        raise AssertionError("episode did not end")
+    return reset + (n,)
+
+
+# Two-car episode plans: (slot, start order, car 0's plan, car 1's plan), a plan being
+# (gain, speed cap, noise, lateral offset of the target, controller seed).  Steady cars aim at
+# their own side of the track, side-by-side pairs at the same line (they lean on each other),
+# reckless cars (gain 1, no cap, steering noise 1.5) leave the track within a few bends.  The car
+# that starts on the -normal side (the first of the start order) aims at negative offsets.
+_RECKLESS = (1.0, 40.0, 1.5)
+TRAJ_MULTI_PLANS = (
+    # car 1 reckless: crashes early and stays frozen; car 0 drives the lap alone and finishes
+    (16, 0, (3.0, 20.0, 0.05, -2.5, 11), _RECKLESS + (2.5, 12)),
+    # car 0 reckless, leaning on car 1 before it crashes; only car 1 finishes, > 200 steps later
+    (1, 1, _RECKLESS + (2.5, 21), (3.0, 20.0, 0.05, -2.5, 22)),
+    # both reckless: contact, then both off the track; nobody finishes, placement by progress
+    (2, 1, _RECKLESS + (2.5, 31), (1.0, 30.0, 1.5, -2.5, 32)),
+    # car 1 reckless, car 0 crawling at speed 1.9: truncated at 3,000 steps, nobody finished
+    (0, 0, (3.0, 1.9, 0.0, -2.5, 51), _RECKLESS + (2.5, 52)),
+    # side by side for a whole lap, targets 2.4 apart (the cars are 2 wide), car 1 the slower one
+    (16, 0, (3.0, 20.0, 0.05, -1.2, 43), (3.0, 18.0, 0.05, 1.2, 44)),
+)
+
+
+def _pack_multi(cols):
+    out = {}
+    for k in _MULTI_STEP_COLS:
+        a = np.array(cols[k])
+        if a.dtype == object:
+            raise TypeError(k)
+        out[k] = a
+    out["cp"] = out["cp"].astype(np.uint8)
+    out["placement"] = out["placement"].astype(np.int8)
+    out["finished_step"] = out["finished_step"].astype(np.int32)
+    out["steps"] = out["steps"].astype(np.int32)
+    out["car_rays"] = out["car_rays"].astype(np.uint8)
+    return out
+
+
+def gen_traj_multi(track, multi_racing_env, recs_tracks, plans=None):
+    """traj_multi.npz: whole two-car episodes of MultiRacingEnv (multi_racing_env.py:118-269)
+    from its own reset to dones['__all__'], both cars driven by scripted controllers; per
+    episode slot / order / length / reset rows, per step what the env returned and its
+    state afterwards (tests/multi_traj_cases.py names the census the set must meet).  Then
+    the two shortest episodes again through the reference's SelfPlayWrapper
+    (environment/wrappers.py:29-55) for agent_idx 0 and 1, the opponent replaying the other
+    car's recorded actions: asserted equal to the matching car's rows (done == done_all), so
+    only ``wrap_episode`` / ``wrap_len`` are stored."""
+    import torch
+    _repo_on_path()
+    import environment.wrappers as wrappers
+    from tests import multi_traj_cases as mtc
+    plans = TRAJ_MULTI_PLANS if plans is None else plans
+    cols = {k: [] for k in _MULTI_STEP_COLS}
+    ep = {k: [] for k in ("slot", "order", "reset_obs", "reset_x", "reset_y", "reset_angle")}
+    off = [0]
+    state0 = np.random.get_state()
+    for ti, first, p0, p1 in plans:
+        env = _multi_env(multi_racing_env, recs_tracks, ti)
+        obs0, x0, y0, a0, n = _multi_episode(env, first, (p0, p1), cols)
+        ep["slot"].append(ti); ep["order"].append(first); ep["reset_obs"].append(obs0)
+        ep["reset_x"].append(x0); ep["reset_y"].append(y0); ep["reset_angle"].append(a0)
+        off.append(off[-1] + n)
+        print(f"traj_multi slot {ti} order {first}: {n} steps, finished={[c.finished for c in env.cars]} "
+              f"crashed={[c.crashed for c in env.cars]} placement={cols['placement'][-1]}")
+    assert all(np.array_equal(a, b) for a, b in zip(state0[1:3], np.random.get_state()[1:3])), "global RNG was used"
+    out = _pack_multi(cols)
+    out.update({k: np.array(v) for k, v in ep.items()})
+    out["off"] = np.array(off, dtype=np.int64)
+    # --- SelfPlayWrapper rows
+    L = np.diff(out["off"])
+    short = [int(e) for e in np.argsort(L, kind="stable")[:2]]
+    wrap_len = [int(min(L[e], 400)) for e in short]
+
+    class _Opponent:
+        def __init__(self, rows):
+            self.rows, self.t = rows, 0
+
+        def get_action_and_value(self, obs_tensor):
+            a = torch.from_numpy(self.rows[self.t][None].copy())
+            self.t += 1
+            return a, None, None, None
+
+    for e, n in zip(short, wrap_len):
+        a = int(out["off"][e])
+        for idx in (0, 1):
+            env = _multi_env(multi_racing_env, recs_tracks, int(out["slot"][e]))
+            w = wrappers.SelfPlayWrapper(env, agent_idx=idx)
+            w.set_opponent(_Opponent(out["actions"][a:a + n, 1 - idx]))
+            obs, _ = _forced_reset(lambda: w.reset(seed=0), int(out["order"][e]))
+            assert np.array_equal(obs, out["reset_obs"][e][idx])
+            for t in range(n):
+                obs, rew, done, trunc, info = w.step(out["actions"][a + t, idx])
+                assert np.array_equal(obs, out["obs"][a + t, idx]) and float(rew) == out["reward"][a + t, idx]
+                assert bool(done) == bool(out["done_all"][a + t]) and bool(trunc) == bool(out["truncated"][a + t])
+        print(f"traj_multi wrapper: episode {e}, {n} steps, agent_idx 0 and 1 equal the recorded rows")
+    out["wrap_episode"] = np.array(short, dtype=np.int64)
+    out["wrap_len"] = np.array(wrap_len, dtype=np.int64)
+    c = mtc.census(out)
+    for e in c["episodes"]:
+        print("  ", e)
+    print(f"traj_multi census: contact steps {c['contact']} (longest run {c['contact_run']}), "
+          f"car-ray steps {c['car_ray_steps']}, slots {c['slots']}, orders {c['orders']}")
+    mtc.check_census(c, [r["width"] for r in recs_tracks])
+    mtc.check_placement_column(out)
+    _save("traj_multi.npz", **out)
+
+
+# eval_multi plans per (track, run): car 0's and car 1's (gain, speed cap, noise, offset); one
+# default_rng per car, seeded 9100 + 10 * episode + car.
+EVAL_MULTI_SEED = 5  # its shuffle stream starts 0, 1, 0, 0, 1, 1, 1, 0, 1: the offsets below follow it
+EVAL_MULTI_PLANS = {
+    (0, 0): ((3.0, 20.0, 0.05, -2.0), (3.0, 15.0, 0.05, 2.0)),      # car 0 finishes first
+    (0, 1): ((3.0, 15.0, 0.05, 2.0), (3.0, 20.0, 0.05, -2.0)),      # only car 1 finishes
+    (1, 0): (_RECKLESS + (-2.0,), (1.0, 30.0, 1.5, 2.0)),           # both crash
+    (1, 1): ((3.0, 1.5, 0.0, -2.0), _RECKLESS + (2.0,)),            # truncated at 3,000 steps
+    (2, 0): (_RECKLESS + (2.0,), (3.0, 20.0, 0.05, -2.0)),          # car 0 crashes, car 1 finishes
+    (2, 1): ((3.0, 20.0, 0.05, 2.0), _RECKLESS + (-2.0,)),          # car 1 crashes, car 0 finishes
+    (3, 0): (_RECKLESS + (2.0,), (1.0, 30.0, 1.5, -2.0)),           # both crash
+    (3, 1): ((3.0, 18.0, 0.05, -1.0), (3.0, 20.0, 0.05, 1.0)),      # side by side, car 1 finishes
+}
+
+
+def gen_eval_multi(track, multi_racing_env, plans=None):
+    """eval_multi.npz: utils/metrics.py:80-150 eval_multi_agent itself on
+    rx.evaluate.eval_pool(4, 2)'s protocol (gen_eval_metrics' pool and width rule), the agent a
+    scripted stand-in whose get_action_and_value is called twice per step (car 0, then car 1).
+    np.random.seed(S) once before the first episode; every reset's order is recorded and
+    asserted equal to S's stream of np.random.shuffle([0, 1]) calls: nothing else consumed the
+    global RNG.  A ninth call repeats the first episode with max_steps=40 (placement None)."""
+    import torch
+    sys.path.insert(0, REF)
+    from utils.metrics import eval_multi_agent
+    plans = EVAL_MULTI_PLANS if plans is None else plans
+    np.random.seed(0)
+    pool = track.gen_tracks(num_tracks=4, seed=42)
+    widths = [np.random.RandomState(42 + i).randint(4, 10) for i in range(4)]
+    S = EVAL_MULTI_SEED
+    keys = ("total_reward", "progress", "finished", "crashed", "speed", "placement", "steps", "total_distance",
+            "distance_per_step")
+    out = {k: [] for k in keys}
+    acts, off, orders, fin_cars = [], [0], [], []
+
+    class Scripted:
+        def __init__(self, env, plan, seeds):
+            self.env, self.plan, self.log, self.calls = env, plan, [], 0
+            self.rngs = [np.random.default_rng(s) for s in seeds]
+
+        def get_action_and_value(self, obs_tensor):
+            q = self.calls % 2
+            self.calls += 1
+            a = _controller(self.env, self.rngs[q], *self.plan[q][:3], car=q, offset=self.plan[q][3], coast=-1.0)
+            self.log.append(a)
+            return torch.from_numpy(a[None]), None, None, None
+
+    def order_of(env):  # the car on the -normal side of the start line is first in agent_order
+        n0 = env.track.normals[0]
+        s = [(c.x - env.track.waypoints[0][0]) * n0[0] + (c.y - env.track.waypoints[0][1]) * n0[1] for c in env.cars]
+        return 0 if s[0] < s[1] else 1
+
+    def episode(t, r, i, max_steps):
+        env = multi_racing_env.MultiRacingEnv(num_agents=2, num_sensors=11, track_pool=pool, track_id=t,
+                                              track_width=widths[r])
+        agent = Scripted(env, plans[(t, r)], (9100 + 10 * i, 9101 + 10 * i))
+        reset = env.reset
+
+        def recording_reset(*a, **k):
+            res = reset(*a, **k)
+            orders.append(order_of(env))
+            return res
+        env.reset = recording_reset
+        m = eval_multi_agent(env, agent, "cpu", max_steps=max_steps)
+        assert len(agent.log) == 2 * m["steps"]
+        fin_cars.append([bool(c.finished) for c in env.cars])
+        return m, np.array(agent.log, dtype=np.float32).reshape(-1, 2, 2)
+
+    np.random.seed(S)
+    eps = [(t, r) for t in range(4) for r in range(2)]
+    for i, (t, r) in enumerate(eps + [eps[0]]):
+        m, a = episode(t, r, 0 if i == len(eps) else i, 40 if i == len(eps) else 3000)
+        for k in keys:
+            v = m[k]
+            out[k].append(0 if (k == "placement" and v is None) else v)
+        acts.append(a)
+        off.append(off[-1] + len(a))
+        print(f"eval_multi track {t} run {r}: {m}")
+    st = np.random.RandomState(S)
+    want = []
+    for _ in orders:
+        o = [0, 1]
+        st.shuffle(o)
+        want.append(o[0])
+    assert orders == want, (orders, want)
+    print(f"eval_multi: the {len(orders)} recorded start orders {orders} equal np.random.seed({S})'s shuffle stream")
+    assert out["placement"][-1] == 0 and out["steps"][-1] == 40 and len(acts[-1]) == 40
+    # both branches of the car choice (metrics.py:127-138), a crash ending and a truncation
+    assert [True, False] in fin_cars[:8] and [False, True] in fin_cars[:8], fin_cars
+    ended = [(f, s, p) for f, s, p in zip(fin_cars[:8], out["steps"][:8], out["placement"][:8])]
+    assert any(not any(f) and s < 3000 and p > 0 for f, s, p in ended), "no crash ending"
+    assert any(not any(f) and s == 3000 and p > 0 for f, s, p in ended), "no truncation"
+    print("eval_multi episodes (cars finished, steps, placement):", ended)
+    res = {}
+    for k, v in out.items():
+        dt = {"steps": np.int64, "placement": np.int64, "finished": np.uint8, "crashed": np.uint8}.get(k, np.float64)
+        res[k] = np.array(v, dtype=dt)
+    res["actions"] = np.concatenate(acts).astype(np.float32)
+    res["off"] = np.array(off, dtype=np.int64)
+    res["orders"] = np.array(orders, dtype=np.uint8)
+    res["widths"] = np.array(widths, dtype=np.int64)
+    res["num_runs"] = np.array(2)
+    res["seed"] = np.array(S)
+    res["max_steps"] = np.array([3000] * 8 + [40], dtype=np.int64)
+    res["finished_cars"] = np.array(fin_cars, dtype=np.uint8)
+    res["cp"], res["cp_off"] = _pack_ragged(pool)
+    _save("eval_multi.npz", **res)
 
 
 def gen_gae():
@@ -1082,7 +1401,7 @@ def gen_line_counts():
 def main(argv):
     want = set(argv[1:]) or {"geometry", "raycast", "step_single", "traj_single", "step_multi", "gae", "agent",
                              "ppo_update", "ppo_update_mb32k", "schedules", "eval_metrics", "line_counts",
-                             "lattice", "placed"}
+                             "lattice", "placed", "traj_multi", "eval_multi"}
     if "line_counts" in want:
         gen_line_counts()
         want.discard("line_counts")
@@ -1099,7 +1418,7 @@ def main(argv):
         return
     track, car, racing_env, multi_racing_env = _import_reference()
     recs = None
-    if want & {"geometry", "raycast", "step_single", "traj_single", "step_multi"}:
+    if want & {"geometry", "raycast", "step_single", "traj_single", "step_multi", "traj_multi"}:
         recs = gen_geometry(track) if "geometry" in want else _tracks_set(track)[0]
     if "raycast" in want:
         gen_raycast(track, recs)
@@ -1109,6 +1428,10 @@ def main(argv):
         gen_traj_single(track, racing_env, recs)
     if "step_multi" in want:
         gen_step_multi(track, multi_racing_env, recs)
+    if "traj_multi" in want:
+        gen_traj_multi(track, multi_racing_env, recs)
+    if "eval_multi" in want:
+        gen_eval_multi(track, multi_racing_env)
     if "lattice" in want:
         gen_lattice(track, racing_env, multi_racing_env)
     if "placed" in want:
